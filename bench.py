@@ -6,6 +6,7 @@ He-uniform synthetic weights (no checkpoints exist offline). One "step" = one te
 call over the whole per-GPU batch, inputs already resident in HBM.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--model adain|wct|sanet|...]
+                    [--dump-outputs DIR] [--full]
     python bench.py --config 4 [--gpus 8]     # BASELINE configs[4]: 1024^2, 128 images
                                               # split over the GPUs, host gather timed
 
@@ -19,16 +20,26 @@ splits G images over the ranks (strong scaling). --gather copies every step's ou
 one host buffer shared by all ranks (/dev/shm, each rank's slice page-locked) inside the
 timed region: the "results gathered on the host" of BASELINE configs[4].
 
-The JSON line also carries:
+A plain run sets up, runs the warm-up and the timed steps, and prints one JSON line:
+`value` (images/s) and `ms_per_step` (milliseconds per timed step) over exactly --steps
+steps. --dump-outputs DIR then writes what the last timed step returned as DIR/<name>.npy
+(at most 64 MB; larger arrays as a fixed seeded sample, see dump_outputs); the inputs and
+weights are seeded, so two builds can be compared output for output. --full adds the
+measurements that take runs of their own: the CPU baseline, the stand-alone AdaIN kernel
+pair and, in a default run, the other BASELINE configs as `configs` sub-records
+(--no-cpu-baseline / --no-configs drop those two again).
+
+The JSON line also carries (from HIP events around the launches of the timed steps):
   roofline     the dominant kernel's algorithmic FLOP (or bytes) per launch divided by
                its mean launch time, measured with HIP events on the launch stream
                during the timed steps, against the MI355X peak; "traffic" is that
                launch's HBM bytes from the committed per-dispatch PMC table;
-  roofline_adain  the same for the AdaIN statistics+apply pair (HBM-bound);
-  roofline_adain_stats  calc_mean_std alone (the AdaIN statistics path: one read of the
-               feature, 4 B per element) against the HBM peak;
-  cpu_baseline the CPU oracle (PyTorch-CPU restatement of the reference) timed on this
-               host on a bounded sample (rank 0, N=1 only).
+  roofline_adain  the same for the AdaIN statistics+apply pair (HBM-bound; where the model
+               path fuses the pair away, measured stand-alone under --full, else null);
+  roofline_adain_stats  --full: calc_mean_std alone (the AdaIN statistics path: one read of
+               the feature, 4 B per element) against the HBM peak;
+  cpu_baseline --full: the CPU oracle (PyTorch-CPU restatement of the reference) timed on
+               this host on a bounded sample (rank 0, N=1 only).
 """
 from __future__ import annotations
 
@@ -464,10 +475,39 @@ def selftest_model():
     return _M()
 
 
+DUMP_BUDGET = 64 * 10 ** 6   # --dump-outputs: bytes written per run, all arrays together
+DUMP_SEED = 0
+
+
+def dump_outputs(dirname, arrays, rank=0, world=1):
+    """Write each (name, tensor) of `arrays` as dirname/<name>.npy (float32, or float64 for a
+    float64 tensor; <name>.rank<r>.npy in a multi-rank run). The arrays share DUMP_BUDGET
+    equally: one that exceeds its share is written as a fixed sample, its elements at
+    sorted flat indices drawn from numpy's default_rng(DUMP_SEED), the same indices for the
+    same shape in every run."""
+    import numpy as np
+    import torch
+    os.makedirs(dirname, exist_ok=True)
+    share = DUMP_BUDGET // (max(len(arrays), 1) * world) - 4096  # (.npy header)
+    for name, t in arrays:
+        t = torch.as_tensor(t).detach()
+        if t.dtype != torch.float64:
+            t = t.float()
+        keep = share // t.element_size()
+        if t.numel() > keep:
+            idx = np.sort(np.random.default_rng(DUMP_SEED).integers(0, t.numel(), size=keep))
+            t = t.reshape(-1)[torch.from_numpy(idx).to(t.device)]
+        suffix = f".rank{rank}" if world > 1 else ""
+        np.save(os.path.join(dirname, f"{name}{suffix}.npy"), t.cpu().numpy())
+
+
 def run_workload(kind, size, batch, gbatch, gather, micro, steps, warmup, world, rank, dev,
-                 tgroup, cuda=True):
+                 tgroup, cuda=True, dump=None):
     """Build `kind` with synthetic weights, run `warmup` untimed and `steps` timed steps (a
-    barrier + device sync on both sides, MAX over ranks) and return the measurement."""
+    barrier + device sync on both sides, MAX over ranks) and return the measurement. With
+    `dump`, what the last timed step returned to its caller is written there afterwards
+    (dump_outputs): the stylised images of the step's last test() call, or a training /
+    forward step's losses; with a host gather, rank 0 also writes the gathered batch."""
     import torch
     import torch.distributed as dist
     from rpst import ops, synth
@@ -486,6 +526,7 @@ def run_workload(kind, size, batch, gbatch, gather, micro, steps, warmup, world,
     # image i of the global batch is the same tensor whatever the rank count
     content = torch.from_numpy(synth.image_range(1000, (total, 3, size, size), start, end)).to(dev)
     style = torch.from_numpy(synth.image_range(2000, (total, 3, size, size), start, end)).to(dev)
+    last = {}  # the losses dict of the latest training / forward step (--dump-outputs)
 
     if kind in TRAIN_KINDS:
         from rpst.shard import GradientAllReduce
@@ -496,7 +537,8 @@ def run_workload(kind, size, batch, gbatch, gather, micro, steps, warmup, world,
 
         def step():
             optimizer.zero_grad()
-            _, tot = model(content, style)
+            losses, tot = model(content, style)
+            last["losses"] = {k: v.detach() for k, v in losses.items()}
             tot.backward()
             if reduce_grads is not None:
                 reduce_grads()
@@ -514,7 +556,8 @@ def run_workload(kind, size, batch, gbatch, gather, micro, steps, warmup, world,
     if kind == "forward":
         def step():
             with torch.no_grad():
-                _, tot = model(content, style)
+                losses, tot = model(content, style)
+            last["losses"] = losses
             return tot
     elif kind not in TRAIN_KINDS:
         def step():
@@ -593,6 +636,15 @@ def run_workload(kind, size, batch, gbatch, gather, micro, steps, warmup, world,
             gathered_ok = gathered_ok and torch.equal(host.full, model.test(*full))
         host_rec = {"pinned": host.pinned, "bytes_per_step": total * 3 * size * size * 4,
                     "all_finite": gathered_ok}
+    if dump:
+        if "losses" in last:
+            arrays = sorted(last["losses"].items())
+        else:
+            arrays = [("output", out)]
+            if host is not None and rank == 0:
+                arrays.append(("gathered", host.full))
+        dump_outputs(dump, arrays, rank, world)
+    if host is not None:
         if world > 1:
             dist.barrier(group=tgroup)
         host.close()
@@ -717,12 +769,24 @@ def main():
                     help="copy each step's output into a shared host buffer (timed)")
     ap.add_argument("--micro-batch", type=int, default=None,
                     help="images per test() call within a step (default: the whole batch)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline run also measure the CPU baseline, the stand-alone "
+                         "AdaIN kernel pair (roofline_adain / roofline_adain_stats) and, in a "
+                         "default run, the other BASELINE configs")
+    ap.add_argument("--no-cpu-baseline", action="store_true",
+                    help="with --full: skip the CPU baselines")
     ap.add_argument("--no-configs", action="store_true",
-                    help="default run only: skip the configs[0], [2]-[4] sub-records")
+                    help="with --full, default run only: skip the configs[0], [2]-[4] sub-records")
     ap.add_argument("--layer-order", default=None,
-                    help="write the traced launch names of one step (tools/pmc_traffic.py)")
+                    help="with --full: write the traced launch names of one step "
+                         "(tools/pmc_traffic.py)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps write what the last one returned as DIR/<name>.npy")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    if args.layer_order and not args.full:
+        ap.error("--layer-order needs --full (it names the stand-alone AdaIN launches)")
 
     default_run = args.config is None and args.model is None
     model_kind, size, batch, gbatch, gather, micro = CONFIGS[args.config or 1]
@@ -763,10 +827,10 @@ def main():
         dev = torch.device("cpu")
 
     meas = run_workload(model_kind, size, batch, gbatch, gather, micro, args.steps, args.warmup,
-                        world, rank, dev, tgroup, cuda)
+                        world, rank, dev, tgroup, cuda, args.dump_outputs)
     summary, dt = meas["summary"], meas["dt"]
     sub = []
-    if cuda and default_run and not args.no_configs:
+    if args.full and cuda and default_run and not args.no_configs:
         # every BASELINE config in the same driver-timed run: configs[2] / [3] (one GPU's
         # batch) on rank 0 of a 1-GPU run, configs[4] (128 images at 1024^2 split over the
         # ranks, host gather) at every GPU count
@@ -811,8 +875,9 @@ def main():
             rec["roofline_stack"] = stack_roofline(summary, args.steps, dt)
             if model_kind == "wct":
                 rec["roofline_wct"] = wct_roofline(summary, meas.get("wct_phases"))
-            adain_summary = measure_adain_standalone(dev, min(meas["B"], 32), 256,
-                                                     min(size, 512) ** 2)
+            # (a plain run reports the AdaIN pair only where the timed steps launched it)
+            adain_summary = measure_adain_standalone(
+                dev, min(meas["B"], 32), 256, min(size, 512) ** 2) if args.full else {}
             rec["roofline_adain"] = adain_roofline(
                 summary if any(k.startswith("adain") for k in summary) else adain_summary)
             rec["roofline_adain_stats"] = stats_roofline(adain_summary)
@@ -821,7 +886,7 @@ def main():
                 order["adain_name"] = next((k for k in adain_summary if k.startswith("adain")), None)
                 order["stats_name"] = next((k for k in adain_summary if k.startswith("stats")), None)
                 json.dump(order, open(args.layer_order, "w"), indent=1)
-            if world == 1 and not args.no_cpu_baseline:
+            if args.full and world == 1 and not args.no_cpu_baseline:
                 rec["cpu_baseline"] = cpu_baseline(model_kind, size)
             else:
                 rec["cpu_baseline"] = None

@@ -27,13 +27,13 @@ def pytest_configure(config):
 
 @pytest.fixture(scope="session")
 def golden():
-    import numpy as np
+    from helpers import load_golden  # (a set over 1 MiB is stored in parts)
 
     cache = {}
 
     def load(name):
         if name not in cache:
-            cache[name] = dict(np.load(os.path.join(GOLDEN, name + ".npz"), allow_pickle=False))
+            cache[name] = load_golden(name)
         return cache[name]
 
     return load

@@ -92,7 +92,7 @@ def gen_stats(net):
         out[f"cmean{i}"] = cm.numpy()
         out[f"cstd{i}"] = cs.numpy()
         out[f"adain{i}"] = o.numpy()
-    np.savez_compressed(os.path.join(HERE, "stats.npz"), n=len(shapes), **out)
+    helpers.save_golden("stats", n=len(shapes), **out)  # (over 1 MiB: stored in parts)
 
 
 def rp_config(hidden, blocks=5):
@@ -186,8 +186,7 @@ def gen_wct(net):
         out[f"net_style{i}"] = s
         out[f"net_out{i}"] = y.numpy()
         ncase += 1
-    np.savez_compressed(os.path.join(HERE, "wct.npz"), nmat=len(mats), ncase=len(cases),
-                        nnet=ncase, **out)
+    helpers.save_golden("wct", nmat=len(mats), ncase=len(cases), nnet=ncase, **out)
 
 
 def gen_wct_large(net):
@@ -486,7 +485,7 @@ def gen_grads(net):
             else:
                 assert p.grad is None, name
         out[f"names{i}"] = np.array(names)
-    np.savez_compressed(os.path.join(HERE, "grads.npz"), n=len(cases), **out)
+    helpers.save_golden("grads", n=len(cases), **out)
 
 
 def gen_grads_wct(net):
@@ -703,7 +702,7 @@ def gen_grad_floors(net):
     out = {}
     for family in ("grads", "grads_wct", "grads_sam", "grads_src", "grads_ms",
                    "grads_adaptive"):
-        g = np.load(os.path.join(HERE, f"{family}.npz"))
+        g = helpers.load_golden(family)
         for i in range(int(g["n"])):
             names = [str(n) for n in g[f"names{i}"]]
             sq, lsq = {}, {}

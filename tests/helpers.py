@@ -12,6 +12,65 @@ TOL_NET = 1e-4         # full networks in fp32, rel-L2
 TOL_NET_MAXABS = 5e-4  # full networks: max-abs <= TOL_NET_MAXABS * max|ref|
 
 
+GOLDEN_DIR = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
+# A golden set is one <name>.npz, or, where that would pass 1 MiB (the size limit of a
+# committed file), <name>.part00.npz, <name>.part01.npz, ...: each part holds at most
+# GOLDEN_PART_BYTES of array data, and an array larger than GOLDEN_PIECE_BYTES is stored as
+# consecutive pieces of its flattened data, "<key>::0", "<key>::1", ... beside "<key>::shape".
+GOLDEN_PART_BYTES = 960 * 1024
+GOLDEN_PIECE_BYTES = 480 * 1024
+
+
+def save_golden(name, **arrays):
+    """Write the golden set `name` (replacing its files); load_golden returns it unchanged."""
+    import glob
+    for old in glob.glob(os.path.join(GOLDEN_DIR, name + ".npz")) + glob.glob(
+            os.path.join(GOLDEN_DIR, name + ".part[0-9][0-9].npz")):
+        os.remove(old)
+    entries = []
+    for key, a in arrays.items():
+        a = np.asarray(a)
+        assert "::" not in key, key
+        if a.nbytes <= GOLDEN_PIECE_BYTES:
+            entries.append((key, a))
+            continue
+        flat = np.ascontiguousarray(a).reshape(-1)
+        per = GOLDEN_PIECE_BYTES // a.itemsize
+        entries.append((key + "::shape", np.array(a.shape, dtype=np.int64)))
+        entries += [(f"{key}::{j}", flat[o:o + per])
+                    for j, o in enumerate(range(0, flat.size, per))]
+    if sum(a.nbytes for _, a in entries) <= GOLDEN_PART_BYTES:
+        np.savez_compressed(os.path.join(GOLDEN_DIR, name + ".npz"), **dict(entries))
+        return
+    parts, size = [{}], 0
+    for key, a in entries:
+        if size + a.nbytes > GOLDEN_PART_BYTES:
+            parts.append({})
+            size = 0
+        parts[-1][key] = a
+        size += a.nbytes
+    for i, part in enumerate(parts):
+        np.savez_compressed(os.path.join(GOLDEN_DIR, f"{name}.part{i:02d}.npz"), **part)
+
+
+def load_golden(name):
+    """The golden set `name` as a dict of arrays, whichever way it is stored."""
+    import glob
+    paths = sorted(glob.glob(os.path.join(GOLDEN_DIR, name + ".part[0-9][0-9].npz")))
+    raw = {}
+    for p in paths or [os.path.join(GOLDEN_DIR, name + ".npz")]:
+        raw.update(np.load(p, allow_pickle=False))
+    out = {}
+    for key, a in raw.items():
+        if "::" not in key:
+            out[key] = a
+        elif key.endswith("::shape"):
+            base = key[:-len("::shape")]
+            n = sum(1 for k in raw if k.startswith(base + "::")) - 1
+            out[base] = np.concatenate([raw[f"{base}::{j}"] for j in range(n)]).reshape(a)
+    return out
+
+
 def rel_l2(a, b):
     a = torch.as_tensor(a).double().cpu()
     b = torch.as_tensor(b).double().cpu()

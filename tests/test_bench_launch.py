@@ -69,6 +69,47 @@ def test_inference_creates_no_rccl_group():
     assert rec["config"]["process_group"] == "gloo"
 
 
+def test_dump_outputs_writes_last_step_and_repeats(tmp_path):
+    """--dump-outputs: the last timed step's result as float32 .npy, identical from run to
+    run (seeded inputs); --steps sets the number of timed steps."""
+    import numpy as np
+    import torch
+    sys.path.insert(0, ROOT)
+    runs = []
+    for d in ("a", "b"):
+        rec = _bench("--steps", "3", "--warmup", "1", "--size", "8",
+                     "--dump-outputs", str(tmp_path / d))
+        assert rec["steps"] == 3 and rec["ms_per_step"] > 0
+        assert os.listdir(tmp_path / d) == ["output.npy"]
+        runs.append(np.load(tmp_path / d / "output.npy"))
+    assert runs[0].dtype == np.float32 and runs[0].shape == (4, 3, 8, 8)
+    assert np.array_equal(runs[0], runs[1])
+    sys.path.insert(0, os.path.join(ROOT, "rp-style-transfer_amd"))
+    from rpst import synth
+    import bench
+    c, s = (torch.from_numpy(synth.image(seed, (4, 3, 8, 8))) for seed in (1000, 2000))
+    assert np.array_equal(runs[0], bench.selftest_model().test(c, s).numpy())
+
+
+def test_dump_outputs_samples_within_budget(tmp_path, monkeypatch):
+    """An output over its share of the budget is written as a fixed sample: the same sorted
+    indices every time, float64 kept, everything else as float32."""
+    import numpy as np
+    import torch
+    sys.path.insert(0, ROOT)
+    import bench
+    monkeypatch.setattr(bench, "DUMP_BUDGET", 2 * (4096 + 400))
+    big = torch.arange(1000, dtype=torch.float64).reshape(10, 100)
+    small = torch.arange(50, dtype=torch.float16)
+    bench.dump_outputs(str(tmp_path), [("big", big), ("small", small)])
+    b, s = np.load(tmp_path / "big.npy"), np.load(tmp_path / "small.npy")
+    assert b.dtype == np.float64 and b.shape == (50,) and s.dtype == np.float32
+    assert np.array_equal(s, np.arange(50)) and np.all(np.diff(b) >= 0)
+    idx = np.sort(np.random.default_rng(bench.DUMP_SEED).integers(0, 1000, size=50))
+    assert np.array_equal(b, idx.astype(np.float64))
+    assert sum(os.path.getsize(tmp_path / f) for f in os.listdir(tmp_path)) <= bench.DUMP_BUDGET
+
+
 def test_cpu_share_follows_omp_num_threads(monkeypatch):
     sys.path.insert(0, ROOT)
     import bench

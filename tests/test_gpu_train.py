@@ -189,7 +189,7 @@ def test_training_step_matches_cpu_autograd(cuda, hidden, shape):
 
 
 def test_training_gradients_match_reference(cuda, golden):
-    """Gradients pinned to the REFERENCE (tests/golden/grads.npz: the reference's own
+    """Gradients pinned to the REFERENCE (tests/golden/grads.part*.npz: the reference's own
     AdaINRPNet.forward + total_loss.backward(), adain_rp.py:110-138): hidden 4 at 32x32 and
     the benched width, hidden 16, at 128x128. Per-tensor rel-L2 <= 1e-4."""
     g = golden("grads")

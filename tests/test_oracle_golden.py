@@ -421,3 +421,26 @@ def test_state_dict_keys_match_reference(name):
             "vgg": lambda: net.vgg, "decoder": lambda: net.decoder}[name]()
     got = [[k, list(v.shape)] for k, v in mine.state_dict().items()]
     assert got == ref
+
+
+def test_golden_sets_round_trip_and_stay_under_one_mib(tmp_path, monkeypatch):
+    """helpers.save_golden / load_golden: a set over 1 MiB is stored in parts, each under
+    1 MiB, and comes back bit-identical; no committed golden file passes 1 MiB."""
+    import helpers
+    for f in os.listdir(GOLD):
+        assert os.path.getsize(os.path.join(GOLD, f)) <= 2 ** 20, f
+    monkeypatch.setattr(helpers, "GOLDEN_DIR", str(tmp_path))
+    rng = np.random.default_rng(0)
+    big = {"n": np.array(3), "names0": np.array(["a.weight", "b.bias"]),
+           "x": rng.standard_normal((300, 1031)).astype(np.float32),
+           "y": rng.standard_normal((129, 1000)), "z": rng.standard_normal((7, 5))}
+    for name, arrays in (("big", big), ("small", {"n": big["n"], "z": big["z"]})):
+        helpers.save_golden(name, **arrays)
+        back = helpers.load_golden(name)
+        assert set(back) == set(arrays)
+        for k, a in arrays.items():
+            assert back[k].dtype == a.dtype and back[k].shape == a.shape
+            assert back[k].tobytes() == a.tobytes()
+    files = sorted(os.listdir(tmp_path))
+    assert "small.npz" in files and "big.part00.npz" in files and "big.npz" not in files
+    assert all(os.path.getsize(tmp_path / f) <= 2 ** 20 for f in files)

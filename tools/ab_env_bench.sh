@@ -6,7 +6,7 @@ O=gpurun_out/${1:-abenv}; shift; mkdir -p $O
 for rep in 1 2; do
   for e in "$@"; do
     f=$O/$(echo $e | tr '=' '_').$rep.json
-    env $e timeout -k 10 300 python bench.py --no-configs --no-cpu-baseline > $f 2> $f.err || { tail $f.err; exit 1; }
+    env $e timeout -k 10 300 python bench.py --full --no-configs --no-cpu-baseline > $f 2> $f.err || { tail $f.err; exit 1; }
     python -c "import json;d=json.load(open('$f'));k=d['kernel_ms_per_step'];print('$e', d['value'], ' '.join(x.split()[1] + ':' + str(round(k[x], 3)) for x in k))"
   done
 done

@@ -6,6 +6,6 @@ O=$R/gpurun_out/${1:-configs}
 mkdir -p $O
 cd $R
 for c in ${CONFIGS:-1 2 3 4}; do
-  timeout -k 10 600 python bench.py --config $c ${EXTRA:-} > $O/config$c.json 2> $O/config$c.err || { tail $O/config$c.err; exit 1; }
+  timeout -k 10 600 python bench.py --full --config $c ${EXTRA:-} > $O/config$c.json 2> $O/config$c.err || { tail $O/config$c.err; exit 1; }
   python -c "import json;d=json.load(open('$O/config$c.json'));r=d['roofline'];print('config $c', d['value'], d['unit'], d['ms_per_step'], r['kernel'], r['frac'], d.get('cpu_baseline'))"
 done

@@ -12,5 +12,5 @@ if [ -n "$AB" ]; then
   ROUNDS=${ROUNDS:-2} LAYERS=${LAYERS:-"128->256 64->128 256->128"} bash tools/ab_variants.sh $AB > $O/ab.log 2>&1 || { tail $O/ab.log; exit 1; }
   cat $O/ab.log
 fi
-timeout -k 10 300 python bench.py > $O/bench.json 2> $O/bench.err || { tail $O/bench.err; exit 1; }
+timeout -k 10 300 python bench.py --full > $O/bench.json 2> $O/bench.err || { tail $O/bench.err; exit 1; }
 cat $O/bench.json

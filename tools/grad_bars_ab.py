@@ -19,7 +19,7 @@ import numpy as np  # noqa: E402
 import torch  # noqa: E402
 
 import network as net  # noqa: E402
-from helpers import (grad_bar, ms_grads_config, rel_l2, rp_config,  # noqa: E402
+from helpers import (grad_bar, load_golden, ms_grads_config, rel_l2, rp_config,  # noqa: E402
                      src_grads_config, synth_)
 from rpst import ops  # noqa: E402
 
@@ -32,7 +32,7 @@ for k in os.environ.get("RPST_TRAIN_F4", "").split(","):
 
 
 def load(n):
-    return np.load(os.path.join(ROOT, "tests", "golden", f"{n}.npz"))
+    return load_golden(n)
 
 
 def model(family, g, i):

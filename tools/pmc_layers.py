@@ -1,7 +1,7 @@
 """Per-layer PMC counter table from rocprofv3 --pmc runs of bench.py (any counters).
 
     cd /tmp && rocprofv3 --pmc SQ_WAVE_CYCLES ... --output-format csv -d <out>/sq_a -o run -- \
-        python3 bench.py --steps 1 --warmup 0 --no-cpu-baseline --layer-order <out>/order.json
+        python3 bench.py --full --steps 1 --warmup 0 --no-cpu-baseline --layer-order <out>/order.json
     python tools/pmc_layers.py <out>/order.json <out>/sq_a [<out>/sq_b ...] > table.csv
 
 Conv dispatches are attributed to layers by position in the step (tools/pmc_traffic.py

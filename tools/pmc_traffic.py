@@ -3,7 +3,7 @@
 FETCH_SIZE and WRITE_SIZE are collected in separate passes (MI355X_MICROARCH.md §HBM):
 
     cd /tmp && rocprofv3 --pmc FETCH_SIZE --output-format csv -d <out>/pmc_fetch -o run -- \
-        python3 bench.py --steps 2 --warmup 1 --no-cpu-baseline --layer-order <out>/order.json
+        python3 bench.py --full --steps 2 --warmup 1 --no-cpu-baseline --layer-order <out>/order.json
     (same with WRITE_SIZE into <out>/pmc_write)
     python tools/pmc_traffic.py <out>/pmc_fetch <out>/pmc_write <out>/order.json \
         profiles/<round>_pmc_traffic.json

@@ -9,5 +9,5 @@ timeout -k 10 400 python -u -m pytest tests/test_gpu_kernels.py tests/test_gpu_f
 tail -2 $O/tests.log
 timeout -k 10 300 python tools/bench_conv.py --layers adain --algo winograd4 --rounds 2 > $O/conv.log 2>&1 || { tail $O/conv.log; exit 1; }
 cat $O/conv.log
-timeout -k 10 300 python bench.py --no-cpu-baseline > $O/bench.json 2> $O/bench.err || { tail $O/bench.err; exit 1; }
+timeout -k 10 300 python bench.py --full --no-cpu-baseline > $O/bench.json 2> $O/bench.err || { tail $O/bench.err; exit 1; }
 python -c "import json;d=json.load(open('$O/bench.json'));print(d['value'], d['roofline']['launch_ms'], d['roofline']['frac']); print(d['kernel_ms_per_step'])"

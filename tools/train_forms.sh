@@ -19,7 +19,7 @@ done
 [ -n "$NOBENCH" ] && exit 0
 for m in train_sanet train_source; do
   for v in "" "RPST_TRAIN_QUARTER=1"; do
-    env $v timeout -k 10 300 python bench.py --model $m --no-cpu-baseline > $O/bench_$m.json 2> $O/bench_$m.err || { tail -3 $O/bench_$m.err; continue; }
+    env $v timeout -k 10 300 python bench.py --full --model $m --no-cpu-baseline > $O/bench_$m.json 2> $O/bench_$m.err || { tail -3 $O/bench_$m.err; continue; }
     python -c "import json;d=json.load(open('$O/bench_$m.json'));print('$m', '$v', d['value'], d['unit'], d['ms_per_step'])"
   done
 done

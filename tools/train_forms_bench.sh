@@ -8,7 +8,7 @@ cd $R
 ALL=adain,multiscale,wct,sanet,source
 for m in train train_wct train_sanet train_multiscale train_source train_adaptive; do
   for v in "RPST_TRAIN_F4=" "RPST_TRAIN_F4=$ALL"; do
-    env $v timeout -k 10 300 python bench.py --model $m --no-cpu-baseline > $O/b.json 2> $O/b.err || { tail -3 $O/b.err; continue; }
+    env $v timeout -k 10 300 python bench.py --full --model $m --no-cpu-baseline > $O/b.json 2> $O/b.err || { tail -3 $O/b.err; continue; }
     python -c "import json;d=json.load(open('$O/b.json'));print('$m', '${v#RPST_TRAIN_F4=}' or 'default', d['value'], d['unit'], d['ms_per_step'])"
   done
 done

@@ -5,7 +5,7 @@ reference's arithmetic), torch GPU fp32, and the kernels under each conv algorit
     python tools/vgg_feat_err.py
 """
 import copy, os, sys, json
-ROOT="/root/repo"
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "tests")); sys.path.insert(0, os.path.join(ROOT, "rp-style-transfer_amd")); sys.path.insert(0, ROOT)
 import numpy as np, torch
 import network as net
