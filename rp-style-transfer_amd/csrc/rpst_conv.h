@@ -176,6 +176,8 @@ __device__ __forceinline__ float combine(const float (&r)[RawN<INOP>::R], bool o
 
 // Sum each of v[0..15] over the 32 lanes of a half-wave. Returns the total of element
 // e = (j >> 1) & 15 (lanes 2e and 2e+1 of the half hold it); 16 shuffles instead of 80.
+// (halfwave_reduce_scatter<16> below computes the same, but conv_mfma_kernel compiles to
+// different code with it, so the kernel keeps this form)
 __device__ __forceinline__ float halfwave_reduce_scatter16(float (&v)[16], int j) {
   float w[8], u[4], t[2];
   bool b = (j & 16) != 0;
@@ -223,22 +225,6 @@ __device__ __forceinline__ float halfwave_reduce_scatter(float (&v)[V], int j) {
   return s;
 }
 
-// Sum each of v[0..7] over the 32 lanes of a half-wave. Returns the total of element
-// e = (j >> 2) & 7 (lanes 4e..4e+3 of the half hold it).
-__device__ __forceinline__ float halfwave_reduce_scatter8(float (&v)[8], int j) {
-  float u[4], t[2];
-  bool b = (j & 16) != 0;
-#pragma unroll
-  for (int i = 0; i < 4; ++i) u[i] = (b ? v[i + 4] : v[i]) + __shfl_xor(b ? v[i] : v[i + 4], 16, 64);
-  b = (j & 8) != 0;
-#pragma unroll
-  for (int i = 0; i < 2; ++i) t[i] = (b ? u[i + 2] : u[i]) + __shfl_xor(b ? u[i] : u[i + 2], 8, 64);
-  b = (j & 4) != 0;
-  float s = (b ? t[1] : t[0]) + __shfl_xor(b ? t[0] : t[1], 4, 64);
-  s += __shfl_xor(s, 2, 64);
-  return s + __shfl_xor(s, 1, 64);
-}
-
 // ---- Winograd F(2x2,3x3) path (rpst_wino.hip) ----------------------------------------
 constexpr int kWinoNTH = 256;  // threads per block
 // tile shape in use: output channels (BM) x rows (TH, x kTW columns) per block
@@ -272,6 +258,65 @@ size_t wino4_mix_floats(int N, int Cin, int Cout);
 int wino4_mix(ConvArgs& a, const double* T, const double* cvec, const float* direct_packed,
               int direct_cout_pad, float* ws, hipStream_t st);
 
+// device helpers shared by the two F(4x4) kernels (rpst_wino4.hip, rpst_wino4q.hip)
+// kernel arguments loaded at their use (s_load through an opaque copy of the kernarg
+// pointer, so the loads are not hoisted out of the loop that contains the use)
+typedef const __attribute__((address_space(4))) ConvArgs* KArgs;
+__device__ __forceinline__ KArgs late_args() {
+  KArgs p = (KArgs)__builtin_amdgcn_kernarg_segment_ptr();
+#if __HIP_DEVICE_COMPILE__  // the host pass only emits the launch stub (no "s" registers)
+  asm volatile("" : "+s"(p));
+#endif
+  return p;
+}
+// buffer resource over `bytes` at p, or over zero records (every access reads 0) if !ok
+// (compiled to a scalar select: no branch splits an MFMA stream around it)
+__device__ __forceinline__ __amdgpu_buffer_rsrc_t rsrc_or_zero(const float* p, unsigned bytes, bool ok) {
+  return __builtin_amdgcn_make_buffer_rsrc((void*)p, (short)0, ok ? (int)bytes : 0, 0x00020000);
+}
+// a wave-uniform value made opaque at this point (not hoisted out of the enclosing loop)
+__device__ __forceinline__ int launder(int v) {
+#if __HIP_DEVICE_COMPILE__
+  asm volatile("" : "+s"(v));
+#endif
+  return v;
+}
+// sum over the 16 lanes of a DPP row, in every lane: four DPP adds (quad xor 1, quad xor 2,
+// half-row mirror, row mirror) instead of four ds_bpermute round trips through the LDS
+__device__ __forceinline__ float row16_sum(float v) {
+  v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0xB1, 0xF, 0xF, false));
+  v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x4E, 0xF, 0xF, false));
+  v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x141, 0xF, 0xF, false));
+  v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x140, 0xF, 0xF, false));
+  return v;
+}
+// branch-free padding resolution (resolve() above, as selects): reflect(1) or zero padding;
+// false for a zero-padding position, v clamped into [0, n) either way
+__device__ __forceinline__ bool resolve_bf(int& v, int n, bool zero_pad) {
+  const bool in = v >= 0 && v < n;
+  const int r = reflect1(v, n);
+  v = zero_pad ? min(max(v, 0), n - 1) : r;
+  return in || !zero_pad;
+}
+// A^T applied to one 6-vector -> 4 values
+__device__ __forceinline__ void at6(const float (&m)[6], float (&p)[4]) {
+  const float s12 = m[1] + m[2], d12 = m[1] - m[2];
+  const float s34 = m[3] + m[4], d34 = m[3] - m[4];
+  p[0] = (m[0] + s12) + s34;
+  p[1] = fmaf(2.f, d34, d12);
+  p[2] = fmaf(4.f, s34, s12);
+  p[3] = fmaf(8.f, d34, d12) + m[5];
+}
+// spatial tile of logical block b (after the co-split digit): row tile fastest, then column
+// tile, then image, on the hardware's round-robin XCD assignment (consecutive blocks on
+// consecutive XCDs). The measurements that settled it are quoted in each kernel's source.
+__device__ __forceinline__ void w4_tile(int b, int tiles_x, int tiles_y, int& tx, int& ty, int& n) {
+  ty = b % tiles_y;
+  b /= tiles_y;
+  tx = b % tiles_x;
+  n = b / tiles_x;
+}
+
 // ---- F(4x4,3x3), position-quarter form (rpst_wino4q.hip) ------------------------------
 // 8 x 64 outputs x 64 channels per 512-thread block, each wave 9 of the 36 positions. Its
 // weight image follows the F(4x4) one in the packed buffer; wino4_launch / wino4_fold /
@@ -300,6 +345,5 @@ inline size_t wino4_image_floats_max(int Cout, int Cin) {
   const size_t q = wino4q_packed_floats(Cout, Cin), p = wino4_packed_floats(Cout, Cin);
   return q > p ? q : p;
 }
-
 
 }  // namespace rpst

@@ -32,7 +32,12 @@
 // prefetched two chunks ahead (its loads come from HBM).
 #include "rpst_conv.h"
 
-#include <cstdlib>
+// timing-only experiments (results wrong; tools/build_variants.sh -DRPST_WINO_DBG=n): bit0 no
+// global loads in the loop, bit1 no LDS reads, bit2 no barrier, bit3 no patch stores, bit4 no
+// weight loads, bit5 no patch loads
+#ifndef RPST_WINO_DBG
+#define RPST_WINO_DBG 0
+#endif
 
 namespace rpst {
 
@@ -92,10 +97,9 @@ int wino_th() { return 4 * (2 / kWMT); }
 // per CU) leaves CUs idle (the 64x64 relu4_1 / relu5_1 layers of SAModel training at B = 8:
 // 128 blocks), so such layers take one co tile per block
 int wino_persist(int in_op, int64_t spatial_blocks) {
-  const char* e = getenv("RPST_WINO_PERSIST");  // A/B switch for the one-load loaders
   if (in_op == RPST_IN_MAXPOOL2 || in_op == RPST_IN_ADD_UPSAMPLE2 || in_op == RPST_IN_ADD_ADAIN)
     return 0;
-  return (e && *e) ? atoi(e) != 0 : spatial_blocks >= 512;
+  return spatial_blocks >= 512;
 }
 
 size_t wino_packed_floats(int Cout, int Cin) { return wino_image_floats(kWMT, Cout, Cin); }
@@ -108,10 +112,7 @@ int wino_pack(const float* w, float* pk, int Cout, int Cin, hipStream_t st) {
 }
 
 // ---- the kernel -------------------------------------------------------------------------
-// DBG (timing experiments only, tools/wino_dbg.sh; results are wrong): bit0 no global
-// loads in the loop, bit1 no LDS reads, bit2 no barrier, bit3 no patch stores, bit4 no
-// weight loads, bit5 no patch loads; 256 = the production kernel through that switch.
-template <int INOP, int MT, bool PERSIST, int DBG = 0>
+template <int INOP, int MT, bool PERSIST, int DBG = RPST_WINO_DBG>
 __global__ __launch_bounds__(kWinoNTH, 2) void wino_mfma_kernel(ConvArgs a) {
   constexpr int NT = 2 / MT;
   constexpr int BM = 32 * MT, TH = 4 * NT;
@@ -481,18 +482,6 @@ int wino_launch(ConvArgs& a, int in_op, hipStream_t st) {
   const int64_t blocks = (int64_t)a.tiles_x * a.tiles_y * a.N * (a.persist ? 1 : a.co_tiles);
   RPST_REQUIRE(blocks <= 0x7fffffffLL, "conv2d: grid too large");
   const unsigned nb = (unsigned)blocks;
-  const char* dbg = getenv("RPST_WINO_DBG");
-  if (dbg && *dbg && in_op == RPST_IN_NONE && a.persist) {
-    switch (atoi(dbg)) {
-#define RPST_WINO_DBGCASE(D) \
-  case D: wino_mfma_kernel<RPST_IN_NONE, MT, true, D><<<nb, kWinoNTH, 0, st>>>(a); break;
-      RPST_WINO_DBGCASE(1) RPST_WINO_DBGCASE(2) RPST_WINO_DBGCASE(4) RPST_WINO_DBGCASE(15)
-      RPST_WINO_DBGCASE(16) RPST_WINO_DBGCASE(32) RPST_WINO_DBGCASE(256)
-#undef RPST_WINO_DBGCASE
-      default: break;
-    }
-    return launch_status("wino_mfma_kernel(debug)");
-  }
 #define RPST_WINO_GO(OP)                                                                  \
   (a.persist ? (void)(wino_mfma_kernel<OP, MT, true><<<nb, kWinoNTH, 0, st>>>(a))          \
              : (void)(wino_mfma_kernel<OP, MT, false><<<nb, kWinoNTH, 0, st>>>(a)))

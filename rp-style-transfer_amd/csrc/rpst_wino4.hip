@@ -24,7 +24,7 @@
 // into a 4-stage LDS ring by LDS-DMA three steps ahead (step g + 3 issued inside step g's
 // MFMA stream; per-lane patch offsets resolved against the padding once per block); one
 // counted vmcnt wait and one barrier per step. One block loops over the co tiles of its
-// spatial tile (split over two same-XCD blocks for Cin >= 128: a.cosplit).
+// spatial tile (split over two blocks for Cin >= 128 and >= 4 co tiles: a.cosplit).
 // The output transform splits like the positions: each wave applies A^T . A to its three
 // rows (a partial 4x4 tile), the two waves of a tile row swap the partials of the channel
 // half the other one finishes through LDS, and each adds, biases, activates and stores 16
@@ -32,9 +32,6 @@
 // the design minimises VALU per MFMA; measured alternatives and their timings:
 // profiles/r01_wino4_variants.log, profiles/r02_wino4_variants.log.
 #include "rpst_conv.h"
-#ifndef RPST_W4_CPOL
-#define RPST_W4_CPOL 0  // output-store cache policy (aux bits of buffer_store), A/B only
-#endif
 #include "rpst_wct.h"
 
 #include <type_traits>
@@ -48,40 +45,18 @@ constexpr int kW4CK = 8;                   // input channels per chunk
 #define RPST_W4DBG 0
 #endif
 // DMA of step g + 3 issued inside step g's MFMA stream (its address SALU then issues
-// beside the matrix pipe): weights after MFMA pair RPST_W4_HW, patch after RPST_W4_HP
-// (-1: before the input transform). 0 / 2 measured best (profiles/r02_wino4_variants.log)
-#ifndef RPST_W4_HW
-#define RPST_W4_HW 0
-#endif
-#ifndef RPST_W4_HP
-#define RPST_W4_HP 2
-#endif
-#ifndef RPST_W4_AHEAD  // MFMA groups whose A operands are read ahead (NR = 4; NR = 2: 3)
-// 2: 64->128 N64 8.17 -> 8.02 ms, 32->64 2.57 -> 2.50, 64->32 1.15 -> 1.11 against 3; NR = 2's
-// 16->32 / 32->16 measured 0.005 ms slower at 2 (tools/ab_bench_libs.sh, profiles/r05/ahead_ab.log)
-#define RPST_W4_AHEAD 2
-#endif
-#ifndef RPST_W4_HW2  // the same issue slots for the NR = 2 form
-#define RPST_W4_HW2 RPST_W4_HW
-#endif
-#ifndef RPST_W4_HP2
-#define RPST_W4_HP2 RPST_W4_HP
-#endif
-#ifndef RPST_W4_ORDER  // spatial block order (w4_tile): 3 = row tile fastest (round 5)
-#define RPST_W4_ORDER 3
-#endif
+// beside the matrix pipe): weights after MFMA pair kW4HW, patch after kW4HP, for both block
+// forms. 0 / 2 measured best, also against issuing before the input transform
+// (profiles/r02_wino4_variants.log)
+constexpr int kW4HW = 0, kW4HP = 2;
+// MFMA groups whose A operands are read ahead, NR = 4 / NR = 2. NR = 4 at 2 against 3: 64->128
+// N64 8.17 -> 8.02 ms, 32->64 2.57 -> 2.50, 64->32 1.15 -> 1.11; NR = 2's 16->32 / 32->16
+// measured 0.005 ms slower at 2 (tools/ab_bench_libs.sh, profiles/r05/ahead_ab.log)
+constexpr int kW4Ahead = 2, kW4Ahead2 = 3;
 constexpr int kW4BM = 32;                  // output channels per co tile
 constexpr int kW4TH = 16, kW4TW = 64;      // output rows x columns per block
 constexpr int kW4PH = kW4TH + 2;           // patch rows
 constexpr int kW4PS = 68;                  // patch row stride (floats): 66 columns + 2 spare
-// window columns 4-7 read as a second ds_read_b128 (round 6) instead of 4-5 as a b64: the b64
-// reads of the four channel groups k of a wave hit the same banks (channel stride 768 floats
-// = 0 mod 64 banks): 13-17 % of LDS cycles bank-conflicted on the small-Cin layers
-// (profiles/r05_sq_layers.csv), 0 % with the b128 (profiles/r06/sq_rd128.log); layer times
-// unchanged within noise (32->64 2.52 / 2.55 ms, 64->128 7.91 / 7.93, profiles/r06/rd128_ab.log)
-#ifndef RPST_W4_RD128
-#define RPST_W4_RD128 1
-#endif
 constexpr int kW4CS = 1280;                // channel stride (floats)
 constexpr int kW4DMA = 20;                 // 4-B LDS-DMA pieces per patch channel (64 floats)
 constexpr int kW4DMA4 = 5;                 // 16-B pieces (256 floats) on interior blocks
@@ -208,8 +183,8 @@ bool wino4_fits(int N, int Cin, int Hs, int Ws, int in_op) {
   return (int64_t)(3 * Cin + 8) * plane < (1LL << 32) - (1LL << 20);
 }
 int wino4_persist() { return 1; }  // one block per spatial tile loops over the co tiles
-// tile rows per block (W4Geo): 2 for the layers with Cin * Cout <= RPST_WINO4_HALF (512: the
-// RP stacks' 16->32 and 32->16), 4 otherwise -- a function of the layer's shape only, so an
+// tile rows per block (W4Geo): 2 for the layers with Cin * Cout <= 512 (the RP stacks' 16->32
+// and 32->16), 4 otherwise -- a function of the layer's shape only, so an
 // image's bits never depend on its batch. tools/ab_env.sh (bench_conv, ms, NR = 4 / NR = 2,
 // two rounds): 16->32 N64 1.018 / 0.974, 32->16 N32 0.665 / 0.627, 32->64 N64 2.506 / 2.585,
 // 64->32 N32 1.115 / 1.105, 64->128 N64 8.03 / 8.34 (profiles/r03/wino4_half_ab.log): the
@@ -220,17 +195,11 @@ int wino4_persist() { return 1; }  // one block per spatial tile loops over the 
 // groups ahead at NR = 4): 64->32 N32 1.10 -> 1.06 ms at NR = 2 (32->64 2.50 either way), so
 // layers with <= 32 output channels switch up to Cin * Cout = 2048 (profiles/r05/half_ab.log).
 int wino4_rows(int Cin, int Cout, int in_op) {
-  static const int lim = [] {  // RPST_WINO4_HALF: the product threshold alone (A/B)
-    const char* e = getenv("RPST_WINO4_HALF");
-    return (e && *e) ? atoi(e) : -1;
-  }();
   if (wino4q_applies(Cin, Cout, in_op)) return 2;  // rpst_wino4q.hip: 8 output rows
   const int64_t cc = (int64_t)Cin * Cout;
-  if (lim >= 0) return cc <= lim ? 2 : 4;
   return cc <= 512 || (Cout <= 32 && cc <= 2048) ? 2 : 4;
 }
 
-// B^T row transform of one 6-vector (in place): the shared terms of rows (1,2) and (3,4)
 // what the F(4x4) epilogue needs besides the tile (wino4_mfma_kernel's epi_ctx)
 struct EpiCtx {
   int W, H, Cout, gy0, gx0, rows, n, sidx, statP;
@@ -244,37 +213,7 @@ struct EpiCtx {
   float2* statp;
 };
 
-// kernel arguments loaded at their use (s_load through an opaque copy of the kernarg
-// pointer, so the loads are not hoisted out of the loop that contains the use)
-typedef const __attribute__((address_space(4))) ConvArgs* KArgs;
-__device__ __forceinline__ KArgs late_args() {
-  KArgs p = (KArgs)__builtin_amdgcn_kernarg_segment_ptr();
-#if __HIP_DEVICE_COMPILE__  // the host pass only emits the launch stub (no "s" registers)
-  asm volatile("" : "+s"(p));
-#endif
-  return p;
-}
-// buffer resource over `bytes` at p, or over zero records (every access reads 0) if !ok
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t rsrc_or_zero(const float* p, unsigned bytes, bool ok) {
-  return __builtin_amdgcn_make_buffer_rsrc((void*)p, (short)0, ok ? (int)bytes : 0, 0x00020000);
-}
-// sum over the 16 lanes of a DPP row, in every lane: four DPP adds (quad xor 1, quad xor 2,
-// half-row mirror, row mirror) instead of four ds_bpermute round trips through the LDS
-__device__ __forceinline__ float row16_sum(float v) {
-  v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0xB1, 0xF, 0xF, false));
-  v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x4E, 0xF, 0xF, false));
-  v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x141, 0xF, 0xF, false));
-  v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x140, 0xF, 0xF, false));
-  return v;
-}
-// a wave-uniform value made opaque at this point (not hoisted out of the enclosing loop)
-__device__ __forceinline__ int launder(int v) {
-#if __HIP_DEVICE_COMPILE__
-  asm volatile("" : "+s"(v));
-#endif
-  return v;
-}
-
+// B^T row transform of one 6-vector (in place): the shared terms of rows (1,2) and (3,4)
 __device__ __forceinline__ void bt6(float& d0, float& d1, float& d2, float& d3, float& d4,
                                     float& d5) {
   const float A = fmaf(-4.f, d2, d4), B = fmaf(-4.f, d1, d3);
@@ -289,69 +228,12 @@ __device__ __forceinline__ void bt6(float& d0, float& d1, float& d2, float& d3, 
   d5 = t5;
 }
 
-// A^T applied to one 6-vector -> 4 values
-__device__ __forceinline__ void at6(const float (&m)[6], float (&p)[4]) {
-  const float s12 = m[1] + m[2], d12 = m[1] - m[2];
-  const float s34 = m[3] + m[4], d34 = m[3] - m[4];
-  p[0] = (m[0] + s12) + s34;
-  p[1] = fmaf(2.f, d34, d12);
-  p[2] = fmaf(4.f, s34, s12);
-  p[3] = fmaf(8.f, d34, d12) + m[5];
-}
-
-// branch-free padding resolution (resolve() in rpst_conv.h, as selects): reflect(1) or
-// zero padding; false for a zero-padding position, v clamped into [0, n) either way
-__device__ __forceinline__ bool resolve_bf(int& v, int n, bool zero_pad) {
-  const bool in = v >= 0 && v < n;
-  const int r = reflect1(v, n);
-  v = zero_pad ? min(max(v, 0), n - 1) : r;
-  return in || !zero_pad;
-}
-
-// Round 5 (tools/ab_bench_libs.sh, profiles/r05/order_ab.log, configs[1], two rounds): row
-// tile fastest with the hardware's round-robin XCD assignment 546.5 / 547.6 img/s against
-// 543.1 / 544.1 for the round-4 order 0 swizzled (16->32 0.94 -> 0.88 ms, 64->128 8.02 ->
-// 7.90); order 0 unswizzled 545.4 / 544.1, order 3 swizzled 543.7 / 543.5.
-#ifndef RPST_W4_SWZ  // 1: consecutive logical blocks on one XCD (xcd_swizzle)
-#define RPST_W4_SWZ 0
-#endif
-__device__ __forceinline__ int w4_block_id() {
-  return RPST_W4_SWZ ? xcd_swizzle(blockIdx.x, (int)gridDim.x) : (int)blockIdx.x;
-}
-
-// spatial tile of logical block b (after the co-split digit): order 0 = column tile fastest,
-// then row tile, then image; 1 = image fastest, then column, row; 2 = column, image, row;
-// 3 = row, column, image
-// (RPST_W4_ORDER at build time: which tiles the resident blocks share). tools/ab_variants.sh,
-// two rounds (ms, order 0 / 1 / 2): 128->256 N64 28.46 / 28.86 / 28.37, 64->128 8.00 /
-// 8.47 / 7.83, 256->128 N32 13.81 / 14.17 / 13.76, 32->64 2.54 / 2.69 / 2.57; in bench.py
-// (with the statistics epilogue) order 2 measured 29.30 ms for 128->256 vs 29.09 for order 0
-// and the same AdaIN-RP rate within noise (521.5 vs 520.2 img/s): order 0 stays.
-__device__ __forceinline__ void w4_tile(int b, int order, int tiles_x, int tiles_y, int N,
-                                        int& tx, int& ty, int& n) {
-  if (order == 1) {
-    n = b % N;
-    b /= N;
-    tx = b % tiles_x;
-    ty = b / tiles_x;
-  } else if (order == 2) {
-    tx = b % tiles_x;
-    b /= tiles_x;
-    n = b % N;
-    ty = b / N;
-  } else if (order == 3) {  // row tile fastest, then column tile, image
-    ty = b % tiles_y;
-    b /= tiles_y;
-    tx = b % tiles_x;
-    n = b / tiles_x;
-  } else {
-    tx = b % tiles_x;
-    b /= tiles_x;
-    ty = b % tiles_y;
-    n = b / tiles_y;
-  }
-}
-
+// Block order (w4_tile), round 5 (tools/ab_bench_libs.sh, profiles/r05/order_ab.log,
+// configs[1], two rounds): row tile fastest with the hardware's round-robin XCD assignment
+// 546.5 / 547.6 img/s against 543.1 / 544.1 for the round-4 order (column tile fastest,
+// consecutive logical blocks on one XCD; 16->32 0.94 -> 0.88 ms, 64->128 8.02 -> 7.90); column
+// tile fastest round-robin 545.4 / 544.1, row tile fastest on one XCD 543.7 / 543.5.
+//
 // STATS: the calc_mean_std partials epilogue (a.stat_part); BTAB: the folded per-(n, co)
 // border-class bias table (a.btab). Both are template arguments so a plain layer's
 // epilogue carries none of their VALU; the two transformed-row halves (ph, waves 0-3 and
@@ -364,8 +246,6 @@ __global__ __launch_bounds__(W4Geo<NR>::NTH, W4Geo<NR>::LAUNCH_WPE) void wino4_m
   // patch DMA, 2 no weight DMA, 8 no input transform, 16 no barriers, 32 no epilogue,
   // 64 no weight LDS reads, 128 no DMA waits
   constexpr int DBG = RPST_W4DBG;
-  // DMA placement of step g + 3: before the transform (-1) or after MFMA pair q of step g
-  constexpr int kHW = NR == 2 ? RPST_W4_HW2 : RPST_W4_HW, kHP = NR == 2 ? RPST_W4_HP2 : RPST_W4_HP;
   static_assert(RawN<INOP>::R == 1, "one raw load per patch element");
   // one __shared__ object per ring stage: the stage a K step reads and the one its DMA
   // fills are then distinct objects, so the compiler's wait insertion does not drain the
@@ -376,19 +256,16 @@ __global__ __launch_bounds__(W4Geo<NR>::NTH, W4Geo<NR>::LAUNCH_WPE) void wino4_m
   __shared__ __attribute__((aligned(16))) float smem3[S > 3 ? Geo::STAGE : 4];
   __shared__ __attribute__((aligned(16))) float dummy[256];  // target of padding DMA pieces
 
-  // block -> (column tile, row tile, image), XCD-swizzled (neighbouring spatial tiles share
-  // halo rows and every block of an XCD streams the same weight slices through its L2);
-  // one block loops over every co tile of its spatial tile
-  int bid = w4_block_id();
-  // a.cosplit blocks per spatial tile (consecutive logical ids: one XCD, dispatched
-  // together, so the patch they all stream is served by that XCD's L2), each looping over
-  // co_tiles / cosplit co tiles
+  // block -> (co-split group, row tile, column tile, image): a.cosplit blocks per spatial
+  // tile (consecutive ids, dispatched together), each looping over co_tiles / cosplit co
+  // tiles
+  int bid = (int)blockIdx.x;
   const int cog = bid % a.cosplit;
   bid /= a.cosplit;
   const int nct = a.co_tiles / a.cosplit;
   const int ct0 = cog * nct;
   int tx, ty, n;
-  w4_tile(bid, RPST_W4_ORDER, a.tiles_x, a.tiles_y, a.N, tx, ty, n);
+  w4_tile(bid, a.tiles_x, a.tiles_y, tx, ty, n);
   const int nch = a.nchunks, K4 = 2 * nch, G = nct * K4;  // K steps per co tile / in total
   const int y0 = ty * Geo::TH, x0 = tx * kW4TW;
 
@@ -396,10 +273,9 @@ __global__ __launch_bounds__(W4Geo<NR>::NTH, W4Geo<NR>::LAUNCH_WPE) void wino4_m
   const int lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int k = lane >> 4, tn = lane & 15;
   const int wr = wave % NR, ph = wave / NR;  // tile row, transformed-row half
-  // optional static priority (a.persist & 2: waves 4-7, & 4: waves 0-3; RPST_WINO4_PRIO=1/2):
-  // with the DMA inside the MFMA stream, equal priorities measured fastest (128->256 28.47
-  // vs 28.75 ms with waves 4-7 at priority 1; profiles/r02_wino4_variants.log)
-  if ((ph && (a.persist & 2)) || (!ph && (a.persist & 4))) __builtin_amdgcn_s_setprio(1);
+  // every wave at the default priority: with the DMA inside the MFMA stream, equal
+  // priorities measured fastest (128->256 28.47 vs 28.75 ms with waves 4-7 at priority 1;
+  // profiles/r02_wino4_variants.log)
 
   const bool pooled = INOP == RPST_IN_UPSAMPLE2;
   const unsigned in_plane = pooled ? (unsigned)(a.Hs * a.Ws) : (unsigned)(a.H * a.W);
@@ -559,16 +435,18 @@ __global__ __launch_bounds__(W4Geo<NR>::NTH, W4Geo<NR>::LAUNCH_WPE) void wino4_m
   };
 
 
-  // one K step of 4 channels from a stage: 72 VALU of input transform + 36 MFMAs
-  // hw / hp: called after MFMA pair kHW / kHP (RPST_W4VAR placement experiments)
   // input rows ph .. ph + 4 of this lane's 6x6 window of one step
   auto load_rows = [&](const float* pbuf, float (&d)[5][6]) {
     const float* pr = pbuf + k * Geo::CS + (4 * wr + ph) * kW4PS + 4 * tn;
 #pragma unroll
     for (int r = 0; r < 5; ++r) {
-#if RPST_W4_RD128
-      // columns 4 tn + 4 .. + 7 as a second ds_read_b128 (the empty asm keeps it whole: the
-      // compiler narrows it to the b64 of the 2 columns used, whose k-groups share banks)
+      // columns 4 tn + 4 .. + 7 as a second ds_read_b128 (round 6; the empty asm keeps it
+      // whole: the compiler narrows it to the b64 of the 2 columns used). The b64 reads of the
+      // four channel groups k of a wave hit the same banks (channel stride = 0 mod 64 banks):
+      // 13-17 % of LDS cycles bank-conflicted on the small-Cin layers
+      // (profiles/r05_sq_layers.csv), 0 % with the b128 (profiles/r06/sq_rd128.log); layer
+      // times unchanged within noise (32->64 2.52 / 2.55 ms, 64->128 7.91 / 7.93,
+      // profiles/r06/rd128_ab.log)
       floatx4 u = *reinterpret_cast<const floatx4*>(pr + r * kW4PS);
       floatx4 v = *reinterpret_cast<const floatx4*>(pr + r * kW4PS + 4);
       asm("" : "+v"(u), "+v"(v));
@@ -578,25 +456,15 @@ __global__ __launch_bounds__(W4Geo<NR>::NTH, W4Geo<NR>::LAUNCH_WPE) void wino4_m
       d[r][3] = u[3];
       d[r][4] = v[0];
       d[r][5] = v[1];
-#else
-      const float4 u = *reinterpret_cast<const float4*>(pr + r * kW4PS);
-      const float2 v = *reinterpret_cast<const float2*>(pr + r * kW4PS + 4);
-      d[r][0] = u.x;
-      d[r][1] = u.y;
-      d[r][2] = u.z;
-      d[r][3] = u.w;
-      d[r][4] = v.x;
-      d[r][5] = v.y;
-#endif
     }
   };
   // one K step of 4 channels from a stage (its rows already in d): 72 VALU of input
-  // transform + 36 MFMAs; hw / hp run after MFMA pair kHW / kHP (the DMA of step g + 3)
+  // transform + 36 MFMAs; hw / hp run after MFMA pair kW4HW / kW4HP (the DMA of step g + 3)
   auto compute = [&](const float* pbuf, float (&d)[5][6], auto&& hw, auto&& hp) {
     {
       const float* wq = pbuf + Geo::SPATCH + ph * 9 * 256 + lane * 4;
       float4 w4[9];
-      constexpr int kA = NR == 4 ? RPST_W4_AHEAD : 3;  // A-operand groups read ahead
+      constexpr int kA = NR == 4 ? kW4Ahead : kW4Ahead2;  // A-operand groups read ahead
 #pragma unroll
       for (int q = 0; q < kA; ++q)
         w4[q] = (DBG & 64) ? make_float4(1.f, 2.f, 3.f, (float)q)
@@ -639,8 +507,8 @@ __global__ __launch_bounds__(W4Geo<NR>::NTH, W4Geo<NR>::LAUNCH_WPE) void wino4_m
         acc[p0][1] = __builtin_amdgcn_mfma_f32_16x16x4f32(w4[q].y, v0, acc[p0][1], 0, 0, 0);
         acc[p1][0] = __builtin_amdgcn_mfma_f32_16x16x4f32(w4[q].z, v1, acc[p1][0], 0, 0, 0);
         acc[p1][1] = __builtin_amdgcn_mfma_f32_16x16x4f32(w4[q].w, v1, acc[p1][1], 0, 0, 0);
-        if (q == kHW) hw();
-        if (q == kHP) hp();
+        if (q == kW4HW) hw();
+        if (q == kW4HP) hp();
       }
     }
   };
@@ -693,8 +561,7 @@ __global__ __launch_bounds__(W4Geo<NR>::NTH, W4Geo<NR>::LAUNCH_WPE) void wino4_m
     e.Cout = L->Cout;
     e.slope = L->relu == RPST_ACT_RELU ? 0.f : (L->relu == RPST_ACT_LRELU ? 0.2f : 1.f);
     int btx, bty;
-    w4_tile(w4_block_id() / L->cosplit, RPST_W4_ORDER,
-            L->tiles_x, L->tiles_y, L->N, btx, bty, e.n);
+    w4_tile((int)blockIdx.x / L->cosplit, L->tiles_x, L->tiles_y, btx, bty, e.n);
     const int bx0 = btx * kW4TW;
     e.gy0 = bty * Geo::TH + 4 * wr;
     e.gx0 = bx0 + 4 * tn;
@@ -783,7 +650,7 @@ __global__ __launch_bounds__(W4Geo<NR>::NTH, W4Geo<NR>::LAUNCH_WPE) void wino4_m
       for (int yy = 0; yy < 4; ++yy) {
         const floatx4 v = {Y[yy * 4], Y[yy * 4 + 1], Y[yy * 4 + 2], Y[yy * 4 + 3]};
         __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v), ro,
-                                               (int)(e.voff[yy] + cofs), 0, RPST_W4_CPOL);
+                                               (int)(e.voff[yy] + cofs), 0, 0);
       }
     } else if (e.pool) {
       // max_pool2d(2, 2, ceil_mode) of the finished tile: tiles start on even rows and
@@ -951,10 +818,8 @@ __global__ __launch_bounds__(W4Geo<NR>::NTH, W4Geo<NR>::LAUNCH_WPE) void wino4_m
     float d[5][6];
     load_rows(cur, d);
     const bool live3 = g + S - 1 < G;
-    if constexpr (kHW < 0) issue_w(g + S - 1, live3, nx3);
-    if constexpr (kHP < 0) issue_p(ks3, live3, nx3);
-    auto hw = [&]() { if constexpr (kHW >= 0) issue_w(g + S - 1, live3, nx3); };
-    auto hp = [&]() { if constexpr (kHP >= 0) issue_p(ks3, live3, nx3); };
+    auto hw = [&]() { issue_w(g + S - 1, live3, nx3); };
+    auto hp = [&]() { issue_p(ks3, live3, nx3); };
     compute(cur, d, hw, hp);
     ks3 = ks3 + 1 == K4 ? 0 : ks3 + 1;
     if (ks == K4 - 1) {
@@ -1197,23 +1062,14 @@ int wino4_launch(ConvArgs& a, int in_op, hipStream_t st) {
   a.tiles_y = (a.H + 4 * nr - 1) / (4 * nr);
   a.co_tiles = a.Cout_pad / kW4BM;
   a.stat_P = a.tiles_x * a.tiles_y * nr;
-  {
-    const char* e = getenv("RPST_WINO4_PRIO");  // A/B switch for a static priority
-    const int pr = (e && *e) ? atoi(e) : 0;
-    a.persist = 1 | (pr == 1 ? 2 : 0) | (pr == 2 ? 4 : 0);
-  }
+  a.persist = 1;
   RPST_REQUIRE((int64_t)a.co_tiles * a.nchunks * kW4WCH * 4 < (1LL << 31),
                "conv2d: winograd4 weight image exceeds 2 GiB");
-  {
-    // blocks per spatial tile: 2 once a co tile has >= 32 K steps (Cin >= 128) and there
-    // are >= 4 co tiles (the shorter blocks' prologue then costs less than the L2 reuse of
-    // the shared patch gains); RPST_WINO4_COSPLIT overrides (A/B)
-    const char* e = getenv("RPST_WINO4_COSPLIT");
-    int c = (e && *e) ? atoi(e) : (2 * a.nchunks >= 32 && a.co_tiles >= 4 ? 2 : 1);
-    c = c < 1 ? 1 : (c > a.co_tiles ? a.co_tiles : c);
-    while (a.co_tiles % c) --c;
-    a.cosplit = c;
-  }
+  // blocks per spatial tile: 2 once a co tile has >= 32 K steps (Cin >= 128) and there
+  // are >= 4 co tiles (the shorter blocks' prologue then costs less than the L2 reuse of
+  // the shared patch gains; 1 / 2 / 4 re-measured in profiles/r05/order_ab.log)
+  a.cosplit = 2 * a.nchunks >= 32 && a.co_tiles >= 4 ? 2 : 1;
+  while (a.co_tiles % a.cosplit) --a.cosplit;
   const int64_t blocks = (int64_t)a.tiles_x * a.tiles_y * a.N * a.cosplit;
   RPST_REQUIRE(blocks <= 0x7fffffffLL, "conv2d: grid too large");
   const unsigned nb = (unsigned)blocks;

@@ -17,78 +17,29 @@
 //
 // Block = 8 waves (two per SIMD), output 8 rows x 64 columns x 64 channels: wave w owns tile
 // row w >> 2 and quarter w & 3. Per K step (4 input channels) the weight slice (64 co x 36
-// positions x 4 ci = 36 KiB) and the patch (4 channels x 10 rows x 68) stream into a 3-stage
-// LDS ring by LDS-DMA: W(x + 2) and P(x + 3) are issued inside step x. The four quarters of
-// a tile row meet in the epilogue: each wave sends its 9 positions of the other three
-// quarters' 16-channel blocks through a weight stage (6 passes of 2 accumulator elements x 3
-// positions) and finishes its own block with the full output transform.
+// positions x 4 ci = 36 KiB) and the patch (4 channels x 10 rows x 72) stream into an LDS ring
+// (2 weight stages, 4 patch stages) by LDS-DMA: W(x + 1) and P(x + 4) are issued inside step
+// x. The four quarters of a tile row meet in the epilogue: each wave sends its 9 positions of
+// the other three quarters' 16-channel blocks through a weight stage (6 passes of 2
+// accumulator elements x 3 positions) and finishes its own block with the full output
+// transform.
 #include "rpst_conv.h"
-#ifndef RPST_W4_CPOL
-#define RPST_W4_CPOL 0  // output-store cache policy (aux bits of buffer_store), A/B only
-#endif
 
 #include <type_traits>
+
+// timing-only experiments (results wrong; tools/build_variants.sh -DRPST_W4Q_DBG=n): 1 no patch
+// DMA, 2 no weight DMA, 4 no epilogue exchange, 8 no input transform, 16 no step barriers,
+// 32 no epilogue at all, 64 no output stores (issued never), 128 no DMA waits. Round 6 on the
+// final kernel, 128->256 @512^2 N64 (profiles/r06/epilogue_ab.log): 26.8 ms; no epilogue 25.3;
+// no output stores 24.8; no exchange 25.7; no output transform (a bit since removed) 26.1
+#ifndef RPST_W4Q_DBG
+#define RPST_W4Q_DBG 0
+#endif
 
 namespace rpst {
 namespace {
 
-typedef __attribute__((address_space(3))) void* q_lds_t;
-typedef const __attribute__((address_space(4))) ConvArgs* QArgs;
-
-// kernel arguments loaded at their use (s_load through an opaque copy of the kernarg
-// pointer, so the loads are not hoisted into the main loop's scalar registers)
-__device__ __forceinline__ QArgs q_args() {
-  QArgs p = (QArgs)__builtin_amdgcn_kernarg_segment_ptr();
-#if __HIP_DEVICE_COMPILE__
-  asm volatile("" : "+s"(p));
-#endif
-  return p;
-}
-// buffer resource over `bytes` at p, or over zero records (every access reads 0) if !ok;
-// the select is a mask, so no branch splits the MFMA stream around it
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t q_rsrc(const float* p, unsigned bytes, bool ok) {
-  return __builtin_amdgcn_make_buffer_rsrc((void*)p, (short)0, (int)(bytes & (0u - (unsigned)ok)),
-                                           0x00020000);
-}
 __device__ __forceinline__ int q_mask(int v, bool ok) { return v & -(int)ok; }
-// sum over the 16 lanes of a DPP row, in every lane
-__device__ __forceinline__ float q_row16_sum(float v) {
-  v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0xB1, 0xF, 0xF, false));
-  v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x4E, 0xF, 0xF, false));
-  v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x141, 0xF, 0xF, false));
-  v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x140, 0xF, 0xF, false));
-  return v;
-}
-// a wave-uniform value made opaque here (not hoisted out of the enclosing loop)
-__device__ __forceinline__ int q_launder(int v) {
-#if __HIP_DEVICE_COMPILE__
-  asm volatile("" : "+s"(v));
-#endif
-  return v;
-}
-// reflect(1) or zero padding, branch-free; false for a zero-padding position
-__device__ __forceinline__ bool q_resolve(int& v, int n, bool zero_pad) {
-  const bool in = v >= 0 && v < n;
-  const int r = reflect1(v, n);
-  v = zero_pad ? min(max(v, 0), n - 1) : r;
-  return in || !zero_pad;
-}
-// A^T applied to one 6-vector -> 4 values
-#ifndef RPST_W4Q_DBG
-#define RPST_W4Q_DBG 0
-#endif
-__device__ __forceinline__ void q_at6(const float (&m)[6], float (&p)[4]) {
-  if (RPST_W4Q_DBG & 256) {  // timing only: no output transform
-    p[0] = m[0]; p[1] = m[1]; p[2] = m[2]; p[3] = m[3] + m[4] + m[5];
-    return;
-  }
-  const float s12 = m[1] + m[2], d12 = m[1] - m[2];
-  const float s34 = m[3] + m[4], d34 = m[3] - m[4];
-  p[0] = (m[0] + s12) + s34;
-  p[1] = fmaf(2.f, d34, d12);
-  p[2] = fmaf(4.f, s34, s12);
-  p[3] = fmaf(8.f, d34, d12) + m[5];
-}
 // acc += a * b on v_mfma_f32_16x16x4_f32 with the accumulator tied in place ("+v"). The
 // builtin's untied form lets the register allocator rename every accumulator tuple each K
 // step (dst != srcC): with 144 accumulator registers that costs 60-100 more and spills.
@@ -149,19 +100,10 @@ __device__ __forceinline__ void q_bt3(float d0, float d1, float d2, float d3, fl
 
 constexpr int kQCo = 64;                     // output channels per co tile
 constexpr int kQTH = 8, kQTW = 64;           // output rows x columns per block
-#ifndef RPST_W4Q_AL
-// 1: patch rows staged from x0 - 4 (16-B aligned sources for the interior blocks' 16-B
-// pieces), column x0 - 1 at LDS column 3; 0: from x0 - 1 (4-B aligned sources)
-#define RPST_W4Q_AL 1
-#endif
-#ifndef RPST_W4Q_EDGE
-#define RPST_W4Q_EDGE 1
-#endif
-#ifndef RPST_W4Q_ALRD  // the odd window column: 1 = ds_read_b32, 2 = a whole ds_read_b128
-#define RPST_W4Q_ALRD 1
-#endif
-constexpr int kQXO = RPST_W4Q_AL ? 4 : 1;    // patch columns staged left of the tile
-constexpr int kQPS = RPST_W4Q_AL ? 72 : 68;  // patch row stride (floats): 66 used columns
+// patch rows are staged from x0 - 4 (16-B aligned sources for the interior blocks' 16-B
+// pieces), so column x0 - 1 sits at LDS column kQXO - 1 = 3
+constexpr int kQXO = 4;                      // patch columns staged left of the tile
+constexpr int kQPS = 72;                     // patch row stride (floats): columns 3 .. 68 used
 constexpr int kQCS = 768;                    // patch channel stride (floats)
 constexpr int kQWS = 9216;                   // weight floats per (co tile, K step)
 constexpr int kQPAT = 4 * kQCS;              // patch stage: 4 channels (12 KiB)
@@ -169,26 +111,15 @@ constexpr int kQNTH = 512;
 constexpr int kQMaxCo = 512;                 // output channels the LDS bias table holds
 constexpr int kQWPI = 5;                     // 1-KiB weight pieces per wave and step (36 / 8)
 constexpr int kQWide = 2, kQSlow = 6;        // patch pieces per wave and step: 16-B / 4-B
-constexpr int kQDMA4 = 3, kQDMA = RPST_W4Q_AL ? 12 : 11;  // patch pieces per channel: 16-B / 4-B
+constexpr int kQDMA4 = 3, kQDMA = 12;        // patch pieces per channel: 16-B / 4-B
 constexpr int kQRP = kQPS / 4;               // 16-B pieces per patch row
 constexpr int kQXS = 4 * 3 * 3 * 64 * 2;     // epilogue exchange floats per tile row and pass
-// timing-only experiments (results wrong; tools/build_variants.sh -DRPST_W4Q_DBG=n): 1 no patch
-// DMA, 2 no weight DMA, 4 no epilogue exchange, 8 no input transform, 16 no step barriers,
-// 32 no epilogue at all, 64 no output stores (issued never), 128 no DMA waits, 256 no output
-// transform. Round 6 on the final kernel, 128->256 @512^2 N64 (profiles/r06/epilogue_ab.log):
-// 26.8 ms; no epilogue 25.3; no output stores 24.8; no exchange 25.7; no transform 26.1
-#ifndef RPST_W4Q_WG0
-#define RPST_W4Q_WG0 0  // MFMA group of a step whose issue slot takes the first W(x + 1) piece
-#endif
-#ifndef RPST_W4Q_PG
-#define RPST_W4Q_PG 5   // MFMA group after which the P(x + 4) pieces are issued
-#endif
-#ifndef RPST_W4Q_AHEAD
+constexpr int kQWG0 = 0;  // MFMA group of a step whose issue slot takes the first W(x + 1) piece
+constexpr int kQPG = 5;   // MFMA group after which the P(x + 4) pieces are issued
 // MFMA groups whose A operands are read ahead: configs[1] 539.7 / 541.7 img/s at 2, 545.2 /
 // 546.6 at 3 (128->256 N64 28.05 -> 27.65 ms), 537 at 4, 522 at 5 (tools/ab_bench_libs.sh,
-// profiles/r05/ahead_ab.log)
-#define RPST_W4Q_AHEAD 3
-#endif
+// profiles/r05/ahead_ab.log; re-swept with kQPG and kQWG0 in profiles/r06/placement_resweep.log)
+constexpr int kQAhead = 3;
 static_assert(10 * kQRP <= kQDMA4 * 64 && kQDMA4 * 256 <= kQCS, "16-B pieces in a channel");
 static_assert(10 * kQPS <= kQDMA * 64 && kQDMA * 64 <= kQCS, "4-B pieces in a channel");
 static_assert(2 * kQWide >= kQDMA4 && 2 * kQSlow >= kQDMA && 8 * kQWPI >= 36, "coverage");
@@ -323,56 +254,20 @@ struct QEpi {
   int statP;
 };
 
-// Block order (tools/ab_bench_libs.sh, profiles/r05/order_ab.log; configs[1], two rounds):
-// row tile fastest with the hardware's round-robin XCD assignment (consecutive blocks on
-// consecutive XCDs) 553.3 / 553.1 img/s; column tile fastest with consecutive logical blocks
-// on one XCD (xcd_swizzle, the round-4 choice) 548.3 / 547.3; row tile fastest swizzled
-// 534.7; column tile fastest unswizzled 536.2; image-fastest orders 503-538.
-#ifndef RPST_W4Q_ORDER  // 0 column tile fastest, 1 row tile fastest, 2 / 3 image-fastest forms
-#define RPST_W4Q_ORDER 1
-#endif
-#ifndef RPST_W4Q_SWZ  // 1: consecutive logical blocks on one XCD (xcd_swizzle)
-#define RPST_W4Q_SWZ 0
-#endif
-__device__ __forceinline__ int q_block_id() {
-  return RPST_W4Q_SWZ ? xcd_swizzle(blockIdx.x, (int)gridDim.x) : (int)blockIdx.x;
-}
-__device__ __forceinline__ void q_tile(int b, int tiles_x, int tiles_y, int cosplit, int& tx,
-                                       int& ty, int& n) {
-  if (RPST_W4Q_ORDER == 1) {
-    ty = b % tiles_y;
-    b /= tiles_y;
-    tx = b % tiles_x;
-    n = b / tiles_x;
-  } else if (RPST_W4Q_ORDER == 2) {  // image fastest, then row tile, column tile
-    const int nimg = (int)(gridDim.x / ((unsigned)tiles_x * tiles_y * cosplit));
-    n = b % nimg;
-    b /= nimg;
-    ty = b % tiles_y;
-    tx = b / tiles_y;
-  } else if (RPST_W4Q_ORDER == 3) {  // row tile, image, column tile
-    const int nimg = (int)(gridDim.x / ((unsigned)tiles_x * tiles_y * cosplit));
-    ty = b % tiles_y;
-    b /= tiles_y;
-    n = b % nimg;
-    tx = b / nimg;
-  } else {
-    tx = b % tiles_x;
-    b /= tiles_x;
-    ty = b % tiles_y;
-    n = b / tiles_y;
-  }
-}
-
+// Block order (w4_tile; tools/ab_bench_libs.sh, profiles/r05/order_ab.log; configs[1], two
+// rounds): row tile fastest with the hardware's round-robin XCD assignment (consecutive blocks
+// on consecutive XCDs) 553.3 / 553.1 img/s; column tile fastest with consecutive logical blocks
+// on one XCD (the round-4 choice) 548.3 / 547.3; row tile fastest on one XCD 534.7; column
+// tile fastest round-robin 536.2; image-fastest orders 503-538.
 __device__ __forceinline__ QEpi q_epi_ctx(int wr, int tn) {
-  const QArgs L = q_args();
+  const KArgs L = late_args();
   QEpi e;
   e.W = L->W;
   e.H = L->H;
   e.Cout = L->Cout;
   e.slope = L->relu == RPST_ACT_RELU ? 0.f : (L->relu == RPST_ACT_LRELU ? 0.2f : 1.f);
   int btx, bty;
-  q_tile(q_block_id() / L->cosplit, L->tiles_x, L->tiles_y, L->cosplit, btx, bty, e.n);
+  w4_tile((int)blockIdx.x / L->cosplit, L->tiles_x, L->tiles_y, btx, bty, e.n);
   const int bx0 = btx * kQTW;
   e.gy0 = bty * kQTH + 4 * wr;
   e.gx0 = bx0 + 4 * tn;
@@ -450,13 +345,13 @@ __device__ __forceinline__ void q_finish(const QEpi& e, int co, float (&Y)[16], 
   }
   if ((RPST_W4Q_DBG & 64) && e.statP > -7) {  // timing only: the stores never taken
   } else if (e.bst) {
-    const auto ro = q_rsrc(e.oimg, e.obytes, true);
+    const auto ro = rsrc_or_zero(e.oimg, e.obytes, true);
     const unsigned cofs = cok ? (unsigned)co * (unsigned)(e.H * e.W) * 4u : 0x7fffffffu;
 #pragma unroll
     for (int yy = 0; yy < 4; ++yy) {
       const floatx4 v = {Y[yy * 4], Y[yy * 4 + 1], Y[yy * 4 + 2], Y[yy * 4 + 3]};
       __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v), ro,
-                                             (int)(e.voff[yy] + cofs), 0, RPST_W4_CPOL);
+                                             (int)(e.voff[yy] + cofs), 0, 0);
     }
   } else if (e.pool) {
     // max_pool2d(2, 2, ceil_mode) of the finished tile, fmaxf in maxpool2_kernel's order
@@ -502,15 +397,11 @@ __device__ __forceinline__ void q_finish(const QEpi& e, int co, float (&Y)[16], 
       }
     }
   }
-#ifndef RPST_W4Q_SDBG
-#define RPST_W4Q_SDBG 0
-#endif
   if constexpr (STATS) {
-    if (!(RPST_W4Q_SDBG & 4)) sum = q_row16_sum(sum);
+    sum = row16_sum(sum);
     const float mean = sum * e.inv;
     float m2 = 0.f;
-    if (RPST_W4Q_SDBG & 2) {
-    } else if (e.full) {
+    if (e.full) {
 #pragma unroll
       for (int i = 0; i < 16; ++i) m2 = fmaf(Y[i] - mean, Y[i] - mean, m2);
     } else {
@@ -522,14 +413,12 @@ __device__ __forceinline__ void q_finish(const QEpi& e, int co, float (&Y)[16], 
           m2 += (yy < rows && gx0 + xx < e.W) ? dv * dv : 0.f;
         }
     }
-    if (RPST_W4Q_SDBG & 2) m2 = mean;
-    if (!(RPST_W4Q_SDBG & 4)) m2 = q_row16_sum(m2);
+    m2 = row16_sum(m2);
     // partials in [n][partial][co] order (stat_merge_t_kernel): a wave's 16 channels of one
     // partial fill whole cache lines (in [n][co][partial] order they were 8-B pieces
     // scattered over 16 planes). Statistics cost, 128->256 N64 (tools/ab_stats.py): 1.5 ms
-    // of 28.4, of which the store 0.2 (SDBG 8: the store kept but never taken at run time),
-    // the centred-square pass 0.33 (SDBG 2); SDBG 1 drops the whole computation (dead code)
-    if (!(RPST_W4Q_SDBG & 1) && tn == 0 && cok && (!(RPST_W4Q_SDBG & 8) || e.statP < 0))
+    // of 28.4, of which the store 0.2 and the centred-square pass 0.33
+    if (tn == 0 && cok)
       e.statp[((int64_t)n * e.statP + e.sidx) * e.Cout + co] = make_float2(mean, m2);
   }
 }
@@ -561,13 +450,13 @@ __global__ __launch_bounds__(kQNTH, 1) void wino4q_mfma_kernel(ConvArgs a) {
   const int lane = threadIdx.x & 63;
   const int k = lane >> 4, tn = lane & 15, wr = wave >> 2;
 
-  // block -> (co-split group, column tile, row tile, image); XCD-swizzled
-  int bid = q_block_id();
+  // block -> (co-split group, row tile, column tile, image)
+  int bid = (int)blockIdx.x;
   const int cog = bid % a.cosplit;
   bid /= a.cosplit;
   const int nct = a.co_tiles / a.cosplit, ct0 = cog * nct;
   int tx, ty, n;
-  q_tile(bid, a.tiles_x, a.tiles_y, a.cosplit, tx, ty, n);
+  w4_tile(bid, a.tiles_x, a.tiles_y, tx, ty, n);
   const int K4 = a.nchunks, G = nct * K4;
   const int y0 = ty * kQTH, x0 = tx * kQTW;
 
@@ -583,24 +472,25 @@ __global__ __launch_bounds__(kQNTH, 1) void wino4q_mfma_kernel(ConvArgs a) {
   const unsigned wbytes = (unsigned)(nct * K4 * kQWS) * 4u;  // this block's co tiles
   const float* w_img = a.wpk + (int64_t)n * a.wstride + (int64_t)ct0 * K4 * kQWS;
 
-  // patch of one K step: 4 channels x [10 rows][68] (66 columns + 2 spare) at channel stride
-  // 768; waves 2c, 2c + 1 fill channel c. Interior blocks (every patch column inside the
-  // image, no upsampling): 16-B pieces (a 72-float row from x0 - 4 = 18 pieces, 16-B aligned
-  // sources, 180 per channel, 3 wave-instructions: half 0 takes 0-1, half 1 takes 2 + a
-  // padding piece; columns x0 - 4 .. x0 - 2 and past x0 + 64 are staged but never read);
-  // elsewhere 4-B pieces (element 64 p + lane resolved against the padding, 12 per channel,
-  // 6 per half). RPST_W4Q_AL 0 stages from x0 - 1 (68-float rows, 4-B aligned sources):
-  // 128->256 N64 26.69-26.94 -> 26.55-26.61 ms, folded 256->128 13.01-13.12 -> 12.75-12.96
+  // patch of one K step: 4 channels x [10 rows][72] at channel stride 768, a row staged from
+  // x0 - kQXO = x0 - 4, so the 66 window columns x0 - 1 .. x0 + 64 sit at LDS columns 3 .. 68
+  // (0-2 and 69-71 are staged but never read); waves 2c, 2c + 1 fill channel c. Interior
+  // blocks (every patch column inside the image, no upsampling): 16-B pieces (a 72-float row
+  // = 18 pieces, 16-B aligned sources, 180 per channel, 3 wave-instructions: half 0 takes
+  // 0-1, half 1 takes 2 + a padding piece); elsewhere 4-B pieces (element 64 p + lane
+  // resolved against the padding, 12 per channel, 6 per half). Against 68-float rows staged
+  // from x0 - 1 (4-B aligned sources) the aligned rows took 128->256 N64 from 26.69-26.94 to
+  // 26.55-26.61 ms, folded 256->128 from 13.01-13.12 to 12.75-12.96
   // (profiles/r06/aligned_patch_ab.log).
   // Per-lane source offsets are resolved once per block.
   const int hf = wave & 1;
   const bool zp = a.pad == RPST_PAD_ZERO;
   const int rs = up ? a.Ws : a.W;
-  // RPST_W4Q_EDGE (with the aligned rows): in a row of W % 4 == 0 floats a 16-B piece is
-  // wholly inside or outside the image, so the full-width x-edge tiles take the 16-B pieces
-  // too: outside pieces read zero (zero padding), and reflect padding's one halo column is
-  // copied in after the stage lands (fix_halo)
-  const bool w4a = RPST_W4Q_AL && RPST_W4Q_EDGE && (a.W & 3) == 0;
+  // in a row of W % 4 == 0 floats a 16-B piece of the aligned rows is wholly inside or outside
+  // the image, so the full-width x-edge tiles take the 16-B pieces too: outside pieces read
+  // zero (zero padding), and reflect padding's one halo column is copied in after the stage
+  // lands (fix_halo; profiles/r06/edge_tiles_ab.log)
+  const bool w4a = (a.W & 3) == 0;
   const bool wide = !up && ((x0 >= 1 && x0 + kQTW < a.W) || (w4a && x0 + kQTW <= a.W));
   const bool fixL = wide && w4a && !zp && x0 == 0;
   const bool fixR = wide && w4a && !zp && x0 + kQTW == a.W;
@@ -614,7 +504,7 @@ __global__ __launch_bounds__(kQNTH, 1) void wino4q_mfma_kernel(ConvArgs a) {
       int y = y0 - 1 + row;
       const int xs = x0 - kQXO + 4 * j;
       const bool okx = !w4a || (xs >= 0 && xs + 3 < a.W);
-      const bool ok = p < kQDMA4 && f < 10 * kQRP && q_resolve(y, a.H, zp) && okx;
+      const bool ok = p < kQDMA4 && f < 10 * kQRP && resolve_bf(y, a.H, zp) && okx;
       poff[i] = ok ? ((unsigned)(y * rs) + (unsigned)xs) * 4u : oob;
     }
 #pragma unroll
@@ -626,7 +516,7 @@ __global__ __launch_bounds__(kQNTH, 1) void wino4q_mfma_kernel(ConvArgs a) {
       const int f = 64 * p + lane;
       const int row = min(f / kQPS, 9), col = f - (f / kQPS) * kQPS;
       int y = y0 - 1 + row, x = x0 - kQXO + col;
-      const bool oky = q_resolve(y, a.H, zp), okx = q_resolve(x, a.W, zp);
+      const bool oky = resolve_bf(y, a.H, zp), okx = resolve_bf(x, a.W, zp);
       const bool ok = p < kQDMA && col >= kQXO - 1 && col < kQXO + 1 + kQTW &&
                       f < 10 * kQPS && oky && okx;
       poff[i] = ok ? ((unsigned)((up ? y >> 1 : y) * rs) + (unsigned)(up ? x >> 1 : x)) * 4u : oob;
@@ -641,15 +531,15 @@ __global__ __launch_bounds__(kQNTH, 1) void wino4q_mfma_kernel(ConvArgs a) {
   constexpr int DBG = RPST_W4Q_DBG;
   auto issue_w = [&](int g, float* stg, int i) {
     if (DBG & 2) return;
-    const int wv = q_launder(wave);
+    const int wv = launder(wave);
     const int pc = wv + 8 * i;
     const bool live = g < G;
     const int so = q_mask((g * kQWS + pc * 256) * 4, live);
     if (i < 4) {
-      q_dma16(q_rsrc(w_img, wbytes, live), stg + pc * 256, lane * 16, so);
+      q_dma16(rsrc_or_zero(w_img, wbytes, live), stg + pc * 256, lane * 16, so);
     } else {
       const bool real = pc < 36;
-      q_dma16(q_rsrc(w_img, wbytes, live && real), real ? stg + pc * 256 : dummy, lane * 16,
+      q_dma16(rsrc_or_zero(w_img, wbytes, live && real), real ? stg + pc * 256 : dummy, lane * 16,
               q_mask(so, real));
     }
   };
@@ -657,10 +547,10 @@ __global__ __launch_bounds__(kQNTH, 1) void wino4q_mfma_kernel(ConvArgs a) {
   auto issue_p = [&](auto WIDEc, int g, int ks, float* stg) {
     constexpr bool WIDE = decltype(WIDEc)::value;
     if (DBG & 1) return;
-    const int wv = q_launder(wave);
+    const int wv = launder(wave);
     const int c = 4 * ks + (wv >> 1);
     const bool ok = g < G && c < a.Cin;
-    const auto r = q_rsrc(in_img, oob, ok);
+    const auto r = rsrc_or_zero(in_img, oob, ok);
     const int so = q_mask((int)((unsigned)c * in_plane * 4u), ok);
     float* xs = stg + (wv >> 1) * kQCS;
     const bool h1 = (wv & 1) != 0;
@@ -671,8 +561,7 @@ __global__ __launch_bounds__(kQNTH, 1) void wino4q_mfma_kernel(ConvArgs a) {
 #pragma unroll
       for (int i = 0; i < kQSlow - 1; ++i)
         q_dma4(r, xs + 64 * (h1 ? kQSlow + i : i), poffs[i][tid], so);
-      q_dma4(r, h1 && !RPST_W4Q_AL ? dummy : xs + 64 * (h1 ? 2 * kQSlow - 1 : kQSlow - 1),
-             poffs[kQSlow - 1][tid], so);
+      q_dma4(r, xs + 64 * (h1 ? 2 * kQSlow - 1 : kQSlow - 1), poffs[kQSlow - 1][tid], so);
     }
   };
   // before step x's barrier: W(x) (issued in step x - 1 ahead of its patch group) and
@@ -739,36 +628,19 @@ __global__ __launch_bounds__(kQNTH, 1) void wino4q_mfma_kernel(ConvArgs a) {
     for (int p = 0; p < 9; ++p)
 #pragma unroll
       for (int cb = 0; cb < 4; ++cb) acc[p][cb] = floatx4{0.f, 0.f, 0.f, 0.f};
-    // lane (k, tn) reads rows 4 wr + QR .. + 4 of channel k of a patch, columns 4 tn .. + 7
-    // (two conflict-free ds_read_b128; the empty asm keeps them whole, the compiler would
-    // otherwise narrow them to the 5 floats a quarter uses, as bank-conflicted b32 reads)
+    // lane (k, tn) reads rows 4 wr + QR .. + 4 of channel k of a patch. Window columns
+    // 4 tn .. + 5 sit at LDS columns 4 tn + 3 .. + 8: the quarter's five (QC = 0: 0-4, QC = 1:
+    // 1-5) as one aligned ds_read_b128 (the empty asm keeps it whole) and a ds_read_b32 for the
+    // odd one (all 64 lanes in one pass; the four channel groups k share its banks, but a
+    // second whole b128 brought 13-17 VGPR spills back: profiles/r06/odd_column_read_ab.log)
     const int roff = k * kQCS + (4 * wr + QR) * kQPS + 4 * tn;
     auto read_row = [&](const float* stg, int rr, float (&d)[8]) {
-      if (RPST_W4Q_AL) {
-        // window columns 4 tn .. + 5 sit at LDS columns 4 tn + 3 .. + 8: the quarter's five
-        // (QC = 0: 0-4, QC = 1: 1-5) as two aligned ds_read_b128 (a ds_read_b32 for the odd
-        // one: all 64 lanes in one pass, and the four channel groups k share its banks)
-        const float* rp = stg + roff + rr * kQPS;
-        if (RPST_W4Q_ALRD == 2) {
-          floatx4 e = *reinterpret_cast<const floatx4*>(rp + (QC ? 8 : 0));
-          floatx4 u = *reinterpret_cast<const floatx4*>(rp + 4);
-          asm("" : "+v"(e), "+v"(u));
-          d[0] = QC ? 0.f : e[3]; d[1] = u[0]; d[2] = u[1]; d[3] = u[2]; d[4] = u[3];
-          d[5] = QC ? e[0] : 0.f; d[6] = 0.f; d[7] = 0.f;
-        } else {
-          floatx4 u = *reinterpret_cast<const floatx4*>(rp + 4);
-          const float e = QC ? rp[8] : rp[3];
-          asm("" : "+v"(u));
-          d[0] = QC ? 0.f : e; d[1] = u[0]; d[2] = u[1]; d[3] = u[2]; d[4] = u[3];
-          d[5] = QC ? e : 0.f; d[6] = 0.f; d[7] = 0.f;
-        }
-        return;
-      }
-      floatx4 u = *reinterpret_cast<const floatx4*>(stg + roff + rr * kQPS);
-      floatx4 v = *reinterpret_cast<const floatx4*>(stg + roff + rr * kQPS + 4);
-      asm("" : "+v"(u), "+v"(v));
-      d[0] = u[0]; d[1] = u[1]; d[2] = u[2]; d[3] = u[3];
-      d[4] = v[0]; d[5] = v[1]; d[6] = v[2]; d[7] = v[3];
+      const float* rp = stg + roff + rr * kQPS;
+      floatx4 u = *reinterpret_cast<const floatx4*>(rp + 4);
+      const float e = QC ? rp[8] : rp[3];
+      asm("" : "+v"(u));
+      d[0] = QC ? 0.f : e; d[1] = u[0]; d[2] = u[1]; d[3] = u[2]; d[4] = u[3];
+      d[5] = QC ? e : 0.f; d[6] = 0.f; d[7] = 0.f;
     };
     // column pass of one row (this quarter's 3 transformed columns)
     auto col_pass = [&](const float (&d)[8], float (&u)[3]) {
@@ -816,7 +688,7 @@ __global__ __launch_bounds__(kQNTH, 1) void wino4q_mfma_kernel(ConvArgs a) {
       if (DBG & 16) asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
       else q_lds_barrier();  // W(x), P(x + 1) complete; every wave is done with step x - 1
       constexpr int ord[9] = {0, 3, 6, 1, 4, 7, 2, 5, 8};
-      constexpr int kA = RPST_W4Q_AHEAD;  // A-operand groups read ahead
+      constexpr int kA = kQAhead;  // A-operand groups read ahead
       float4 w4[9];
 #pragma unroll
       for (int q = 0; q < kA; ++q)
@@ -833,9 +705,9 @@ __global__ __launch_bounds__(kQNTH, 1) void wino4q_mfma_kernel(ConvArgs a) {
         q_mfma<0>(acc[p][1], w4[p].y, V[p]);
         q_mfma<0>(acc[p][2], w4[p].z, V[p]);
         q_mfma<0>(acc[p][3], w4[p].w, V[p]);
-        if (q >= RPST_W4Q_WG0 && q < RPST_W4Q_WG0 + kQWPI) issue_w(x + 1, wsn, q - RPST_W4Q_WG0);
+        if (q >= kQWG0 && q < kQWG0 + kQWPI) issue_w(x + 1, wsn, q - kQWG0);
         // P(x + 4): K step ks + 4 of this co tile, or of the next one
-        if (q == RPST_W4Q_PG) {
+        if (q == kQPG) {
           const int k4 = ks + 4 < K4 ? ks + 4 : ks + 4 - K4;
           if (wide) issue_p(std::true_type{}, x + 4, k4, psx);
           else issue_p(std::false_type{}, x + 4, k4, psx);
@@ -857,28 +729,13 @@ __global__ __launch_bounds__(kQNTH, 1) void wino4q_mfma_kernel(ConvArgs a) {
     // their blocks through ws1 and each wave finishes its own 16 channels (co = 64 ctile +
     // 16 Q + 4 k + r) of tile (wr, tn)
     auto epilogue = [&](int ctile) {
-#ifdef RPST_W4Q_NOEPI  // register-pressure experiment: keep the accumulators live only
-      {
-        float t = 0.f;
-#pragma unroll
-        for (int p = 0; p < 9; ++p)
-#pragma unroll
-          for (int cb = 0; cb < 4; ++cb) t += acc[p][cb][0] + acc[p][cb][1] + acc[p][cb][2] + acc[p][cb][3];
-        q_args()->out[threadIdx.x + ctile] = t;
-#pragma unroll
-        for (int p = 0; p < 9; ++p)
-#pragma unroll
-          for (int cb = 0; cb < 4; ++cb) acc[p][cb] = floatx4{0.f, 0.f, 0.f, 0.f};
-        return;
-      }
-#endif
       if (DBG & 32) {  // keep the accumulators live, skip the epilogue
         float t = 0.f;
 #pragma unroll
         for (int p = 0; p < 9; ++p)
 #pragma unroll
           for (int cb = 0; cb < 4; ++cb) t += acc[p][cb][0];
-        if (t == 1.2345f) q_args()->out[threadIdx.x] = t;
+        if (t == 1.2345f) late_args()->out[threadIdx.x] = t;
 #pragma unroll
         for (int p = 0; p < 9; ++p)
 #pragma unroll
@@ -939,8 +796,8 @@ __global__ __launch_bounds__(kQNTH, 1) void wino4q_mfma_kernel(ConvArgs a) {
           }
 #pragma unroll
           for (int e2 = 0; e2 < 2; ++e2) {
-            q_at6(m[e2][0], P[e2][pt]);
-            q_at6(m[e2][1], P[e2][3 + pt]);
+            at6(m[e2][0], P[e2][pt]);
+            at6(m[e2][1], P[e2][3 + pt]);
           }
           if (!(DBG & 4) && (rp == 0 || pt < 2)) q_lds_barrier();  // the next pass rewrites ws1
         }
@@ -964,7 +821,7 @@ __global__ __launch_bounds__(kQNTH, 1) void wino4q_mfma_kernel(ConvArgs a) {
             float c6[6], y[4];
 #pragma unroll
             for (int I = 0; I < 6; ++I) c6[I] = P[e2][I][x];
-            q_at6(c6, y);
+            at6(c6, y);
 #pragma unroll
             for (int yy = 0; yy < 4; ++yy) Y[yy * 4 + x] = y[yy];
           }
@@ -996,10 +853,6 @@ __global__ __launch_bounds__(kQNTH, 1) void wino4q_mfma_kernel(ConvArgs a) {
       }
     }
   };
-#ifdef RPST_W4Q_ONEQ
-  body(std::integral_constant<int, 0>{});
-  if (0)
-#endif
   switch (wave & 3) {
     case 0: body(std::integral_constant<int, 0>{}); break;
     case 1: body(std::integral_constant<int, 1>{}); break;
@@ -1020,17 +873,11 @@ int wino4q_launch(ConvArgs& a, int in_op, hipStream_t st) {
   a.stat_P = a.tiles_x * a.tiles_y * 2;
   RPST_REQUIRE((int64_t)a.co_tiles * a.nchunks * kQWS * 4 < (1LL << 31),
                "conv2d: winograd4 weight image exceeds 2 GiB");
-  {
-    // blocks per spatial tile: the co tiles split over RPST_W4Q_COSPLIT same-XCD blocks
-    // (default 1: 128->256 @512^2 N64 27.08 / 27.70 / 29.04 ms at 1 / 2 / 4 blocks, the longer
-    // blocks amortise the ring's prologue; gpurun_out/w4q_cs)
-    const char* e = getenv("RPST_W4Q_COSPLIT");
-    int c = (e && *e) ? atoi(e) : 1;
-    c = c < 1 ? 1 : (c > a.co_tiles ? a.co_tiles : c);
-    while (a.co_tiles % c) --c;
-    a.cosplit = c;
-  }
-  const int64_t blocks = (int64_t)a.tiles_x * a.tiles_y * a.N * a.cosplit;
+  // one block per spatial tile loops over every co tile: splitting them over 2 / 4 same-XCD
+  // blocks measured 27.70 / 29.04 ms against 27.08 at 128->256 @512^2 N64 (the longer blocks
+  // amortise the ring's prologue; profiles/r05/order_ab.log has the re-run under the final order)
+  a.cosplit = 1;
+  const int64_t blocks = (int64_t)a.tiles_x * a.tiles_y * a.N;
   RPST_REQUIRE(blocks <= 0x7fffffffLL, "conv2d: grid too large");
   const unsigned nb = (unsigned)blocks;
   const bool stats = a.stat_part != nullptr, btab = a.btab != nullptr;
@@ -1043,11 +890,6 @@ int wino4q_launch(ConvArgs& a, int in_op, hipStream_t st) {
     else                                                                       \
       wino4q_mfma_kernel<OP, S, B, false><<<nb, kQNTH, 0, st>>>(a);            \
   } while (0)
-#ifdef RPST_W4Q_DEV
-  wino4q_mfma_kernel<RPST_IN_NONE, true, false, true><<<nb, kQNTH, 0, st>>>(a);
-  (void)stats; (void)btab;
-  if (0)
-#endif
   if (in_op == RPST_IN_UPSAMPLE2) {
     if (stats) RPST_W4Q_GO(RPST_IN_UPSAMPLE2, true, false);
     else RPST_W4Q_GO(RPST_IN_UPSAMPLE2, false, false);

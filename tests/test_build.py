@@ -22,7 +22,8 @@ def kernels():
 def test_expected_kernels_present(kernels):
     names = " ".join(k["name"] for k in kernels)
     for sym in ("conv_mfma_kernel", "plane_stats_kernel", "plane_apply_kernel",
-                "gemm_f32_kernel", "rowstats_kernel", "gemm_f64_kernel", "stat_merge_kernel"):
+                "gemm_f32_kernel", "rowstats_kernel", "gemm_f64_kernel", "stat_merge_kernel",
+                "wino_mfma_kernel", "wino4_mfma_kernel", "wino4q_mfma_kernel"):
         assert sym in names, sym
 
 

@@ -1,5 +1,5 @@
 # A/B of one environment switch on the AdaIN-RP layers (tools/bench_conv.py, F(4x4)), rounds
-# interleaved by process. Usage: VAR=RPST_WINO4_NOPRIO VALUES="0 1" bash tools/ab_env.sh <tag>
+# interleaved by process. Usage: VAR=RPST_W4Q VALUES="0 1" bash tools/ab_env.sh <tag>
 set -o pipefail
 R=$GRAFT_REPO_ROOT
 O=$R/gpurun_out/${1:-ab}
