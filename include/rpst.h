@@ -137,7 +137,10 @@ int rpst_conv2d_masked(const float* input, const float* packed_weight, const flo
  * weights with the AdaIN scale std_s/std_c folded in along Cin and a per-(n, co) bias by
  * border class carrying mean_s - mean_c*std_s/std_c, so the conv streams the raw feature
  * (conv(pad0(s*x + b)) = conv_{W*s}(pad0(x)) + sum over in-image taps of W*b). Same result
- * as rpst_conv2d within fp32 rounding; rpst_conv2d applies the affine in its tile loader. */
+ * as rpst_conv2d within fp32 rounding; rpst_conv2d applies the affine in its tile loader.
+ * The size does not depend on the calling thread's rpst_conv2d_set_precise /
+ * rpst_conv2d_set_quarter settings (it is the largest over all of them), so a workspace sized
+ * under one setting serves a launch under any other. */
 size_t rpst_conv2d_workspace_size(int N, int Cin, int Hs, int Ws, int Cout, int ksize,
                                   int in_op);
 int rpst_conv2d_ws(const float* input, const float* aux, const float* packed_weight,
@@ -148,7 +151,8 @@ int rpst_conv2d_ws(const float* input, const float* aux, const float* packed_wei
 /* Same conv, additionally returning calc_mean_std (base.py:399-407) of its OUTPUT per
  * (n, co): the statistics are reduced in the conv epilogue from registers and merged in
  * fp64, so an AdaIN consumer never re-reads the feature. mean/std_out: N*Cout floats.
- * Workspace: rpst_conv2d_stats_workspace_size(N, Cin, Hs, Ws, Cout, ksize, in_op). */
+ * Workspace: rpst_conv2d_stats_workspace_size(N, Cin, Hs, Ws, Cout, ksize, in_op), likewise
+ * independent of the precise level and the quarter setting. */
 size_t rpst_conv2d_stats_workspace_size(int N, int Cin, int Hs, int Ws, int Cout, int ksize,
                                         int in_op);
 int rpst_conv2d_stats(const float* input, const float* aux, const float* packed_weight,
@@ -176,8 +180,9 @@ int rpst_conv2d_skip_adain(const float* stylized, const float* content, const fl
                            int Cin, int H, int W, int Cout, int ksize, int pad_mode, int relu,
                            rpst_stream_t stream);
 
-/* Launch geometry (total threads) rpst_conv2d would use for this shape — host-only; lets
- * profilers match rocprofv3 per-dispatch records (Grid_Size) to a layer. */
+/* Launch geometry (total threads) rpst_conv2d would use for this shape under the calling
+ * thread's settings — host-only, read from the same plan the launch reads; lets profilers
+ * match rocprofv3 per-dispatch records (Grid_Size) to a layer. */
 int64_t rpst_conv2d_grid_threads(int N, int Cin, int Hs, int Ws, int Cout, int ksize,
                                  int in_op);
 
@@ -507,7 +512,10 @@ int rpst_wct_phase_ms(float* cov_ms, float* matfun_ms);
  * the consumer conv. F(4x4) layers fold T_n into per-image weights W T_n (fp64, rounded
  * once) and c_n into per-(n, co) border-class biases; other layers materialise T x + c.
  * x: (N, Cin, H, W) fp32; T: (N, Cin, Cin) fp64; offset: (N, Cin) fp64.
- * Workspace: rpst_conv2d_mix_workspace_size(N, Cin, H, W, Cout, ksize). */
+ * Workspace: rpst_conv2d_mix_workspace_size(N, Cin, H, W, Cout, ksize). It does not depend on
+ * the quarter setting but does on the precise level: at rpst_conv2d_set_precise(1) the layer
+ * leaves F(4x4) and the workspace holds T x + c (N*Cin*H*W floats), which every inference
+ * workspace would otherwise carry. Query it at the level the launch runs under. */
 size_t rpst_conv2d_mix_workspace_size(int N, int Cin, int H, int W, int Cout, int ksize);
 int rpst_conv2d_mix(const float* input, const double* T, const double* offset,
                     const float* packed_weight, const float* bias, float* out, int N, int Cin,

@@ -45,6 +45,29 @@ struct ConvArgs {
   int pool_out;
 };
 
+// What the calling thread's switches select, read once per ABI call (conv_mode() in
+// rpst_conv.hip); everything below the entry points takes it as an argument.
+struct ConvMode {
+  int precise;     // rpst_conv2d_set_precise: 0 / 1 (F(2x2) where F(4x4) would run) / 2
+  int quarter;     // 0 off / 1 default rule / 2 forced: rpst_conv2d_set_quarter, else RPST_W4Q
+  int algo;        // RPST_CONV_ALGO: -1 unset, else the RPST_CONV_* value asked for
+  bool narrow;     // RPST_CONV_NARROW (on unless "0")
+  int narrow_rpt;  // RPST_CONV_NARROW_RPT: 2 forces 2 rows per thread, 0 the default
+};
+
+// Launch shape of one kernel form. Each form's *_tiling(ConvArgs&) is a pure host function of
+// the shape fields of `a`: it fills a's tiling fields (Cout_pad, nchunks, tiles_x, tiles_y,
+// co_tiles, persist, cosplit, stat_P) and returns this. The planner and the form's *_launch
+// both call it, so a query and a launch cannot disagree.
+struct ConvTiling {
+  int64_t blocks;
+  int nth;  // threads per block
+  // statistics partials: rows per partial, partials per tile row, tile width; stat_t:
+  // [n][partial][co] order (the position-quarter kernel) instead of [n][co][partial]
+  int stat_nt, stat_wn, stat_tw;
+  bool stat_t;
+};
+
 // image n's input planes (block-uniform n)
 __device__ __forceinline__ const float* conv_in_img(const ConvArgs& a, int n, int64_t per) {
   return (a.in2_from > 0 && n >= a.in2_from) ? a.in2 + (int64_t)(n - a.in2_from) * per
@@ -227,36 +250,31 @@ __device__ __forceinline__ float halfwave_reduce_scatter(float (&v)[V], int j) {
 
 // ---- Winograd F(2x2,3x3) path (rpst_wino.hip) ----------------------------------------
 constexpr int kWinoNTH = 256;  // threads per block
-// tile shape in use: output channels (BM) x rows (TH, x kTW columns) per block
-int wino_bm();
-int wino_th();
-int wino_persist(int in_op, int64_t spatial_blocks);  // 1: grid over spatial tiles only, each block loops over co tiles
 // floats of the Winograd weight image (stored after the direct image for 3x3 convs)
 size_t wino_packed_floats(int Cout, int Cin);
 int wino_pack(const float* w, float* pk, int Cout, int Cin, hipStream_t st);
-// a: shape/operator fields filled in, a.wpk = the Winograd weight image. Sets the tiling
-// fields (Cout_pad, nchunks, tiles_*, co_tiles, stat_P) and launches.
+ConvTiling wino_tiling(ConvArgs& a, int in_op);
+// a: shape/operator fields filled in, a.wpk = the Winograd weight image. Applies
+// wino_tiling and launches.
 int wino_launch(ConvArgs& a, int in_op, hipStream_t st);
 
 // ---- Winograd F(4x4,3x3) path (rpst_wino4.hip) ----------------------------------------
 // 16 x 64 outputs x 32 channels per 512-thread block; statistics partials per tile row
 // of 4 rows x 64 columns.
-constexpr int kW4Rows = 16, kW4Cols = 64, kW4Co = 32;
 bool wino4_supports(int in_op);
 bool wino4_fits(int N, int Cin, int Hs, int Ws, int in_op);
-int wino4_persist();
-// tile rows per F(4x4) block: 4 (16 output rows) or 2 (the position-quarter kernel, or the
-// small layers' 2-row block); statistics partials are per tile row either way
-int wino4_rows(int Cin, int Cout, int in_op);
 size_t wino4_packed_floats(int Cout, int Cin);
 int wino4_pack(const float* w, float* pk, int Cout, int Cin, hipStream_t st);
+ConvTiling wino4_tiling(ConvArgs& a);
 int wino4_launch(ConvArgs& a, int in_op, hipStream_t st);
+// wino4_fold / wino4_mix: a.wpk is the image of the form that launches; quarter: that form is
+// the position-quarter one (rpst_wino4q.hip), whose layout the per-image weights then take
 size_t wino4_fold_floats(int N, int Cin, int Cout);
-int wino4_fold(ConvArgs& a, const float* direct_packed, int direct_cout_pad, float* ws,
-               hipStream_t st);
+int wino4_fold(ConvArgs& a, bool quarter, const float* direct_packed, int direct_cout_pad,
+               float* ws, hipStream_t st);
 size_t wino4_mix_floats(int N, int Cin, int Cout);
-int wino4_mix(ConvArgs& a, const double* T, const double* cvec, const float* direct_packed,
-              int direct_cout_pad, float* ws, hipStream_t st);
+int wino4_mix(ConvArgs& a, bool quarter, const double* T, const double* cvec,
+              const float* direct_packed, int direct_cout_pad, float* ws, hipStream_t st);
 
 // device helpers shared by the two F(4x4) kernels (rpst_wino4.hip, rpst_wino4q.hip)
 // kernel arguments loaded at their use (s_load through an opaque copy of the kernarg
@@ -319,24 +337,19 @@ __device__ __forceinline__ void w4_tile(int b, int tiles_x, int tiles_y, int& tx
 
 // ---- F(4x4,3x3), position-quarter form (rpst_wino4q.hip) ------------------------------
 // 8 x 64 outputs x 64 channels per 512-thread block, each wave 9 of the 36 positions. Its
-// weight image follows the F(4x4) one in the packed buffer; wino4_launch / wino4_fold /
-// wino4_mix dispatch to it for the layers wino4q_applies to.
-bool wino4q_applies(int Cin, int Cout, int in_op);
-// false while the calling thread is at precise level 2 (rpst_conv.hip)
-bool conv_quarter_allowed();
-// 0 off / 1 default rule / 2 forced: the calling thread's rpst_conv2d_set_quarter, else the
-// RPST_W4Q environment variable, read per call (rpst_conv.hip)
-int conv_quarter_mode();
+// weight image follows the F(4x4) one in the packed buffer. The planner (rpst_conv.hip) asks
+// wino4q_applies once per launch; the weight offset, the fold layout and the kernel follow it.
+bool wino4q_applies(int Cin, int Cout, int in_op, const ConvMode& m);
 size_t wino4q_packed_floats(int Cout, int Cin);
 int wino4q_pack(const float* w, float* pk, int Cout, int Cin, hipStream_t st);
 int wino4q_pack_mix(const double* wm, float* pk, int N, int Cout, int Cin, hipStream_t st);
 int wino4q_fold_w(const float* pk, float* out, const float* aux, int N, int Cout, int Cin,
                   hipStream_t st);
+ConvTiling wino4q_tiling(ConvArgs& a);
 int wino4q_launch(ConvArgs& a, int in_op, hipStream_t st);
 // floats of the F(4x4) weight image a layer launches with (per image when folded)
-inline size_t wino4_image_floats(int Cout, int Cin, int in_op) {
-  return wino4q_applies(Cin, Cout, in_op) ? wino4q_packed_floats(Cout, Cin)
-                                          : wino4_packed_floats(Cout, Cin);
+inline size_t wino4_image_floats(int Cout, int Cin, bool quarter) {
+  return quarter ? wino4q_packed_floats(Cout, Cin) : wino4_packed_floats(Cout, Cin);
 }
 // the larger of the two images: workspace sizes use it, so a workspace sized under one
 // precise / quarter setting stays large enough for a launch under another (with Cout % 64

@@ -414,18 +414,11 @@ __global__ void conv_pack_kernel(const float* __restrict__ w, float* __restrict_
   pk[i] = v;
 }
 
-struct TileCfg {
-  int BM, TH;
-};
-
-static TileCfg pick_cfg(int Cout) {
-  if (Cout > 64) return {128, 8};
-  if (Cout > 32) return {64, 8};
-  return {32, 16};
-}
+// output channels per block of the direct kernel
+static int direct_bm(int Cout) { return Cout > 64 ? 128 : (Cout > 32 ? 64 : 32); }
 
 static int pad_cout(int Cout) {
-  const int bm = pick_cfg(Cout).BM;
+  const int bm = direct_bm(Cout);
   return (Cout + bm - 1) / bm * bm;
 }
 
@@ -582,132 +575,102 @@ __global__ __launch_bounds__(256) void conv3x3_narrow_kernel(ConvArgs a) {
   }
 }
 
-static bool narrow_enabled() {
-  const char* e = getenv("RPST_CONV_NARROW");  // A/B switch
-  return !(e && *e && atoi(e) == 0);
-}
-
-// Tile variants per BM. RPST_CONV_VARIANT (tools/bench_conv.py) forces one for tuning;
-// otherwise pick_variant() chooses from the measured table (profiles/r01_bench_conv.log):
-//   BM=128: 3x3 -> v1 (128 co x 8x32 px, 8 accumulators/wave, 134-143 TF/s);
-//           max-pool input or 1x1 -> v2 (128 x 4x32, lighter loader, 113-128 TF/s);
-//   BM=64 / BM=32 -> v1 (4-channel chunks, double-buffered LDS, 1 barrier per chunk).
-// <BM, TH, WM, WN, NTH, CK, DB>: block tile BM x (TH x 32 px), WM x WN waves of NTH/64.
-template <int KS, int INOP>
-static void launch_conv(const ConvArgs& a, int BM, int variant, hipStream_t st) {
-  const int blocks = a.tiles_x * a.tiles_y * a.N * a.co_tiles;
-#define RPST_LAUNCH(BM_, TH_, WM_, WN_, NTH_, CK_, DB_) \
-  conv_mfma_kernel<KS, BM_, TH_, WM_, WN_, INOP, NTH_, CK_, DB_><<<blocks, NTH_, 0, st>>>(a)
-  constexpr int C8 = ConvK<KS>::CK, C4 = ConvK<KS>::CK / 2;
-  // loaders with 2-4 raw loads per element only get the short-tile variants (the tall
-  // ones run out of registers)
-  constexpr bool HEAVY = RawN<INOP>::R > 1;
-  if constexpr (HEAVY) {
-    if (BM == 128) {
-      if (variant == 4) RPST_LAUNCH(128, 4, 2, 2, 256, C4, true);
-      else RPST_LAUNCH(128, 4, 2, 2, 256, C8, false);
-    } else if (BM == 64) {
-      if (variant == 0) RPST_LAUNCH(64, 8, 1, 4, 256, C8, false);
-      else RPST_LAUNCH(64, 8, 1, 4, 256, C4, true);
-    } else {
-      if (variant == 2) RPST_LAUNCH(32, 8, 1, 4, 256, C8, false);
-      else RPST_LAUNCH(32, 8, 1, 4, 256, C4, true);
-    }
-  } else {
-  if (BM == 128) {
-    switch (variant) {
-      case 0: RPST_LAUNCH(128, 8, 2, 4, 512, C8, false); break;
-      case 2: RPST_LAUNCH(128, 4, 2, 2, 256, C8, false); break;
-      case 3: RPST_LAUNCH(128, 8, 2, 2, 256, C4, true); break;
-      case 4: RPST_LAUNCH(128, 4, 2, 2, 256, C4, true); break;
-      default: RPST_LAUNCH(128, 8, 2, 2, 256, C8, false);
-    }
-  } else if (BM == 64) {
-    switch (variant) {
-      case 0: RPST_LAUNCH(64, 8, 1, 4, 256, C8, false); break;
-      case 2: RPST_LAUNCH(64, 8, 1, 8, 512, C8, false); break;
-      default: RPST_LAUNCH(64, 8, 1, 4, 256, C4, true);
-    }
-  } else {
-    switch (variant) {
-      case 0: RPST_LAUNCH(32, 16, 1, 4, 256, C8, false); break;
-      case 2: RPST_LAUNCH(32, 8, 1, 4, 256, C8, false); break;
-      default: RPST_LAUNCH(32, 8, 1, 4, 256, C4, true);
-    }
-  }
-  }
-#undef RPST_LAUNCH
-}
-
 static bool heavy_loader(int in_op) {
   return in_op == RPST_IN_MAXPOOL2 || in_op == RPST_IN_ADD_UPSAMPLE2 ||
          in_op == RPST_IN_ADD_ADAIN;
 }
 
-static int pick_variant(int BM, int ksize, int in_op) {
-  if (BM == 128 && (heavy_loader(in_op) || ksize == 1)) return 2;
-  return 1;
-}
-
-// TH of a variant (the host needs it for the grid)
-static int variant_th(int BM, int variant) {
-  if (BM == 128) return (variant == 2 || variant == 4) ? 4 : 8;
-  if (BM == 64) return 8;
-  return variant == 0 ? 16 : 8;
-}
-
-// threads per workgroup of a variant
-static int variant_nth(int BM, int variant) {
-  return ((BM == 128 && variant == 0) || (BM == 64 && variant == 2)) ? 512 : 256;
-}
-
-// WN (waves along the pixel rows) of a variant: rows per wave = TH / WN
-static int variant_wn(int BM, int variant) {
-  if (BM == 128) return variant == 0 ? 4 : 2;
-  if (BM == 64) return variant == 2 ? 8 : 4;
-  return 4;
-}
-
-static int conv_variant(int BM, int ksize, int in_op) {
-  const char* e = getenv("RPST_CONV_VARIANT");
-  int v = (e && *e) ? atoi(e) : pick_variant(BM, ksize, in_op);
-  if (heavy_loader(in_op)) {  // the variants launch_conv instantiates for heavy loaders
-    if (BM == 128) v = (v == 4) ? 4 : 2;
-    else if (BM == 64) v = (v == 0) ? 0 : 1;
-    else v = (v == 2) ? 2 : 1;
+// Direct tiles <BM, TH, WM, WN, NTH, CK, DB>: block tile BM x (TH x 32 px), WM x WN waves of
+// NTH/64. BM = 128 runs 8 rows for a 3x3 conv with a one-load loader and 4 rows for a 1x1 conv
+// or a 2-4-load loader (the tall tile runs out of registers there); BM = 64 / 32 run 8 rows on
+// 4-channel chunks with double-buffered LDS. The measurements that settled these are in
+// DESIGN.md section 3 ("Conv kernel design", the tile table).
+template <int KS, int INOP>
+static void launch_conv(const ConvArgs& a, int BM, hipStream_t st) {
+  const int blocks = a.tiles_x * a.tiles_y * a.N * a.co_tiles;
+#define RPST_LAUNCH(BM_, TH_, WM_, WN_, NTH_, CK_, DB_) \
+  conv_mfma_kernel<KS, BM_, TH_, WM_, WN_, INOP, NTH_, CK_, DB_><<<blocks, NTH_, 0, st>>>(a)
+  constexpr int C8 = ConvK<KS>::CK, C4 = ConvK<KS>::CK / 2;
+  if (BM == 128) {
+    if constexpr (KS == 1 || RawN<INOP>::R > 1) RPST_LAUNCH(128, 4, 2, 2, 256, C8, false);
+    else RPST_LAUNCH(128, 8, 2, 2, 256, C8, false);
+  } else if (BM == 64) {
+    RPST_LAUNCH(64, 8, 1, 4, 256, C4, true);
+  } else {
+    RPST_LAUNCH(32, 8, 1, 4, 256, C4, true);
   }
-  return v;
+#undef RPST_LAUNCH
 }
 
-// Algorithm for a 3x3 conv: Winograd F(4x4,3x3) (rpst_wino4.hip) for the loader
-// operators it implements, F(2x2,3x3) (rpst_wino.hip) for the others, the direct implicit
-// GEMM for the 16-wide layers and every 1x1. RPST_CONV_ALGO=direct|winograd|winograd4
-// overrides (tests, A/B benches; winograd4 falls back to winograd where unsupported).
+// the tile launch_conv runs; its statistics epilogue exists for >= 4 rows per wave only
+static ConvTiling direct_tiling(ConvArgs& a, int ksize, int in_op) {
+  const int bm = direct_bm(a.Cout), ck = ck_of(ksize);
+  const int th = bm == 128 && (ksize == 1 || heavy_loader(in_op)) ? 4 : 8;
+  const int wn = bm == 128 ? 2 : 4;  // waves along the tile rows
+  a.Cout_pad = pad_cout(a.Cout);
+  a.nchunks = (a.Cin + ck - 1) / ck;
+  a.tiles_x = (a.W + kTW - 1) / kTW;
+  a.tiles_y = (a.H + th - 1) / th;
+  a.co_tiles = a.Cout_pad / bm;
+  a.stat_P = a.tiles_x * a.tiles_y * wn;
+  return {(int64_t)a.tiles_x * a.tiles_y * a.N * a.co_tiles, 256, th / wn, wn, kTW, false};
+}
+
+// Narrow kernel: 64 columns x 4 rpt rows per block, images on grid.z and row tiles on grid.y.
+// rpt (rows per thread): 4 for Cout <= 4 (16->3: 0.307 vs 0.348 ms; RPST_CONV_NARROW_RPT=2
+// overrides), 2 for Cout <= 16 (3->16 at 4 rows spills to scratch: 1.47 vs 0.51 ms). It reads
+// the direct weight image (Cout_pad) and has no statistics epilogue.
+static int narrow_rpt(int Cout, const ConvMode& m) {
+  return Cout <= 4 && m.narrow_rpt != 2 ? 4 : 2;
+}
+static ConvTiling narrow_tiling(ConvArgs& a, int rpt) {
+  const int rows = 4 * rpt;
+  a.Cout_pad = pad_cout(a.Cout);
+  a.nchunks = (a.Cin + ConvK<3>::CK - 1) / ConvK<3>::CK;
+  a.tiles_x = (a.W + kNrTW - 1) / kNrTW;
+  a.tiles_y = (a.H + rows - 1) / rows;
+  a.co_tiles = 1;
+  a.stat_P = 0;
+  return {(int64_t)a.tiles_x * a.tiles_y * a.N, 256, 0, 0, kNrTW, false};
+}
+
 // rpst_conv2d_set_precise: at 1 this thread's launches keep to F(2x2) where F(4x4) would
 // run; at 2 F(4x4) runs, on its 32-channel form only (wino4q_applies)
 static thread_local int t_conv_precise = 0;
 // rpst_conv2d_set_quarter: -1 (default) follows RPST_W4Q, read per launch
 static thread_local int t_conv_quarter = -1;
 
-bool conv_quarter_allowed() { return t_conv_precise != 2; }
-
-int conv_quarter_mode() {
-  if (t_conv_quarter >= 0) return t_conv_quarter;
+// The calling thread's switches and the environment's, read once per ABI call.
+static ConvMode conv_mode() {
+  ConvMode m{};
+  m.precise = t_conv_precise;
   const char* e = getenv("RPST_W4Q");
-  return (e && *e) ? atoi(e) : 1;
+  const int q = t_conv_quarter >= 0 ? t_conv_quarter : ((e && *e) ? atoi(e) : 1);
+  m.quarter = q == 2 ? 2 : q != 0;
+  e = getenv("RPST_CONV_ALGO");  // direct|winograd|winograd4 (tests, A/B benches)
+  m.algo = -1;
+  if (e && e[0] == 'd') m.algo = RPST_CONV_DIRECT;
+  else if (e && !strcmp(e, "winograd")) m.algo = RPST_CONV_WINOGRAD;
+  else if (e && !strcmp(e, "winograd4")) m.algo = RPST_CONV_WINOGRAD4;
+  e = getenv("RPST_CONV_NARROW");  // A/B switch
+  m.narrow = !(e && *e && atoi(e) == 0);
+  e = getenv("RPST_CONV_NARROW_RPT");
+  m.narrow_rpt = (e && *e && atoi(e) == 2) ? 2 : 0;
+  return m;
 }
 
-static int conv_algo(int Cout, int Cin, int Hs, int Ws, int ksize, int in_op) {
+// Algorithm for a 3x3 conv: Winograd F(4x4,3x3) (rpst_wino4.hip) for the loader
+// operators it implements, F(2x2,3x3) (rpst_wino.hip) for the others, the direct implicit
+// GEMM for the 16-wide layers and every 1x1. m.algo overrides (winograd4 falls back to
+// winograd where unsupported). What a launch needs may still move the choice: conv_plan.
+static int conv_algo(int Cout, int Cin, int Hs, int Ws, int ksize, int in_op, const ConvMode& m) {
   if (ksize != 3) return RPST_CONV_DIRECT;
   const bool w4 = wino4_supports(in_op) && wino4_fits(1, Cin, Hs, Ws, in_op);
   const bool nr = (in_op == RPST_IN_NONE || (in_op == RPST_IN_ADD_ADAIN && Cout <= 4)) &&
-                  narrow_shape(Cin, Cout) && narrow_enabled();
-  const char* e = getenv("RPST_CONV_ALGO");
-  if (e && *e) {
-    if (e[0] == 'd') return nr ? RPST_CONV_NARROW : RPST_CONV_DIRECT;
-    if (!strcmp(e, "winograd")) return RPST_CONV_WINOGRAD;
-    if (!strcmp(e, "winograd4")) return w4 ? RPST_CONV_WINOGRAD4 : RPST_CONV_WINOGRAD;
-  }
+                  narrow_shape(Cin, Cout) && m.narrow;
+  if (m.algo == RPST_CONV_DIRECT) return nr ? RPST_CONV_NARROW : RPST_CONV_DIRECT;
+  if (m.algo == RPST_CONV_WINOGRAD) return RPST_CONV_WINOGRAD;
+  if (m.algo == RPST_CONV_WINOGRAD4) return w4 ? RPST_CONV_WINOGRAD4 : RPST_CONV_WINOGRAD;
   // measured (profiles/r01_bench_conv_wino4.log): F(4x4) wins every layer with >= 16 input
   // channels it supports, the 16-wide 32->16 decoder layer included; the narrow shapes
   // (3->16 / 16->3 of the RP stacks, <= 4-channel outputs) run on the VALU kernel (3->16
@@ -717,105 +680,100 @@ static int conv_algo(int Cout, int Cin, int Hs, int Ws, int ksize, int in_op) {
   // 1.59 direct and 2.49 on the VALU kernel (tools/bench_conv.py); other inputs below 16
   // channels, and precise mode, stay direct
   if (nr) return RPST_CONV_NARROW;
-  if (Cin <= 4 && w4 && t_conv_precise != 1) return RPST_CONV_WINOGRAD4;
+  if (Cin <= 4 && w4 && m.precise != 1) return RPST_CONV_WINOGRAD4;
   if (Cin < 16) return RPST_CONV_DIRECT;
-  if (w4 && t_conv_precise != 1) return RPST_CONV_WINOGRAD4;
+  if (w4 && m.precise != 1) return RPST_CONV_WINOGRAD4;
   if (w4) return RPST_CONV_WINOGRAD;  // precise mode, same shapes as F(4x4)
   return Cout >= 32 ? RPST_CONV_WINOGRAD : RPST_CONV_DIRECT;
-}
-
-static void logical_hw(int Hs, int Ws, int in_op, int* H, int* W) {
-  *H = Hs;
-  *W = Ws;
-  if (in_op == RPST_IN_MAXPOOL2) {
-    *H = (Hs + 1) / 2;
-    *W = (Ws + 1) / 2;
-  } else if (in_op == RPST_IN_UPSAMPLE2) {
-    *H = 2 * Hs;
-    *W = 2 * Ws;
-  }
-}
-
-// Launch geometry shared by the entry points: blocks, threads per block, statistics
-// partials per plane and their (rows per partial, partials per tile row) layout.
-struct ConvGeom {
-  int algo;
-  int64_t blocks;
-  int nth, stat_P, stat_nt, stat_wn, stat_tw, tiles_x;
-  bool stat_t;  // partials in [n][partial][co] order (the position-quarter F(4x4) kernel)
-};
-
-// rows per thread of the narrow kernel: 4 for Cout <= 4 (16->3: 0.307 vs 0.348 ms;
-// RPST_CONV_NARROW_RPT=2 overrides), 2 for Cout <= 16 (3->16 at 4 rows spills to scratch:
-// 1.47 vs 0.51 ms)
-static int narrow_rpt(int Cout) {
-  const char* e = getenv("RPST_CONV_NARROW_RPT");
-  return Cout <= 4 && !(e && *e && atoi(e) == 2) ? 4 : 2;
-}
-
-// the narrow kernel puts the images on grid.z and the row tiles on grid.y (<= 65535 each);
-// it has no statistics epilogue
-static bool narrow_launchable(int N, int H, int Cout, bool stats) {
-  return !stats && N <= 65535 && (H + 4 * narrow_rpt(Cout) - 1) / (4 * narrow_rpt(Cout)) <= 65535;
-}
-
-static ConvGeom conv_geom(int N, int Cin, int Hs, int Ws, int Cout, int ksize, int in_op,
-                          bool stats = false) {
-  int H, W;
-  logical_hw(Hs, Ws, in_op, &H, &W);
-  ConvGeom g{};
-  g.algo = conv_algo(Cout, Cin, Hs, Ws, ksize, in_op);
-  if (g.algo == RPST_CONV_NARROW && !narrow_launchable(N, H, Cout, stats))
-    g.algo = RPST_CONV_DIRECT;
-  if (g.algo == RPST_CONV_NARROW) {
-    const int rows = 4 * narrow_rpt(Cout);
-    g.tiles_x = (W + kNrTW - 1) / kNrTW;
-    g.blocks = (int64_t)g.tiles_x * ((H + rows - 1) / rows) * N;
-    g.nth = 256;
-    g.stat_tw = kNrTW;
-    return g;
-  }
-  g.tiles_x = (W + kTW - 1) / kTW;
-  g.stat_tw = kTW;
-  if (g.algo == RPST_CONV_WINOGRAD4) {
-    const int nr = wino4_rows(Cin, Cout, in_op);
-    g.tiles_x = (W + kW4Cols - 1) / kW4Cols;
-    const int ty = (H + 4 * nr - 1) / (4 * nr);
-    g.blocks = (int64_t)g.tiles_x * ty * N * (wino4_persist() ? 1 : (Cout + kW4Co - 1) / kW4Co);
-    g.stat_t = wino4q_applies(Cin, Cout, in_op);
-    g.nth = g.stat_t ? 512 : 128 * nr;
-    g.stat_P = g.tiles_x * ty * nr;
-    g.stat_nt = 4;
-    g.stat_wn = nr;
-    g.stat_tw = kW4Cols;
-    return g;
-  }
-  if (g.algo == RPST_CONV_WINOGRAD) {
-    const int th = wino_th(), bm = wino_bm();
-    const int ty = (H + th - 1) / th;
-    g.blocks = (int64_t)g.tiles_x * ty * N * (wino_persist(in_op, (int64_t)g.tiles_x * ty * N) ? 1 : (Cout + bm - 1) / bm);
-    g.nth = kWinoNTH;
-    g.stat_P = g.tiles_x * ty;
-    g.stat_nt = th;
-    g.stat_wn = 1;
-    return g;
-  }
-  const TileCfg cfg = pick_cfg(Cout);
-  const int variant = conv_variant(cfg.BM, ksize, in_op);
-  const int th = variant_th(cfg.BM, variant), wn = variant_wn(cfg.BM, variant);
-  const int ty = (H + th - 1) / th;
-  g.blocks = (int64_t)g.tiles_x * ty * N * (pad_cout(Cout) / cfg.BM);
-  g.nth = variant_nth(cfg.BM, variant);
-  g.stat_P = g.tiles_x * ty * wn;
-  g.stat_nt = th / wn;
-  g.stat_wn = wn;
-  return g;
 }
 
 static size_t direct_packed_floats(int Cout, int Cin, int ksize) {
   const int ck = ck_of(ksize);
   const size_t nch = (size_t)(Cin + ck - 1) / ck;
   return nch * ksize * ksize * ck * (size_t)pad_cout(Cout);
+}
+
+// the shape fields of a launch: H, W are the logical (post-in_op) size
+static ConvArgs conv_shape(int N, int Cin, int Hs, int Ws, int Cout, int in_op) {
+  ConvArgs a{};
+  a.N = N;
+  a.Cin = Cin;
+  a.Hs = a.H = Hs;
+  a.Ws = a.W = Ws;
+  a.Cout = Cout;
+  if (in_op == RPST_IN_MAXPOOL2) {
+    a.H = (Hs + 1) / 2;
+    a.W = (Ws + 1) / 2;
+  } else if (in_op == RPST_IN_UPSAMPLE2) {
+    a.H = 2 * Hs;
+    a.W = 2 * Ws;
+  }
+  return a;
+}
+
+// What a call needs of its kernel: the statistics epilogue, the residual epilogue, and
+// whether it offers per-image weights to fold into (an RPST_IN_ADAIN loader with a workspace,
+// or rpst_conv2d_mix's T / offset).
+struct ConvNeeds {
+  bool stats, residual, fold;
+};
+
+// Everything decided about one launch, in one place. The launch, the statistics merge and the
+// query functions (rpst_conv2d_algorithm / _quarter / _grid_threads, workspace sizes) read it.
+struct ConvPlan {
+  int algo;      // the RPST_CONV_* that runs, downgrades applied
+  bool quarter;  // F(4x4): the position-quarter form (rpst_wino4q.hip)
+  bool fold;     // F(4x4): per-image weights and border biases (wino4_fold / wino4_mix)
+  int op;        // the loader operator that launches: RPST_IN_NONE once AdaIN folds
+  int rpt;       // narrow: rows per thread
+  size_t wofs;   // floats from the packed buffer's start to the weight image that launches
+  ConvTiling t;
+};
+
+// a: shape fields set (conv_shape); its tiling fields are filled for the planned kernel.
+static ConvPlan conv_plan(ConvArgs& a, int ksize, int in_op, const ConvMode& m, ConvNeeds need) {
+  ConvPlan p{};
+  p.op = in_op;
+  p.algo = conv_algo(a.Cout, a.Cin, a.Hs, a.Ws, ksize, in_op, m);
+  if (p.algo == RPST_CONV_NARROW) {
+    p.rpt = narrow_rpt(a.Cout, m);
+    p.t = narrow_tiling(a, p.rpt);
+    // no statistics epilogue; grid.y / grid.z hold <= 65535 row tiles / images
+    if (need.stats || a.N > 65535 || a.tiles_y > 65535) p.algo = RPST_CONV_DIRECT;
+  }
+  // the residual epilogue (SANet out_conv, sanet.py:97-98) exists on the direct and narrow
+  // kernels only
+  if (need.residual && (p.algo == RPST_CONV_WINOGRAD || p.algo == RPST_CONV_WINOGRAD4))
+    p.algo = RPST_CONV_DIRECT;
+  if (p.algo == RPST_CONV_WINOGRAD4) {
+    // AdaIN in the weights (not with the statistics epilogue: that layer keeps the loader)
+    p.fold = need.fold && !need.stats && a.H >= 2 && a.W >= 2;
+    if (p.fold) p.op = RPST_IN_NONE;
+    p.quarter = wino4q_applies(a.Cin, a.Cout, p.op, m);
+    // the F(4x4) image follows the direct and F(2x2) ones, the quarter form's follows it
+    p.wofs = direct_packed_floats(a.Cout, a.Cin, ksize) + wino_packed_floats(a.Cout, a.Cin) +
+             (p.quarter ? wino4_packed_floats(a.Cout, a.Cin) : 0);
+    p.t = p.quarter ? wino4q_tiling(a) : wino4_tiling(a);
+  } else if (p.algo == RPST_CONV_WINOGRAD) {
+    p.wofs = direct_packed_floats(a.Cout, a.Cin, ksize);
+    p.t = wino_tiling(a, in_op);
+  } else if (p.algo == RPST_CONV_DIRECT) {
+    p.t = direct_tiling(a, ksize, in_op);
+  }
+  return p;
+}
+
+// the largest `bytes(mode)` over every precise level and quarter setting (the thread's other
+// switches as they are): a workspace sized under one setting serves a launch under any other
+template <class F>
+static size_t max_over_modes(ConvMode m, F bytes) {
+  size_t best = 0;
+  for (m.precise = 0; m.precise < 3; ++m.precise)
+    for (m.quarter = 0; m.quarter < 3; ++m.quarter) {
+      const size_t b = bytes(m);
+      best = b > best ? b : best;
+    }
+  return best;
 }
 
 }  // namespace rpst
@@ -833,12 +791,18 @@ extern "C" size_t rpst_conv2d_packed_size(int Cout, int Cin, int ksize) {
   return f * sizeof(float);
 }
 
+// the plan of a plain launch of this shape under the calling thread's mode
+static ConvPlan query_plan(int N, int Cin, int Hs, int Ws, int Cout, int ksize, int in_op) {
+  ConvArgs a = conv_shape(N, Cin, Hs, Ws, Cout, in_op);
+  return conv_plan(a, ksize, in_op, conv_mode(), {});
+}
+
 extern "C" int64_t rpst_conv2d_grid_threads(int N, int Cin, int Hs, int Ws, int Cout,
                                             int ksize, int in_op) {
   if (N <= 0 || Cin <= 0 || Hs <= 0 || Ws <= 0 || Cout <= 0 || (ksize != 1 && ksize != 3))
     return 0;
-  const ConvGeom g = conv_geom(N, Cin, Hs, Ws, Cout, ksize, in_op);
-  return g.blocks * g.nth;
+  const ConvTiling t = query_plan(N, Cin, Hs, Ws, Cout, ksize, in_op).t;
+  return t.blocks * t.nth;
 }
 
 extern "C" int rpst_conv2d_set_precise(int on) {
@@ -854,12 +818,11 @@ extern "C" int rpst_conv2d_set_quarter(int mode) {
 }
 
 extern "C" int rpst_conv2d_algorithm(int Cout, int Cin, int Hs, int Ws, int ksize, int in_op) {
-  return conv_algo(Cout, Cin, Hs, Ws, ksize, in_op);
+  return query_plan(1, Cin, Hs, Ws, Cout, ksize, in_op).algo;
 }
 
 extern "C" int rpst_conv2d_quarter(int Cout, int Cin, int Hs, int Ws, int ksize, int in_op) {
-  if (conv_algo(Cout, Cin, Hs, Ws, ksize, in_op) != RPST_CONV_WINOGRAD4) return 0;
-  return wino4q_applies(Cin, Cout, in_op) ? 1 : 0;
+  return query_plan(1, Cin, Hs, Ws, Cout, ksize, in_op).quarter ? 1 : 0;
 }
 
 extern "C" int rpst_conv2d_pack(const float* weight, float* packed, int Cout, int Cin,
@@ -902,171 +865,142 @@ __global__ __launch_bounds__(256) void mask_apply_kernel(float* __restrict__ out
   }
 }
 
-static int conv_common(const float* input, const float* aux, const float* aux2,
-                       const float* packed_weight,
-                       const float* bias, const float* residual, float* out, int N, int Cin,
-                       int Hs, int Ws, int Cout, int ksize, int pad_mode, int in_op, int relu,
-                       float2* stat_part, int* stat_P, ConvArgs* args_out, hipStream_t st,
-                       float* fold_ws = nullptr, int skip_from = 0,
-                       const float* in2 = nullptr, int in2_from = 0,
-                       const float* mask = nullptr, int pool_out = 0) {
-  RPST_REQUIRE(input && packed_weight && out, "conv2d: null pointer");
-  RPST_REQUIRE(N > 0 && Cin > 0 && Cout > 0 && Hs > 0 && Ws > 0, "conv2d: bad shape");
-  RPST_REQUIRE(ksize == 1 || ksize == 3, "conv2d: ksize must be 1 or 3, got %d", ksize);
-  RPST_REQUIRE(pad_mode == RPST_PAD_ZERO || pad_mode == RPST_PAD_REFLECT, "conv2d: bad pad");
-  RPST_REQUIRE(in_op >= RPST_IN_NONE && in_op <= RPST_IN_ADD_ADAIN, "conv2d: bad in_op");
-  RPST_REQUIRE(relu >= RPST_ACT_NONE && relu <= RPST_ACT_LRELU, "conv2d: bad activation %d", relu);
-  RPST_REQUIRE(!(mask && stat_part), "conv2d: the mask epilogue has no statistics");
-  RPST_REQUIRE(!(pool_out && (stat_part || mask || residual)),
+// One conv launch as the entry points ask for it; what a call does not set is null / zero.
+struct ConvReq {
+  const float* input;
+  const float* aux;   // the loader operator's second tensor / AdaIN statistics
+  const float* aux2;  // RPST_IN_ADD_ADAIN: the content feature
+  const float* packed_weight;
+  const float* bias;
+  const float* residual;
+  float* out;
+  int N, Cin, Hs, Ws, Cout, ksize, pad_mode, in_op, relu;
+  hipStream_t st;
+  float2* stat_part;  // statistics partials (rpst_conv2d_stats)
+  float* fold_ws;     // workspace for per-image folded weights (RPST_IN_ADAIN, or T / offset)
+  int skip_from;      // ConvArgs::skip_from
+  const float* in2;   // ConvArgs::in2, in2_from
+  int in2_from;
+  const float* mask;  // ConvArgs::mask
+  int pool_out;       // ConvArgs::pool_out
+  // rpst_conv2d_mix: conv(pad(T_n x + offset_n)) with both folded into fold_ws (wino4_mix);
+  // the caller has checked that the plan folds
+  const double* T;
+  const double* offset;
+};
+
+// validates r, fills the kernel arguments and plans the launch
+static int conv_prepare(const ConvReq& r, const ConvMode& m, ConvArgs& a, ConvPlan& p) {
+  RPST_REQUIRE(r.input && r.packed_weight && r.out, "conv2d: null pointer");
+  RPST_REQUIRE(r.N > 0 && r.Cin > 0 && r.Cout > 0 && r.Hs > 0 && r.Ws > 0, "conv2d: bad shape");
+  RPST_REQUIRE(r.ksize == 1 || r.ksize == 3, "conv2d: ksize must be 1 or 3, got %d", r.ksize);
+  RPST_REQUIRE(r.pad_mode == RPST_PAD_ZERO || r.pad_mode == RPST_PAD_REFLECT, "conv2d: bad pad");
+  RPST_REQUIRE(r.in_op >= RPST_IN_NONE && r.in_op <= RPST_IN_ADD_ADAIN, "conv2d: bad in_op");
+  RPST_REQUIRE(r.relu >= RPST_ACT_NONE && r.relu <= RPST_ACT_LRELU, "conv2d: bad activation %d", r.relu);
+  RPST_REQUIRE(!(r.mask && r.stat_part), "conv2d: the mask epilogue has no statistics");
+  RPST_REQUIRE(!(r.pool_out && (r.stat_part || r.mask || r.residual)),
                "conv2d: the pooled output has no statistics / mask / residual epilogue");
-  ConvArgs a{};
-  a.mask = mask;
-  a.pool_out = pool_out;
-  a.skip_from = skip_from;
-  a.in = input;
-  a.in2 = in2;
-  a.in2_from = in2 ? in2_from : 0;
-  a.aux = aux;
-  a.aux2 = aux2;
-  a.wpk = packed_weight;
-  a.bias = bias;
-  a.res = residual;
-  a.out = out;
-  a.N = N;
-  a.Cin = Cin;
-  a.Hs = Hs;
-  a.Ws = Ws;
-  a.Cout = Cout;
-  a.pad = pad_mode;
-  a.relu = relu;
-  switch (in_op) {
-    case RPST_IN_MAXPOOL2:
-      a.H = (Hs + 1) / 2;
-      a.W = (Ws + 1) / 2;
-      break;
-    case RPST_IN_UPSAMPLE2:
-      a.H = 2 * Hs;
-      a.W = 2 * Ws;
-      break;
-    case RPST_IN_ADD_UPSAMPLE2:
-      RPST_REQUIRE(aux != nullptr, "conv2d: ADD_UPSAMPLE2 needs aux");
-      RPST_REQUIRE((Hs % 2) == 0 && (Ws % 2) == 0, "conv2d: ADD_UPSAMPLE2 needs even H,W");
-      a.H = Hs;
-      a.W = Ws;
-      break;
-    case RPST_IN_ADAIN:
-      RPST_REQUIRE(aux != nullptr, "conv2d: ADAIN needs aux (AdaIN statistics)");
-      a.H = Hs;
-      a.W = Ws;
-      break;
-    case RPST_IN_ADD_ADAIN:
-      RPST_REQUIRE(aux != nullptr && aux2 != nullptr,
-                   "conv2d: ADD_ADAIN needs the content feature and AdaIN statistics");
-      a.H = Hs;
-      a.W = Ws;
-      break;
-    default:
-      a.H = Hs;
-      a.W = Ws;
+  if (r.in_op == RPST_IN_ADD_UPSAMPLE2) {
+    RPST_REQUIRE(r.aux != nullptr, "conv2d: ADD_UPSAMPLE2 needs aux");
+    RPST_REQUIRE((r.Hs % 2) == 0 && (r.Ws % 2) == 0, "conv2d: ADD_UPSAMPLE2 needs even H,W");
+  } else if (r.in_op == RPST_IN_ADAIN) {
+    RPST_REQUIRE(r.aux != nullptr, "conv2d: ADAIN needs aux (AdaIN statistics)");
+  } else if (r.in_op == RPST_IN_ADD_ADAIN) {
+    RPST_REQUIRE(r.aux != nullptr && r.aux2 != nullptr,
+                 "conv2d: ADD_ADAIN needs the content feature and AdaIN statistics");
   }
-  if (ksize == 3 && pad_mode == RPST_PAD_REFLECT)
+  a = conv_shape(r.N, r.Cin, r.Hs, r.Ws, r.Cout, r.in_op);
+  a.in = r.input;
+  a.in2 = r.in2;
+  a.in2_from = r.in2 ? r.in2_from : 0;
+  a.aux = r.aux;
+  a.aux2 = r.aux2;
+  a.bias = r.bias;
+  a.res = r.residual;
+  a.out = r.out;
+  a.pad = r.pad_mode;
+  a.relu = r.relu;
+  a.stat_part = r.stat_part;
+  a.skip_from = r.skip_from;
+  a.mask = r.mask;
+  a.pool_out = r.pool_out;
+  if (r.ksize == 3 && r.pad_mode == RPST_PAD_REFLECT)
     RPST_REQUIRE(a.H >= 2 && a.W >= 2, "conv2d: reflect padding needs H,W >= 2");
-  RPST_REQUIRE((int64_t)N * (Cout > Cin ? Cout : Cin) * a.H * a.W < (1LL << 40),
+  RPST_REQUIRE((int64_t)r.N * (r.Cout > r.Cin ? r.Cout : r.Cin) * a.H * a.W < (1LL << 40),
                "conv2d: tensor too large");
   // per-image input (plus one chunk of channel padding) must be addressable by a 31-bit
   // buffer offset
-  RPST_REQUIRE(((int64_t)Cin + 16) * Hs * Ws * 4 < (1LL << 31),
+  RPST_REQUIRE(((int64_t)r.Cin + 16) * r.Hs * r.Ws * 4 < (1LL << 31),
                "conv2d: one image's input exceeds 2 GiB");
-  int algo = conv_algo(Cout, Cin, Hs, Ws, ksize, in_op);
-  if (algo == RPST_CONV_NARROW && !narrow_launchable(N, a.H, Cout, stat_part != nullptr))
-    algo = RPST_CONV_DIRECT;
-  // the residual epilogue (SANet out_conv, sanet.py:97-98) exists on the direct and narrow
-  // kernels only
-  if (residual && (algo == RPST_CONV_WINOGRAD || algo == RPST_CONV_WINOGRAD4))
-    algo = RPST_CONV_DIRECT;
-  RPST_REQUIRE(!pool_out || algo == RPST_CONV_WINOGRAD4,
+  const bool fold = r.fold_ws && (r.in_op == RPST_IN_ADAIN || r.T);
+  p = conv_plan(a, r.ksize, r.in_op, m, {r.stat_part != nullptr, r.residual != nullptr, fold});
+  RPST_REQUIRE(!r.pool_out || p.algo == RPST_CONV_WINOGRAD4,
                "conv2d_pool: the pooled-output epilogue exists on the F(4x4) path only "
                "(rpst_conv2d_algorithm == RPST_CONV_WINOGRAD4)");
-  if (algo == RPST_CONV_WINOGRAD4) {
-    a.wpk = packed_weight + direct_packed_floats(Cout, Cin, ksize) + wino_packed_floats(Cout, Cin);
-    a.stat_part = stat_part;
-    int op = in_op;
-    // AdaIN in the weights (not with the statistics epilogue: that layer keeps the loader)
-    const bool fold = in_op == RPST_IN_ADAIN && fold_ws && !stat_part && a.H >= 2 && a.W >= 2;
-    if (fold) op = RPST_IN_NONE;
-    // the position-quarter kernel's image follows the F(4x4) one
-    if (wino4q_applies(Cin, Cout, op)) a.wpk += wino4_packed_floats(Cout, Cin);
-    if (fold) {
-      if (int e = wino4_fold(a, packed_weight, pad_cout(Cout), fold_ws, st)) return e;
+  RPST_REQUIRE(!r.T || p.fold, "conv2d_mix: T / offset on a launch that does not fold them");
+  a.wpk = r.packed_weight + p.wofs;
+  return RPST_OK;
+}
+
+template <int KS, int INOP>
+static int launch_direct(const ConvArgs& a, hipStream_t st) {
+  launch_conv<KS, INOP>(a, direct_bm(a.Cout), st);
+  return launch_status("conv_mfma_kernel");
+}
+
+static int conv_launch(const ConvReq& r, ConvArgs& a, const ConvPlan& p) {
+  hipStream_t st = r.st;
+  if (p.algo == RPST_CONV_WINOGRAD4) {
+    if (p.fold) {
+      const int e = r.T ? wino4_mix(a, p.quarter, r.T, r.offset, r.packed_weight,
+                                    pad_cout(r.Cout), r.fold_ws, st)
+                        : wino4_fold(a, p.quarter, r.packed_weight, pad_cout(r.Cout), r.fold_ws, st);
+      if (e) return e;
     }
-    if (int e = wino4_launch(a, op, st)) return e;
-    if (mask) {  // F(4x4)'s epilogue has no mask: threshold the output in a second pass
-      const int64_t n = (int64_t)N * Cout * a.H * a.W;
-      mask_apply_kernel<<<(unsigned)((n + 1023) / 1024), 256, 0, st>>>(out, mask, n);
-      if (int e = launch_status("mask_apply_kernel")) return e;
+    if (int e = p.quarter ? wino4q_launch(a, p.op, st) : wino4_launch(a, p.op, st)) return e;
+    if (r.mask) {  // F(4x4)'s epilogue has no mask: threshold the output in a second pass
+      const int64_t n = (int64_t)r.N * r.Cout * a.H * a.W;
+      mask_apply_kernel<<<(unsigned)((n + 1023) / 1024), 256, 0, st>>>(r.out, r.mask, n);
+      return launch_status("mask_apply_kernel");
     }
-    if (stat_P) *stat_P = a.stat_P;
-    if (args_out) *args_out = a;
     return RPST_OK;
   }
-  if (algo == RPST_CONV_WINOGRAD) {
-    a.wpk = packed_weight + direct_packed_floats(Cout, Cin, ksize);
-    a.stat_part = stat_part;
-    if (int e = wino_launch(a, in_op, st)) return e;
-    if (stat_P) *stat_P = a.stat_P;
-    if (args_out) *args_out = a;
-    return RPST_OK;
-  }
-  const TileCfg cfg = pick_cfg(Cout);
-  const int variant = conv_variant(cfg.BM, ksize, in_op);
-  const int th = variant_th(cfg.BM, variant);
-  const int ck = ck_of(ksize);
-  a.Cout_pad = pad_cout(Cout);
-  a.nchunks = (Cin + ck - 1) / ck;
-  a.tiles_x = (a.W + kTW - 1) / kTW;
-  a.tiles_y = (a.H + th - 1) / th;
-  a.co_tiles = a.Cout_pad / cfg.BM;
-  const int wn = variant_wn(cfg.BM, variant);
-  a.stat_P = a.tiles_x * a.tiles_y * wn;
-  a.stat_part = stat_part;
-  if (stat_P) *stat_P = a.stat_P;
-  const int64_t blocks = (int64_t)a.tiles_x * a.tiles_y * N * a.co_tiles;
-  RPST_REQUIRE(blocks <= 0x7fffffffLL, "conv2d: grid too large");
-  if (args_out) *args_out = a;
-  if (algo == RPST_CONV_NARROW) {
-    const int rpt = narrow_rpt(Cout);
-    const int nco = Cout <= 4 ? 4 : 16;
-    RPST_REQUIRE(Cin * 9 * nco <= kNrWl, "conv2d: narrow weights exceed LDS");
-    dim3 grid((unsigned)((a.W + kNrTW - 1) / kNrTW), (unsigned)((a.H + 4 * rpt - 1) / (4 * rpt)), N);
-    if (in_op == RPST_IN_ADD_ADAIN) {
-      RPST_REQUIRE(Cout <= 4, "conv2d: narrow skip-AdaIN conv needs Cout <= 4");
-      if (rpt == 4) conv3x3_narrow_kernel<4, 4, RPST_IN_ADD_ADAIN><<<grid, 256, 0, st>>>(a);
+  if (p.algo == RPST_CONV_WINOGRAD) return wino_launch(a, r.in_op, st);
+  if (p.algo == RPST_CONV_NARROW) {
+    RPST_REQUIRE(r.Cin * 9 * (r.Cout <= 4 ? 4 : 16) <= kNrWl, "conv2d: narrow weights exceed LDS");
+    const dim3 grid((unsigned)a.tiles_x, (unsigned)a.tiles_y, r.N);
+    if (r.in_op == RPST_IN_ADD_ADAIN) {
+      RPST_REQUIRE(r.Cout <= 4, "conv2d: narrow skip-AdaIN conv needs Cout <= 4");
+      if (p.rpt == 4) conv3x3_narrow_kernel<4, 4, RPST_IN_ADD_ADAIN><<<grid, 256, 0, st>>>(a);
       else conv3x3_narrow_kernel<4, 2, RPST_IN_ADD_ADAIN><<<grid, 256, 0, st>>>(a);
-    } else if (Cout <= 4) {
-      if (rpt == 4) conv3x3_narrow_kernel<4, 4><<<grid, 256, 0, st>>>(a);
+    } else if (r.Cout <= 4) {
+      if (p.rpt == 4) conv3x3_narrow_kernel<4, 4><<<grid, 256, 0, st>>>(a);
       else conv3x3_narrow_kernel<4, 2><<<grid, 256, 0, st>>>(a);
     } else {
       conv3x3_narrow_kernel<16, 2><<<grid, 256, 0, st>>>(a);
     }
     return launch_status("conv3x3_narrow_kernel");
   }
-  if (ksize == 1) {
-    RPST_REQUIRE(in_op == RPST_IN_NONE, "conv2d: 1x1 conv supports in_op NONE only");
-    launch_conv<1, RPST_IN_NONE>(a, cfg.BM, variant, st);
-  } else if (in_op == RPST_IN_MAXPOOL2) {
-    launch_conv<3, RPST_IN_MAXPOOL2>(a, cfg.BM, variant, st);
-  } else if (in_op == RPST_IN_UPSAMPLE2) {
-    launch_conv<3, RPST_IN_UPSAMPLE2>(a, cfg.BM, variant, st);
-  } else if (in_op == RPST_IN_ADD_UPSAMPLE2) {
-    launch_conv<3, RPST_IN_ADD_UPSAMPLE2>(a, cfg.BM, variant, st);
-  } else if (in_op == RPST_IN_ADAIN) {
-    launch_conv<3, RPST_IN_ADAIN>(a, cfg.BM, variant, st);
-  } else if (in_op == RPST_IN_ADD_ADAIN) {
-    launch_conv<3, RPST_IN_ADD_ADAIN>(a, cfg.BM, variant, st);
-  } else {
-    launch_conv<3, RPST_IN_NONE>(a, cfg.BM, variant, st);
+  RPST_REQUIRE(p.t.blocks <= 0x7fffffffLL, "conv2d: grid too large");
+  if (r.ksize == 1) {
+    RPST_REQUIRE(r.in_op == RPST_IN_NONE, "conv2d: 1x1 conv supports in_op NONE only");
+    return launch_direct<1, RPST_IN_NONE>(a, st);
   }
-  return launch_status("conv_mfma_kernel");
+  switch (r.in_op) {
+    case RPST_IN_MAXPOOL2: return launch_direct<3, RPST_IN_MAXPOOL2>(a, st);
+    case RPST_IN_UPSAMPLE2: return launch_direct<3, RPST_IN_UPSAMPLE2>(a, st);
+    case RPST_IN_ADD_UPSAMPLE2: return launch_direct<3, RPST_IN_ADD_UPSAMPLE2>(a, st);
+    case RPST_IN_ADAIN: return launch_direct<3, RPST_IN_ADAIN>(a, st);
+    case RPST_IN_ADD_ADAIN: return launch_direct<3, RPST_IN_ADD_ADAIN>(a, st);
+    default: return launch_direct<3, RPST_IN_NONE>(a, st);
+  }
+}
+
+static int conv_common(const ConvReq& r, const ConvMode& m) {
+  ConvArgs a;
+  ConvPlan p;
+  if (int e = conv_prepare(r, m, a, p)) return e;
+  return conv_launch(r, a, p);
 }
 
 extern "C" int rpst_conv2d(const float* input, const float* aux, const float* packed_weight,
@@ -1074,9 +1008,11 @@ extern "C" int rpst_conv2d(const float* input, const float* aux, const float* pa
                            int Cin, int Hs, int Ws, int Cout, int ksize, int pad_mode,
                            int in_op, int relu, rpst_stream_t stream) {
   RPST_REQUIRE(in_op != RPST_IN_ADD_ADAIN, "conv2d: ADD_ADAIN goes through rpst_conv2d_skip_adain");
-  return conv_common(input, aux, nullptr, packed_weight, bias, residual, out, N, Cin, Hs, Ws,
-                     Cout, ksize, pad_mode, in_op, relu, nullptr, nullptr, nullptr,
-                     as_stream(stream));
+  return conv_common({.input = input, .aux = aux, .packed_weight = packed_weight, .bias = bias,
+                      .residual = residual, .out = out, .N = N, .Cin = Cin, .Hs = Hs, .Ws = Ws,
+                      .Cout = Cout, .ksize = ksize, .pad_mode = pad_mode, .in_op = in_op,
+                      .relu = relu, .st = as_stream(stream)},
+                     conv_mode());
 }
 
 extern "C" int rpst_conv2d_pair(const float* input, const float* input2, int n1,
@@ -1085,9 +1021,12 @@ extern "C" int rpst_conv2d_pair(const float* input, const float* input2, int n1,
                                 int relu, rpst_stream_t stream) {
   RPST_REQUIRE(n1 > 0 && n1 <= N, "conv2d_pair: need 0 < n1 <= N (n1=%d, N=%d)", n1, N);
   RPST_REQUIRE(n1 == N || input2, "conv2d_pair: null second input");
-  return conv_common(input, nullptr, nullptr, packed_weight, bias, nullptr, out, N, Cin, Hs, Ws,
-                     Cout, ksize, pad_mode, RPST_IN_NONE, relu, nullptr, nullptr, nullptr,
-                     as_stream(stream), nullptr, 0, n1 < N ? input2 : nullptr, n1 < N ? n1 : 0);
+  return conv_common({.input = input, .packed_weight = packed_weight, .bias = bias, .out = out,
+                      .N = N, .Cin = Cin, .Hs = Hs, .Ws = Ws, .Cout = Cout, .ksize = ksize,
+                      .pad_mode = pad_mode, .in_op = RPST_IN_NONE, .relu = relu,
+                      .st = as_stream(stream), .in2 = n1 < N ? input2 : nullptr,
+                      .in2_from = n1 < N ? n1 : 0},
+                     conv_mode());
 }
 
 extern "C" int rpst_conv2d_masked(const float* input, const float* packed_weight,
@@ -1095,9 +1034,11 @@ extern "C" int rpst_conv2d_masked(const float* input, const float* packed_weight
                                   int Cin, int Hs, int Ws, int Cout, int ksize, int pad_mode,
                                   rpst_stream_t stream) {
   RPST_REQUIRE(mask, "conv2d_masked: null mask");
-  return conv_common(input, nullptr, nullptr, packed_weight, bias, nullptr, out, N, Cin, Hs, Ws,
-                     Cout, ksize, pad_mode, RPST_IN_NONE, RPST_ACT_NONE, nullptr, nullptr,
-                     nullptr, as_stream(stream), nullptr, 0, nullptr, 0, mask);
+  return conv_common({.input = input, .packed_weight = packed_weight, .bias = bias, .out = out,
+                      .N = N, .Cin = Cin, .Hs = Hs, .Ws = Ws, .Cout = Cout, .ksize = ksize,
+                      .pad_mode = pad_mode, .in_op = RPST_IN_NONE, .relu = RPST_ACT_NONE,
+                      .st = as_stream(stream), .mask = mask},
+                     conv_mode());
 }
 
 extern "C" int rpst_conv2d_pool(const float* input, const float* aux, const float* packed_weight,
@@ -1105,23 +1046,40 @@ extern "C" int rpst_conv2d_pool(const float* input, const float* aux, const floa
                                 int Cout, int ksize, int pad_mode, int in_op, int relu,
                                 rpst_stream_t stream) {
   RPST_REQUIRE(in_op != RPST_IN_ADD_ADAIN, "conv2d_pool: ADD_ADAIN has no pooled form");
-  return conv_common(input, aux, nullptr, packed_weight, bias, nullptr, out, N, Cin, Hs, Ws,
-                     Cout, ksize, pad_mode, in_op, relu, nullptr, nullptr, nullptr,
-                     as_stream(stream), nullptr, 0, nullptr, 0, nullptr, 1);
+  return conv_common({.input = input, .aux = aux, .packed_weight = packed_weight, .bias = bias,
+                      .out = out, .N = N, .Cin = Cin, .Hs = Hs, .Ws = Ws, .Cout = Cout,
+                      .ksize = ksize, .pad_mode = pad_mode, .in_op = in_op, .relu = relu,
+                      .st = as_stream(stream), .pool_out = 1},
+                     conv_mode());
 }
 
-// workspace of the F(4x4) conv with RPST_IN_ADAIN folded into per-image weights (0 for
-// every other layer)
-static size_t fold_bytes(int N, int Cin, int Hs, int Ws, int Cout, int ksize, int in_op) {
-  if (N <= 0 || Cin <= 0 || Hs < 2 || Ws < 2 || Cout <= 0 || ksize != 3 || in_op != RPST_IN_ADAIN)
-    return 0;
-  if (conv_algo(Cout, Cin, Hs, Ws, ksize, in_op) != RPST_CONV_WINOGRAD4) return 0;
-  return wino4_fold_floats(N, Cin, Cout) * sizeof(float);
+static bool bad_shape(int N, int Cin, int Hs, int Ws, int Cout, int ksize) {
+  return N <= 0 || Cin <= 0 || Hs <= 0 || Ws <= 0 || Cout <= 0 || (ksize != 1 && ksize != 3);
+}
+
+// does a launch that offers per-image weights (an RPST_IN_ADAIN loader with a workspace, or
+// rpst_conv2d_mix with in_op NONE) fold them under mode m
+static bool plan_folds(int N, int Cin, int Hs, int Ws, int Cout, int ksize, int in_op,
+                       const ConvMode& m) {
+  ConvArgs a = conv_shape(N, Cin, Hs, Ws, Cout, in_op);
+  return conv_plan(a, ksize, in_op, m, {false, false, true}).fold;
+}
+
+// workspace of the F(4x4) conv with RPST_IN_ADAIN folded into per-image weights (0 for every
+// other layer): the same under every precise level and quarter setting
+static size_t fold_bytes(int N, int Cin, int Hs, int Ws, int Cout, int ksize, int in_op,
+                         const ConvMode& mode) {
+  if (bad_shape(N, Cin, Hs, Ws, Cout, ksize) || in_op != RPST_IN_ADAIN) return 0;
+  return max_over_modes(mode, [&](const ConvMode& m) {
+    return plan_folds(N, Cin, Hs, Ws, Cout, ksize, in_op, m)
+               ? wino4_fold_floats(N, Cin, Cout) * sizeof(float)
+               : 0;
+  });
 }
 
 extern "C" size_t rpst_conv2d_workspace_size(int N, int Cin, int Hs, int Ws, int Cout, int ksize,
                                              int in_op) {
-  return fold_bytes(N, Cin, Hs, Ws, Cout, ksize, in_op);
+  return fold_bytes(N, Cin, Hs, Ws, Cout, ksize, in_op, conv_mode());
 }
 
 extern "C" int rpst_conv2d_ws(const float* input, const float* aux, const float* packed_weight,
@@ -1130,28 +1088,34 @@ extern "C" int rpst_conv2d_ws(const float* input, const float* aux, const float*
                               int in_op, int relu, void* workspace, size_t workspace_bytes,
                               rpst_stream_t stream) {
   RPST_REQUIRE(in_op != RPST_IN_ADD_ADAIN, "conv2d: ADD_ADAIN goes through rpst_conv2d_skip_adain");
-  const size_t need = fold_bytes(N, Cin, Hs, Ws, Cout, ksize, in_op);
+  const ConvMode m = conv_mode();
+  const size_t need = fold_bytes(N, Cin, Hs, Ws, Cout, ksize, in_op, m);
   if (need && (!workspace || workspace_bytes < need)) {
     set_error("conv2d: workspace %zu < %zu bytes", workspace_bytes, need);
     return RPST_EWORKSPACE;
   }
-  return conv_common(input, aux, nullptr, packed_weight, bias, residual, out, N, Cin, Hs, Ws,
-                     Cout, ksize, pad_mode, in_op, relu, nullptr, nullptr, nullptr,
-                     as_stream(stream), need ? static_cast<float*>(workspace) : nullptr);
+  return conv_common({.input = input, .aux = aux, .packed_weight = packed_weight, .bias = bias,
+                      .residual = residual, .out = out, .N = N, .Cin = Cin, .Hs = Hs, .Ws = Ws,
+                      .Cout = Cout, .ksize = ksize, .pad_mode = pad_mode, .in_op = in_op,
+                      .relu = relu, .st = as_stream(stream),
+                      .fold_ws = need ? static_cast<float*>(workspace) : nullptr},
+                     m);
 }
 
 // conv(pad(T_n x + c_n)): F(4x4) layers fold T_n / c_n into per-image weights and border
-// biases (wino4_mix); other layers materialise z = T x + c (fp32 MFMA GEMM) and convolve it
-static bool mix_folds(int Cin, int H, int W, int Cout, int ksize) {
-  return ksize == 3 && H >= 2 && W >= 2 &&
-         conv_algo(Cout, Cin, H, W, ksize, RPST_IN_NONE) == RPST_CONV_WINOGRAD4;
+// biases (wino4_mix); other layers materialise z = T x + c (fp32 MFMA GEMM) and convolve it.
+// The fold does not depend on the quarter setting, and neither does its size (wino4_mix_floats
+// takes the larger weight image); at precise level 1 the layer runs F(2x2) on z.
+static size_t mix_bytes(int N, int Cin, int H, int W, int Cout, int ksize, const ConvMode& m) {
+  if (bad_shape(N, Cin, H, W, Cout, ksize)) return 0;
+  if (plan_folds(N, Cin, H, W, Cout, ksize, RPST_IN_NONE, m))
+    return (wino4_mix_floats(N, Cin, Cout) + 64) * sizeof(float);
+  return ((size_t)N * Cin * H * W + wct_apply_scratch_floats(N, Cin) + 64) * sizeof(float);
 }
 
 extern "C" size_t rpst_conv2d_mix_workspace_size(int N, int Cin, int H, int W, int Cout,
                                                  int ksize) {
-  if (N <= 0 || Cin <= 0 || H <= 0 || W <= 0 || Cout <= 0 || (ksize != 1 && ksize != 3)) return 0;
-  if (mix_folds(Cin, H, W, Cout, ksize)) return (wino4_mix_floats(N, Cin, Cout) + 64) * sizeof(float);
-  return ((size_t)N * Cin * H * W + wct_apply_scratch_floats(N, Cin) + 64) * sizeof(float);
+  return mix_bytes(N, Cin, H, W, Cout, ksize, conv_mode());
 }
 
 extern "C" int rpst_conv2d_mix(const float* input, const double* T, const double* offset,
@@ -1161,41 +1125,26 @@ extern "C" int rpst_conv2d_mix(const float* input, const double* T, const double
                                rpst_stream_t stream) {
   RPST_REQUIRE(input && T && offset && packed_weight && out, "conv2d_mix: null pointer");
   RPST_REQUIRE(N > 0 && Cin > 0 && Cout > 0 && H > 0 && W > 0, "conv2d_mix: bad shape");
-  const size_t need = rpst_conv2d_mix_workspace_size(N, Cin, H, W, Cout, ksize);
+  const ConvMode m = conv_mode();
+  const size_t need = mix_bytes(N, Cin, H, W, Cout, ksize, m);
   if (!workspace || workspace_bytes < need) {
     set_error("conv2d_mix: workspace %zu < %zu bytes", workspace_bytes, need);
     return RPST_EWORKSPACE;
   }
-  hipStream_t st = as_stream(stream);
-  float* ws = static_cast<float*>(workspace);
-  if (!mix_folds(Cin, H, W, Cout, ksize)) {
-    float* z = ws;
+  ConvReq r{.input = input, .packed_weight = packed_weight, .bias = bias, .out = out, .N = N,
+            .Cin = Cin, .Hs = H, .Ws = W, .Cout = Cout, .ksize = ksize, .pad_mode = pad_mode,
+            .in_op = RPST_IN_NONE, .relu = relu, .st = as_stream(stream),
+            .fold_ws = static_cast<float*>(workspace), .T = T, .offset = offset};
+  if (!plan_folds(N, Cin, H, W, Cout, ksize, RPST_IN_NONE, m)) {
+    float* z = r.fold_ws;
     if (int e = wct_apply_f32(T, offset, input, z, N, Cin, (int64_t)H * W,
-                              z + (size_t)N * Cin * H * W, st))
+                              z + (size_t)N * Cin * H * W, r.st))
       return e;
-    return conv_common(z, nullptr, nullptr, packed_weight, bias, nullptr, out, N, Cin, H, W, Cout,
-                       ksize, pad_mode, RPST_IN_NONE, relu, nullptr, nullptr, nullptr, st);
+    r.input = z;
+    r.fold_ws = nullptr;
+    r.T = r.offset = nullptr;
   }
-  // the F(4x4) launch of conv_common with the folded weights: set up the arguments the way
-  // conv_common does for a NONE loader, then fold and launch
-  RPST_REQUIRE(pad_mode == RPST_PAD_ZERO || pad_mode == RPST_PAD_REFLECT, "conv2d_mix: bad pad");
-  RPST_REQUIRE(relu >= RPST_ACT_NONE && relu <= RPST_ACT_LRELU, "conv2d_mix: bad activation");
-  RPST_REQUIRE(((int64_t)Cin + 16) * H * W * 4 < (1LL << 31), "conv2d_mix: image too large");
-  ConvArgs a{};
-  a.in = input;
-  a.wpk = packed_weight + direct_packed_floats(Cout, Cin, ksize) + wino_packed_floats(Cout, Cin);
-  if (wino4q_applies(Cin, Cout, RPST_IN_NONE)) a.wpk += wino4_packed_floats(Cout, Cin);
-  a.bias = bias;
-  a.out = out;
-  a.N = N;
-  a.Cin = Cin;
-  a.Hs = a.H = H;
-  a.Ws = a.W = W;
-  a.Cout = Cout;
-  a.pad = pad_mode;
-  a.relu = relu;
-  if (int e = wino4_mix(a, T, offset, packed_weight, pad_cout(Cout), ws, st)) return e;
-  return wino4_launch(a, RPST_IN_NONE, st);
+  return conv_common(r, m);
 }
 
 extern "C" int rpst_conv2d_skip_adain(const float* stylized, const float* content,
@@ -1204,87 +1153,76 @@ extern "C" int rpst_conv2d_skip_adain(const float* stylized, const float* conten
                                       int Cout, int ksize, int pad_mode, int relu,
                                       rpst_stream_t stream) {
   RPST_REQUIRE(ksize == 3, "conv2d_skip_adain: 3x3 convs only");
-  return conv_common(stylized, params, content, packed_weight, bias, nullptr, out, N, Cin, H, W,
-                     Cout, ksize, pad_mode, RPST_IN_ADD_ADAIN, relu, nullptr, nullptr, nullptr,
-                     as_stream(stream));
+  return conv_common({.input = stylized, .aux = params, .aux2 = content,
+                      .packed_weight = packed_weight, .bias = bias, .out = out, .N = N,
+                      .Cin = Cin, .Hs = H, .Ws = W, .Cout = Cout, .ksize = ksize,
+                      .pad_mode = pad_mode, .in_op = RPST_IN_ADD_ADAIN, .relu = relu,
+                      .st = as_stream(stream)},
+                     conv_mode());
 }
 
+// bytes of the statistics partials of the fused epilogue: the largest over the modes, since
+// the partial count depends on the kernel that runs
+static size_t stat_bytes(int N, int Cin, int Hs, int Ws, int Cout, int ksize, int in_op,
+                         const ConvMode& mode) {
+  if (bad_shape(N, Cin, Hs, Ws, Cout, ksize)) return 0;
+  return max_over_modes(mode, [&](const ConvMode& m) {
+    ConvArgs a = conv_shape(N, Cin, Hs, Ws, Cout, in_op);
+    conv_plan(a, ksize, in_op, m, {true, false, false});
+    return ((size_t)N * Cout * a.stat_P * sizeof(float2) + 255) / 256 * 256;
+  });
+}
+
+// The partials, then the bytes of rpst_conv2d_workspace_size (kept in the size the ABI has
+// always returned; a statistics launch keeps AdaIN in the loader and does not use them).
 extern "C" size_t rpst_conv2d_stats_workspace_size(int N, int Cin, int Hs, int Ws, int Cout,
                                                    int ksize, int in_op) {
-  if (N <= 0 || Cin <= 0 || Hs <= 0 || Ws <= 0 || Cout <= 0 || (ksize != 1 && ksize != 3)) return 0;
-  // the partial count depends on the kernel the thread's precise / quarter settings select:
-  // sized for the largest of them, so a workspace sized under one setting serves a launch
-  // under any other
-  int stat_P = 0;
-  {
-    const int sp = t_conv_precise, sq = t_conv_quarter;
-    for (int p = 0; p < 3; ++p)
-      for (int q = -1; q < 3; ++q) {
-        t_conv_precise = p;
-        t_conv_quarter = q;
-        const ConvGeom g = conv_geom(N, Cin, Hs, Ws, Cout, ksize, in_op, true);
-        stat_P = g.stat_P > stat_P ? g.stat_P : stat_P;
-      }
-    t_conv_precise = sp;
-    t_conv_quarter = sq;
-  }
-  const size_t stats = ((size_t)N * Cout * stat_P * sizeof(float2) + 255) / 256 * 256;
-  return stats + fold_bytes(N, Cin, Hs, Ws, Cout, ksize, in_op);
+  const ConvMode m = conv_mode();
+  return stat_bytes(N, Cin, Hs, Ws, Cout, ksize, in_op, m) +
+         fold_bytes(N, Cin, Hs, Ws, Cout, ksize, in_op, m);
 }
 
-static int conv2d_stats_impl(const float* input, const float* aux, const float* packed_weight,
-                             const float* bias, const float* residual, float* out, int N,
-                             int Cin, int Hs, int Ws, int Cout, int ksize, int pad_mode,
-                             int in_op, int relu, float* mean, float* std_out, float eps,
-                             void* workspace, size_t workspace_bytes, int store_n,
-                             rpst_stream_t stream) {
+static int conv2d_stats_impl(ConvReq r, float* mean, float* std_out, float eps, void* workspace,
+                             size_t workspace_bytes, int store_n) {
   RPST_REQUIRE(mean && std_out, "conv2d_stats: null statistics pointer");
-  RPST_REQUIRE(store_n >= 1 && store_n <= N, "conv2d_stats: store_n=%d outside [1, N=%d]",
-               store_n, N);
-  const size_t need = rpst_conv2d_stats_workspace_size(N, Cin, Hs, Ws, Cout, ksize, in_op);
+  RPST_REQUIRE(store_n >= 1 && store_n <= r.N, "conv2d_stats: store_n=%d outside [1, N=%d]",
+               store_n, r.N);
+  const ConvMode m = conv_mode();
+  const size_t sb = stat_bytes(r.N, r.Cin, r.Hs, r.Ws, r.Cout, r.ksize, r.in_op, m);
+  const size_t need = sb + fold_bytes(r.N, r.Cin, r.Hs, r.Ws, r.Cout, r.ksize, r.in_op, m);
   if (!workspace || workspace_bytes < need) {
     set_error("conv2d_stats: workspace %zu < %zu bytes", workspace_bytes, need);
     return RPST_EWORKSPACE;
   }
-  hipStream_t st = as_stream(stream);
-  ConvArgs a{};
-  int P = 0;
-  const ConvGeom g = conv_geom(N, Cin, Hs, Ws, Cout, ksize, in_op, true);
-  const int planes = N * Cout;
-  if (g.algo == RPST_CONV_DIRECT && g.stat_nt < 4) {  // tile without the fused statistics epilogue
-    if (int e = conv_common(input, aux, nullptr, packed_weight, bias, residual, out, N, Cin, Hs,
-                            Ws, Cout, ksize, pad_mode, in_op, relu, nullptr, &P, &a, st))
-      return e;
-    return rpst_calc_mean_std(out, mean, std_out, N, Cout, (int64_t)a.H * a.W, eps, stream);
+  r.stat_part = static_cast<float2*>(workspace);
+  r.skip_from = store_n < r.N ? store_n : 0;
+  ConvArgs a;
+  ConvPlan p;
+  if (int e = conv_prepare(r, m, a, p)) return e;
+  // Tiles without the fused statistics epilogue (direct, < 4 rows per wave) convolve, then
+  // reduce the output. So does a layer whose residual moved it from Winograd to a direct tile
+  // with more partials than the workspace was sized for.
+  if ((p.algo == RPST_CONV_DIRECT && p.t.stat_nt < 4) ||
+      (size_t)r.N * r.Cout * a.stat_P * sizeof(float2) > sb) {
+    r.stat_part = nullptr;
+    r.skip_from = 0;
+    if (int e = conv_common(r, m)) return e;
+    return rpst_calc_mean_std(r.out, mean, std_out, r.N, r.Cout, (int64_t)a.H * a.W, eps,
+                              (rpst_stream_t)r.st);
   }
-  const size_t fb = fold_bytes(N, Cin, Hs, Ws, Cout, ksize, in_op);
-  float* fold_ws = fb ? reinterpret_cast<float*>(static_cast<char*>(workspace) + (need - fb))
-                      : nullptr;
-  if (int e = conv_common(input, aux, nullptr, packed_weight, bias, residual, out, N, Cin, Hs, Ws,
-                          Cout, ksize, pad_mode, in_op, relu, static_cast<float2*>(workspace), &P,
-                          &a, st, fold_ws, store_n < N ? store_n : 0))
-    return e;
-  if (g.stat_t) {
-    stat_merge_t_kernel<<<N * ((Cout + 63) / 64), 256, 0, st>>>(
-        static_cast<const float2*>(workspace), mean, std_out, Cout, P, a.tiles_x, g.stat_wn,
-        g.stat_nt, g.stat_tw, a.H, a.W, eps);
+  if (int e = conv_launch(r, a, p)) return e;
+  const float2* part = r.stat_part;
+  if (p.t.stat_t) {
+    stat_merge_t_kernel<<<r.N * ((r.Cout + 63) / 64), 256, 0, r.st>>>(
+        part, mean, std_out, r.Cout, a.stat_P, a.tiles_x, p.t.stat_wn, p.t.stat_nt, p.t.stat_tw,
+        a.H, a.W, eps);
     return launch_status("stat_merge_t_kernel");
   }
-  stat_merge_kernel<<<(planes + 3) / 4, 256, 0, st>>>(static_cast<const float2*>(workspace), mean,
-                                                      std_out, planes, P, a.tiles_x, g.stat_wn,
-                                                      g.stat_nt, g.stat_tw, a.H, a.W, eps);
+  const int planes = r.N * r.Cout;
+  stat_merge_kernel<<<(planes + 3) / 4, 256, 0, r.st>>>(part, mean, std_out, planes, a.stat_P,
+                                                        a.tiles_x, p.t.stat_wn, p.t.stat_nt,
+                                                        p.t.stat_tw, a.H, a.W, eps);
   return launch_status("stat_merge_kernel");
-}
-
-extern "C" int rpst_conv2d_stats(const float* input, const float* aux,
-                                 const float* packed_weight, const float* bias,
-                                 const float* residual, float* out, int N, int Cin, int Hs,
-                                 int Ws, int Cout, int ksize, int pad_mode, int in_op, int relu,
-                                 float* mean, float* std_out, float eps, void* workspace,
-                                 size_t workspace_bytes, rpst_stream_t stream) {
-  return conv2d_stats_impl(input, aux, packed_weight, bias, residual, out, N, Cin, Hs, Ws, Cout,
-                           ksize, pad_mode, in_op, relu, mean, std_out, eps, workspace,
-                           workspace_bytes, N, stream);
 }
 
 extern "C" int rpst_conv2d_stats_store(const float* input, const float* aux,
@@ -1294,9 +1232,23 @@ extern "C" int rpst_conv2d_stats_store(const float* input, const float* aux,
                                        int relu, float* mean, float* std_out, float eps,
                                        int store_n, void* workspace, size_t workspace_bytes,
                                        rpst_stream_t stream) {
-  return conv2d_stats_impl(input, aux, packed_weight, bias, residual, out, N, Cin, Hs, Ws, Cout,
-                           ksize, pad_mode, in_op, relu, mean, std_out, eps, workspace,
-                           workspace_bytes, store_n, stream);
+  return conv2d_stats_impl({.input = input, .aux = aux, .packed_weight = packed_weight,
+                            .bias = bias, .residual = residual, .out = out, .N = N, .Cin = Cin,
+                            .Hs = Hs, .Ws = Ws, .Cout = Cout, .ksize = ksize,
+                            .pad_mode = pad_mode, .in_op = in_op, .relu = relu,
+                            .st = as_stream(stream)},
+                           mean, std_out, eps, workspace, workspace_bytes, store_n);
+}
+
+extern "C" int rpst_conv2d_stats(const float* input, const float* aux,
+                                 const float* packed_weight, const float* bias,
+                                 const float* residual, float* out, int N, int Cin, int Hs,
+                                 int Ws, int Cout, int ksize, int pad_mode, int in_op, int relu,
+                                 float* mean, float* std_out, float eps, void* workspace,
+                                 size_t workspace_bytes, rpst_stream_t stream) {
+  return rpst_conv2d_stats_store(input, aux, packed_weight, bias, residual, out, N, Cin, Hs, Ws,
+                                 Cout, ksize, pad_mode, in_op, relu, mean, std_out, eps, N,
+                                 workspace, workspace_bytes, stream);
 }
 
 // ---- stand-alone max-pool / upsample (used where no conv follows directly) ----------

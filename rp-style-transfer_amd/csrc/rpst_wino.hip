@@ -91,15 +91,22 @@ static size_t wino_image_floats(int MT, int Cout, int Cin) {
 // loaders; the two- and four-load loaders keep one co tile per block (their extra
 // raw registers would spill across the co-tile loop).
 constexpr int kWMT = 1;
-int wino_bm() { return 32 * kWMT; }
-int wino_th() { return 4 * (2 / kWMT); }
-// spatial_blocks = tiles_x * tiles_y * N: a persistent grid of fewer than 512 blocks (two
-// per CU) leaves CUs idle (the 64x64 relu4_1 / relu5_1 layers of SAModel training at B = 8:
-// 128 blocks), so such layers take one co tile per block
-int wino_persist(int in_op, int64_t spatial_blocks) {
-  if (in_op == RPST_IN_MAXPOOL2 || in_op == RPST_IN_ADD_UPSAMPLE2 || in_op == RPST_IN_ADD_ADAIN)
-    return 0;
-  return spatial_blocks >= 512;
+// A persistent grid (one block per spatial tile looping over the co tiles) of fewer than 512
+// blocks (two per CU) leaves CUs idle (the 64x64 relu4_1 / relu5_1 layers of SAModel training
+// at B = 8: 128 blocks), so such layers take one co tile per block
+ConvTiling wino_tiling(ConvArgs& a, int in_op) {
+  constexpr int BM = 32 * kWMT, TH = 4 * (2 / kWMT);
+  a.Cout_pad = (a.Cout + BM - 1) / BM * BM;
+  a.nchunks = (a.Cin + kWCK - 1) / kWCK;
+  a.tiles_x = (a.W + kTW - 1) / kTW;
+  a.tiles_y = (a.H + TH - 1) / TH;
+  a.co_tiles = a.Cout_pad / BM;
+  a.stat_P = a.tiles_x * a.tiles_y;
+  const int64_t spatial = (int64_t)a.tiles_x * a.tiles_y * a.N;
+  const bool heavy = in_op == RPST_IN_MAXPOOL2 || in_op == RPST_IN_ADD_UPSAMPLE2 ||
+                     in_op == RPST_IN_ADD_ADAIN;
+  a.persist = !heavy && spatial >= 512;
+  return {spatial * (a.persist ? 1 : a.co_tiles), kWinoNTH, TH, 1, kTW, false};
 }
 
 size_t wino_packed_floats(int Cout, int Cin) { return wino_image_floats(kWMT, Cout, Cin); }
@@ -471,17 +478,10 @@ __global__ __launch_bounds__(kWinoNTH, 2) void wino_mfma_kernel(ConvArgs a) {
 }
 
 int wino_launch(ConvArgs& a, int in_op, hipStream_t st) {
-  constexpr int MT = kWMT, BM = 32 * MT, TH = 4 * (2 / MT);
-  a.Cout_pad = (a.Cout + BM - 1) / BM * BM;
-  a.nchunks = (a.Cin + kWCK - 1) / kWCK;
-  a.tiles_x = (a.W + kTW - 1) / kTW;
-  a.tiles_y = (a.H + TH - 1) / TH;
-  a.co_tiles = a.Cout_pad / BM;
-  a.stat_P = a.tiles_x * a.tiles_y;
-  a.persist = wino_persist(in_op, (int64_t)a.tiles_x * a.tiles_y * a.N);
-  const int64_t blocks = (int64_t)a.tiles_x * a.tiles_y * a.N * (a.persist ? 1 : a.co_tiles);
-  RPST_REQUIRE(blocks <= 0x7fffffffLL, "conv2d: grid too large");
-  const unsigned nb = (unsigned)blocks;
+  constexpr int MT = kWMT;
+  const ConvTiling t = wino_tiling(a, in_op);
+  RPST_REQUIRE(t.blocks <= 0x7fffffffLL, "conv2d: grid too large");
+  const unsigned nb = (unsigned)t.blocks;
 #define RPST_WINO_GO(OP)                                                                  \
   (a.persist ? (void)(wino_mfma_kernel<OP, MT, true><<<nb, kWinoNTH, 0, st>>>(a))          \
              : (void)(wino_mfma_kernel<OP, MT, false><<<nb, kWinoNTH, 0, st>>>(a)))

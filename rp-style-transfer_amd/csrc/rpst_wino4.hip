@@ -182,7 +182,6 @@ bool wino4_fits(int N, int Cin, int Hs, int Ws, int in_op) {
   const int64_t plane = (int64_t)Hs * Ws * 4;
   return (int64_t)(3 * Cin + 8) * plane < (1LL << 32) - (1LL << 20);
 }
-int wino4_persist() { return 1; }  // one block per spatial tile loops over the co tiles
 // tile rows per block (W4Geo): 2 for the layers with Cin * Cout <= 512 (the RP stacks' 16->32
 // and 32->16), 4 otherwise -- a function of the layer's shape only, so an
 // image's bits never depend on its batch. tools/ab_env.sh (bench_conv, ms, NR = 4 / NR = 2,
@@ -194,10 +193,27 @@ int wino4_persist() { return 1; }  // one block per spatial tile loops over the 
 // by exposed prologues. Only the two smallest layers switch. Round 5 (A operands read 2
 // groups ahead at NR = 4): 64->32 N32 1.10 -> 1.06 ms at NR = 2 (32->64 2.50 either way), so
 // layers with <= 32 output channels switch up to Cin * Cout = 2048 (profiles/r05/half_ab.log).
-int wino4_rows(int Cin, int Cout, int in_op) {
-  if (wino4q_applies(Cin, Cout, in_op)) return 2;  // rpst_wino4q.hip: 8 output rows
+static int w4_rows(int Cin, int Cout) {
   const int64_t cc = (int64_t)Cin * Cout;
   return cc <= 512 || (Cout <= 32 && cc <= 2048) ? 2 : 4;
+}
+
+// statistics partials are per tile row of 4 rows x 64 columns
+ConvTiling wino4_tiling(ConvArgs& a) {
+  const int nr = w4_rows(a.Cin, a.Cout);
+  a.Cout_pad = (a.Cout + kW4BM - 1) / kW4BM * kW4BM;
+  a.nchunks = (a.Cin + kW4CK - 1) / kW4CK;
+  a.tiles_x = (a.W + kW4TW - 1) / kW4TW;
+  a.tiles_y = (a.H + 4 * nr - 1) / (4 * nr);
+  a.co_tiles = a.Cout_pad / kW4BM;
+  a.stat_P = a.tiles_x * a.tiles_y * nr;
+  a.persist = 1;  // a block loops over the co tiles of its share
+  // blocks per spatial tile: 2 once a co tile has >= 32 K steps (Cin >= 128) and there
+  // are >= 4 co tiles (the shorter blocks' prologue then costs less than the L2 reuse of
+  // the shared patch gains; 1 / 2 / 4 re-measured in profiles/r05/order_ab.log)
+  a.cosplit = 2 * a.nchunks >= 32 && a.co_tiles >= 4 ? 2 : 1;
+  while (a.co_tiles % a.cosplit) --a.cosplit;
+  return {(int64_t)a.tiles_x * a.tiles_y * a.N * a.cosplit, 128 * nr, 4, nr, kW4TW, false};
 }
 
 // what the F(4x4) epilogue needs besides the tile (wino4_mfma_kernel's epi_ctx)
@@ -963,13 +979,11 @@ static double* align8(void* p) {
   return reinterpret_cast<double*>((reinterpret_cast<uintptr_t>(p) + 7) & ~uintptr_t(7));
 }
 
-int wino4_fold(ConvArgs& a, const float* direct_packed, int direct_cout_pad, float* ws,
+int wino4_fold(ConvArgs& a, bool q, const float* direct_packed, int direct_cout_pad, float* ws,
                hipStream_t st) {
   RPST_REQUIRE(a.H >= 2 && a.W >= 2, "conv2d: folded AdaIN needs H, W >= 2");
   const int nch = (a.Cin + kW4CK - 1) / kW4CK;
-  // a.wpk is the image of the launched (NONE) form: the quarter layout where it applies
-  const bool q = wino4q_applies(a.Cin, a.Cout, RPST_IN_NONE);
-  const int64_t per = (int64_t)wino4_image_floats(a.Cout, a.Cin, RPST_IN_NONE);
+  const int64_t per = (int64_t)wino4_image_floats(a.Cout, a.Cin, q);
   const int64_t n4 = (int64_t)a.N * (per / 4);
   float* wf = ws;
   float* bt = ws + (int64_t)a.N * per;
@@ -1016,12 +1030,11 @@ __global__ void mix_wt_kernel(const float* __restrict__ dpk, float* __restrict__
   wt[t] = dpk[((int64_t)(m >> 3) * 9 + tap) * 8 * cout_pad + (m & 7) * cout_pad + co];
 }
 
-int wino4_mix(ConvArgs& a, const double* T, const double* cvec, const float* direct_packed,
-              int direct_cout_pad, float* ws, hipStream_t st) {
+int wino4_mix(ConvArgs& a, bool q, const double* T, const double* cvec,
+              const float* direct_packed, int direct_cout_pad, float* ws, hipStream_t st) {
   RPST_REQUIRE(a.H >= 2 && a.W >= 2, "conv2d_mix: needs H, W >= 2");
   const int nch = (a.Cin + kW4CK - 1) / kW4CK;
-  const bool q = wino4q_applies(a.Cin, a.Cout, RPST_IN_NONE);
-  const int64_t per = (int64_t)wino4_image_floats(a.Cout, a.Cin, RPST_IN_NONE);
+  const int64_t per = (int64_t)wino4_image_floats(a.Cout, a.Cin, q);
   float* wf = ws;
   float* bt = ws + (int64_t)a.N * per;
   double* S = align8(bt + (int64_t)a.N * a.Cout * 9);
@@ -1054,25 +1067,12 @@ int wino4_launch(ConvArgs& a, int in_op, hipStream_t st) {
   RPST_REQUIRE(wino4_supports(in_op), "conv2d: winograd4 does not support in_op %d", in_op);
   RPST_REQUIRE(a.res == nullptr, "conv2d: winograd4 has no residual epilogue");
   RPST_REQUIRE(wino4_fits(a.N, a.Cin, a.Hs, a.Ws, in_op), "conv2d: image too large for winograd4");
-  if (wino4q_applies(a.Cin, a.Cout, in_op)) return wino4q_launch(a, in_op, st);
-  a.Cout_pad = (a.Cout + kW4BM - 1) / kW4BM * kW4BM;
-  a.nchunks = (a.Cin + kW4CK - 1) / kW4CK;
-  a.tiles_x = (a.W + kW4TW - 1) / kW4TW;
-  const int nr = wino4_rows(a.Cin, a.Cout, in_op);
-  a.tiles_y = (a.H + 4 * nr - 1) / (4 * nr);
-  a.co_tiles = a.Cout_pad / kW4BM;
-  a.stat_P = a.tiles_x * a.tiles_y * nr;
-  a.persist = 1;
+  const ConvTiling t = wino4_tiling(a);
+  const int nr = t.stat_wn;  // tile rows per block
   RPST_REQUIRE((int64_t)a.co_tiles * a.nchunks * kW4WCH * 4 < (1LL << 31),
                "conv2d: winograd4 weight image exceeds 2 GiB");
-  // blocks per spatial tile: 2 once a co tile has >= 32 K steps (Cin >= 128) and there
-  // are >= 4 co tiles (the shorter blocks' prologue then costs less than the L2 reuse of
-  // the shared patch gains; 1 / 2 / 4 re-measured in profiles/r05/order_ab.log)
-  a.cosplit = 2 * a.nchunks >= 32 && a.co_tiles >= 4 ? 2 : 1;
-  while (a.co_tiles % a.cosplit) --a.cosplit;
-  const int64_t blocks = (int64_t)a.tiles_x * a.tiles_y * a.N * a.cosplit;
-  RPST_REQUIRE(blocks <= 0x7fffffffLL, "conv2d: grid too large");
-  const unsigned nb = (unsigned)blocks;
+  RPST_REQUIRE(t.blocks <= 0x7fffffffLL, "conv2d: grid too large");
+  const unsigned nb = (unsigned)t.blocks;
   const bool stats = a.stat_part != nullptr, btab = a.btab != nullptr;
   RPST_REQUIRE(!btab || in_op == RPST_IN_NONE, "conv2d: winograd4 bias table with a loader op");
   // RELU: the activation as one v_med3 per element (the RP stacks and VGG: every large

@@ -226,18 +226,32 @@ int wino4q_fold_w(const float* pk, float* out, const float* aux, int N, int Cout
 // input channels in multiples of 16 (a co tile = a whole number of 4-step ring turns).
 // Below 128 input channels a block's 8-16 K steps per co tile leave the prologue and the
 // 4-way epilogue exposed: 32->64 @512^2 N64 3.12 vs 2.54 ms, 64->128 8.16 vs 8.09 on the
-// 32-channel kernel (gpurun_out/w4q_d, profiles/r05). Mode (conv_quarter_mode: the calling
+// 32-channel kernel (profiles/r05). ConvMode::quarter (the calling
 // thread's rpst_conv2d_set_quarter, else RPST_W4Q read per launch like RPST_CONV_ALGO): 0
 // off, 1 the rule above, 2 forced on for every shape it supports (Cin >= 16; parity tests,
 // A/B). A training step's constant branches (rpst_conv2d_set_precise(2)) keep the 32-channel
 // form: same per-conv error (tools/conv_err.py), but the gradient goldens were pinned on its
 // rounding pattern.
-bool wino4q_applies(int Cin, int Cout, int in_op) {
-  const int en = conv_quarter_mode();
-  const int min_cin = en == 2 ? 16 : 128;
-  return en && conv_quarter_allowed() && (in_op == RPST_IN_NONE || in_op == RPST_IN_UPSAMPLE2) &&
+bool wino4q_applies(int Cin, int Cout, int in_op, const ConvMode& m) {
+  const int min_cin = m.quarter == 2 ? 16 : 128;
+  return m.quarter && m.precise != 2 && (in_op == RPST_IN_NONE || in_op == RPST_IN_UPSAMPLE2) &&
          Cout >= 64 && Cout <= kQMaxCo &&
          Cin >= min_cin && Cin % 16 == 0;
+}
+
+// statistics partials per tile row of 4 rows x 64 columns, in [n][partial][co] order
+ConvTiling wino4q_tiling(ConvArgs& a) {
+  a.Cout_pad = (a.Cout + kQCo - 1) / kQCo * kQCo;
+  a.nchunks = (a.Cin + 3) / 4;  // K steps of 4 channels
+  a.tiles_x = (a.W + kQTW - 1) / kQTW;
+  a.tiles_y = (a.H + kQTH - 1) / kQTH;
+  a.co_tiles = a.Cout_pad / kQCo;
+  a.stat_P = a.tiles_x * a.tiles_y * 2;
+  // one block per spatial tile loops over every co tile: splitting them over 2 / 4 same-XCD
+  // blocks measured 27.70 / 29.04 ms against 27.08 at 128->256 @512^2 N64 (the longer blocks
+  // amortise the ring's prologue; profiles/r05/order_ab.log has the re-run under the final order)
+  a.cosplit = 1;
+  return {(int64_t)a.tiles_x * a.tiles_y * a.N, kQNTH, 4, kQTH / 4, kQTW, true};
 }
 
 // ---- the epilogue of one finished 4x4 tile and channel ---------------------------------
@@ -865,21 +879,11 @@ __global__ __launch_bounds__(kQNTH, 1) void wino4q_mfma_kernel(ConvArgs a) {
 int wino4q_launch(ConvArgs& a, int in_op, hipStream_t st) {
   RPST_REQUIRE(in_op == RPST_IN_NONE || in_op == RPST_IN_UPSAMPLE2,
                "conv2d: winograd4 (quarter) does not support in_op %d", in_op);
-  a.Cout_pad = (a.Cout + kQCo - 1) / kQCo * kQCo;
-  a.nchunks = (a.Cin + 3) / 4;  // K steps of 4 channels
-  a.tiles_x = (a.W + kQTW - 1) / kQTW;
-  a.tiles_y = (a.H + kQTH - 1) / kQTH;
-  a.co_tiles = a.Cout_pad / kQCo;
-  a.stat_P = a.tiles_x * a.tiles_y * 2;
+  const ConvTiling t = wino4q_tiling(a);
   RPST_REQUIRE((int64_t)a.co_tiles * a.nchunks * kQWS * 4 < (1LL << 31),
                "conv2d: winograd4 weight image exceeds 2 GiB");
-  // one block per spatial tile loops over every co tile: splitting them over 2 / 4 same-XCD
-  // blocks measured 27.70 / 29.04 ms against 27.08 at 128->256 @512^2 N64 (the longer blocks
-  // amortise the ring's prologue; profiles/r05/order_ab.log has the re-run under the final order)
-  a.cosplit = 1;
-  const int64_t blocks = (int64_t)a.tiles_x * a.tiles_y * a.N;
-  RPST_REQUIRE(blocks <= 0x7fffffffLL, "conv2d: grid too large");
-  const unsigned nb = (unsigned)blocks;
+  RPST_REQUIRE(t.blocks <= 0x7fffffffLL, "conv2d: grid too large");
+  const unsigned nb = (unsigned)t.blocks;
   const bool stats = a.stat_part != nullptr, btab = a.btab != nullptr;
   RPST_REQUIRE(!btab || in_op == RPST_IN_NONE, "conv2d: winograd4 bias table with a loader op");
   RPST_REQUIRE(!(stats && btab), "conv2d: winograd4 folded bias with statistics");

@@ -167,7 +167,8 @@ def test_quarter_kernel_switch_is_per_launch(monkeypatch):
     """rpst_conv2d_quarter / rpst_conv2d_set_quarter: the position-quarter F(4x4) kernel takes
     the Cin >= 128 layers by default; RPST_W4Q is read per launch (0 off, 2 forced on every
     shape it supports) and the thread-local setter overrides it; precise level 2 keeps the
-    32-channel form. Workspace sizes do not depend on the setting."""
+    32-channel form. Workspace sizes do not depend on the setting; the stats and fold sizes do
+    not depend on the precise level either (the mix size does: at level 1 it holds T x + c)."""
     monkeypatch.delenv("RPST_CONV_ALGO", raising=False)
     monkeypatch.delenv("RPST_W4Q", raising=False)
     lib = _lib.load()
@@ -179,18 +180,33 @@ def test_quarter_kernel_switch_is_per_launch(monkeypatch):
     assert q(64, 128, 23, 70, 3, 2) == 1             # upsample loader
     assert q(200, 144, 19, 90, 3, 0) == 1            # Cin % 16 == 0, partial co tile
     assert q(256, 136, 64, 64, 3, 0) == 0            # Cin % 16 != 0
-    sizes = (lib.rpst_conv2d_stats_workspace_size(2, 128, 37, 200, 256, 3, 0),
-             lib.rpst_conv2d_workspace_size(2, 256, 37, 70, 96, 3, 4),
-             lib.rpst_conv2d_mix_workspace_size(2, 128, 37, 70, 96, 3))
+    def sample():
+        return (lib.rpst_conv2d_stats_workspace_size(2, 128, 37, 200, 256, 3, 0),
+                lib.rpst_conv2d_workspace_size(2, 256, 37, 70, 96, 3, 4),
+                lib.rpst_conv2d_mix_workspace_size(2, 128, 37, 70, 96, 3))
+
+    def sample_levels():
+        out = []
+        for level in (0, 1, 2):
+            p = lib.rpst_conv2d_set_precise(level)
+            try:
+                out.append(sample())
+            finally:
+                lib.rpst_conv2d_set_precise(p)
+        return out
+
+    sizes = sample()
+    levels = sample_levels()
+    assert levels[0] == sizes
+    assert levels[0][:2] == levels[1][:2] == levels[2][:2] and levels[0][1] > 0
     monkeypatch.setenv("RPST_W4Q", "0")
     assert q(256, 128, 512, 512, 3, 0) == 0
     monkeypatch.setenv("RPST_W4Q", "2")
     assert q(128, 64, 512, 512, 3, 0) == 1
     assert q(64, 16, 512, 512, 3, 0) == 1
     assert q(32, 64, 512, 512, 3, 0) == 0            # Cout < 64 even when forced
-    assert (lib.rpst_conv2d_stats_workspace_size(2, 128, 37, 200, 256, 3, 0),
-            lib.rpst_conv2d_workspace_size(2, 256, 37, 70, 96, 3, 4),
-            lib.rpst_conv2d_mix_workspace_size(2, 128, 37, 70, 96, 3)) == sizes
+    assert sample() == sizes
+    assert sample_levels() == levels                 # per level, equal across quarter settings
     old = lib.rpst_conv2d_set_quarter(0)
     try:
         assert old == -1
@@ -206,6 +222,31 @@ def test_quarter_kernel_switch_is_per_launch(monkeypatch):
         lib.rpst_conv2d_set_quarter(old)
     monkeypatch.delenv("RPST_W4Q")
     assert q(128, 64, 512, 512, 3, 0) == 0
+
+
+def test_grid_threads_reports_the_launched_grid(monkeypatch):
+    """rpst_conv2d_grid_threads reads the plan the launch reads, the F(4x4) co-split included:
+    128 -> 128 at 64x64 has 16 chunks of 8 channels (>= 32 K steps of 4) and 4 co tiles of 32,
+    so the 32-channel form splits them over 2 blocks per spatial tile."""
+    for k in ("RPST_CONV_ALGO", "RPST_W4Q", "RPST_CONV_NARROW"):
+        monkeypatch.delenv(k, raising=False)
+    lib = _lib.load()
+    shape = (1, 128, 64, 64, 128, 3, 0)
+    old = lib.rpst_conv2d_set_quarter(0)
+    try:
+        # one 64-column tile x four 16-row tiles x co-split 2, 512 threads
+        assert lib.rpst_conv2d_grid_threads(*shape) == 1 * 4 * 2 * 512
+    finally:
+        lib.rpst_conv2d_set_quarter(old)
+    assert lib.rpst_conv2d_quarter(128, 128, 64, 64, 3, 0) == 1
+    # the quarter form: one column tile x eight 8-row tiles, 512 threads, no co-split
+    assert lib.rpst_conv2d_grid_threads(*shape) == 1 * 8 * 512
+    old = lib.rpst_conv2d_set_quarter(0)
+    try:
+        # three co tiles (Cout = 96) do not split
+        assert lib.rpst_conv2d_grid_threads(1, 128, 64, 64, 96, 3, 0) == 4 * 512
+    finally:
+        lib.rpst_conv2d_set_quarter(old)
 
 
 def test_plan_rejects_unfused_first_transform():

@@ -582,6 +582,67 @@ def test_conv2d_adain_input_op(cuda, conv_algo, fold, pad, shape, cin, cout):
     assert rel_l2(out, ref) < 1e-5
 
 
+@pytest.mark.parametrize("pad", [0, 1])
+@pytest.mark.parametrize("shape,cin,cout", [((2, 24, 40), 32, 16), ((1, 23, 134), 128, 96)])
+def test_conv2d_workspace_sized_at_another_precise_level(cuda, monkeypatch, pad, shape, cin, cout):
+    """A workspace sized while the thread is at precise level 1 serves an IN_ADAIN launch at
+    level 0 (both F(4x4) forms, the AdaIN fold, ragged tiles and a partial co tile): status 0
+    and the bits of the plainly sized call, for rpst_conv2d_ws and for rpst_conv2d_stats."""
+    from rpst import _lib, ops
+    for k in ("RPST_CONV_ALGO", "RPST_W4Q"):
+        monkeypatch.delenv(k, raising=False)
+    lib = _lib.load()
+    n, h, w = shape
+    c = gen(60, (n, cin, h, w), 2.0, 0.5).clamp_min(0)
+    s = gen(61, (n, cin, h, w), 1.0, 1.0).clamp_min(0)
+    mc, sc = R.calc_mean_std(c)
+    ms, ss = R.calc_mean_std(s)
+    aux = ops.adain_params(mc, sc, ms, ss).to(cuda)
+    x = c.to(cuda)
+    p = ops.pack_conv_weight(gen(62, (cout, cin, 3, 3), 0.08).to(cuda))
+    b = gen(63, (cout,), 0.05).to(cuda)
+    old = lib.rpst_conv2d_set_precise(0)
+    try:
+        _ws_at_other_level(lib, ops, cuda, x, aux, p, b, pad, (n, cin, h, w, cout))
+    finally:
+        lib.rpst_conv2d_set_precise(old)
+
+
+def _ws_at_other_level(lib, ops, cuda, x, aux, p, b, pad, dims):
+    n, cin, h, w, cout = dims
+    assert lib.rpst_conv2d_algorithm(cout, cin, h, w, 3, ops.IN_ADAIN) == 2   # F(4x4)
+    ref = ops.conv2d(x, p, b, cout, 3, pad=pad, in_op=ops.IN_ADAIN, aux=aux, relu=True, fold=True)
+
+    def sized_at_1(query):
+        lib.rpst_conv2d_set_precise(1)
+        try:
+            nbytes = query(n, cin, h, w, cout, 3, ops.IN_ADAIN)
+        finally:
+            lib.rpst_conv2d_set_precise(0)
+        assert nbytes > 0
+        return torch.empty(nbytes, device=cuda, dtype=torch.uint8), nbytes
+
+    ws, nbytes = sized_at_1(lib.rpst_conv2d_workspace_size)
+    out = torch.empty_like(ref)
+    stream = torch.cuda.current_stream(cuda).cuda_stream
+    st = lib.rpst_conv2d_ws(x.data_ptr(), aux.data_ptr(), p.data_ptr(), b.data_ptr(), None,
+                            out.data_ptr(), n, cin, h, w, cout, 3, pad, ops.IN_ADAIN, 1,
+                            ws.data_ptr(), nbytes, stream)
+    assert st == 0, lib.rpst_last_error()
+    assert torch.equal(out, ref)
+    if cin != 32:
+        return
+    ref_o, ref_m, ref_s = ops.conv2d_stats(x, p, b, cout, 3, pad=pad, in_op=ops.IN_ADAIN, aux=aux,
+                                           relu=True)
+    ws, nbytes = sized_at_1(lib.rpst_conv2d_stats_workspace_size)
+    out, mean, std = torch.empty_like(ref_o), torch.empty_like(ref_m), torch.empty_like(ref_s)
+    st = lib.rpst_conv2d_stats(x.data_ptr(), aux.data_ptr(), p.data_ptr(), b.data_ptr(), None,
+                               out.data_ptr(), n, cin, h, w, cout, 3, pad, ops.IN_ADAIN, 1,
+                               mean.data_ptr(), std.data_ptr(), 1e-5, ws.data_ptr(), nbytes, stream)
+    assert st == 0, lib.rpst_last_error()
+    assert torch.equal(out, ref_o) and torch.equal(mean, ref_m) and torch.equal(std, ref_s)
+
+
 def test_adain_rp_fused_equals_unfused(cuda):
     import network as net
     import network.adain_rp as arp

@@ -1,9 +1,9 @@
-"""Conv tile-variant / algorithm micro-benchmark (interleaved rounds in one process).
+"""Conv algorithm micro-benchmark (interleaved rounds in one process).
 
-For each conv layer shape of the benchmark workloads, times every tile variant of the
-direct rpst_conv2d (RPST_CONV_VARIANT) and the Winograd path (RPST_CONV_ALGO) with HIP
-events on the launch stream, checks that all produce the same output within 1e-5 rel-L2,
-and prints effective TF/s (direct-convolution FLOPs / time).
+For each conv layer shape of the benchmark workloads, times the direct rpst_conv2d and the
+two Winograd paths (RPST_CONV_ALGO) with HIP events on the launch stream, checks that all
+produce the same output within 1e-5 rel-L2, and prints effective TF/s (direct-convolution
+FLOPs / time).
 
     python tools/bench_conv.py [--layers adain|vgg|all] [--rounds 3]
 """
@@ -36,11 +36,7 @@ VGG = [
     (64, 512, 64, 64, 512, 3, 1, 0), (32, 512, 64, 64, 512, 1, 0, 0),
     (32, 64, 512, 512, 3, 3, 1, 0),  # the VGG decoders' last conv (SAModel, SourceNet)
 ]
-VARIANTS = {128: [0, 1, 2, 3, 4], 64: [0, 1, 2], 32: [0, 1, 2]}
-
-
-def bm_of(cout):
-    return 128 if cout > 64 else (64 if cout > 32 else 32)
+ALGOS = {"direct": "direct", "wino": "winograd", "wino4": "winograd4"}
 
 
 def main():
@@ -51,8 +47,6 @@ def main():
     ap.add_argument("--only", default=None, help="substring filter on 'cin->cout'")
     ap.add_argument("--algo", default=None, choices=["direct", "winograd", "winograd4"],
                     help="time one algorithm only (profiling)")
-    ap.add_argument("--default-only", action="store_true",
-                    help="direct default variant vs Winograd only")
     args = ap.parse_args()
     layers = {"adain": ADAIN, "vgg": VGG, "fused": FUSED, "all": ADAIN + FUSED + VGG}[args.layers]
     dev = torch.device("cuda:0")
@@ -71,23 +65,12 @@ def main():
                              torch.rand(2 * n * cin, device=dev, generator=g) + 0.5])
         h, wd = ops.conv_out_hw(hs, ws, in_op)
         flops = 2.0 * n * cout * h * wd * cin * k * k
-        variants = [None] if args.default_only else VARIANTS[bm_of(cout)]
-        times = {("d", v): [] for v in variants}
-        if k == 3:
-            times[("w", None)] = []
-            times[("w4", None)] = []
-        if args.algo:
-            want = {"direct": "d", "winograd": "w", "winograd4": "w4"}[args.algo]
-            times = {key: [] for key in times if key[0] == want}
+        times = {name: [] for name, algo in ALGOS.items()
+                 if (k == 3 or name == "direct") and args.algo in (None, algo)}
         ref = None
         for rnd in range(args.rounds):
             for key in times:
-                algo, v = key
-                os.environ["RPST_CONV_ALGO"] = {"w": "winograd", "w4": "winograd4"}.get(algo, "direct")
-                if v is None:
-                    os.environ.pop("RPST_CONV_VARIANT", None)
-                else:
-                    os.environ["RPST_CONV_VARIANT"] = str(v)
+                os.environ["RPST_CONV_ALGO"] = ALGOS[key]
                 out = ops.conv2d(x, p, b, cout, k, pad=pad, in_op=in_op, relu=True, aux=aux)
                 if ref is None:
                     ref = out.clone()
@@ -102,12 +85,10 @@ def main():
                 e1.record()
                 torch.cuda.synchronize()
                 times[key].append(e0.elapsed_time(e1) / args.reps)
-        os.environ.pop("RPST_CONV_VARIANT", None)
         os.environ.pop("RPST_CONV_ALGO", None)
         row = {"layer": f"{cin}->{cout} k{k} {h}x{wd} N{n} pad{pad} op{in_op}"}
-        for (algo, v), ts in times.items():
+        for name, ts in times.items():
             ms = min(ts)
-            name = {"w": "wino", "w4": "wino4"}.get(algo, "direct" if v is None else f"v{v}")
             row[f"{name}_ms"] = round(ms, 3)
             # effective TF/s: direct-convolution FLOPs / time (F(2x2) executes 4/9, F(4x4) 1/4)
             row[f"{name}_tf"] = round(flops / ms / 1e9, 1)
