@@ -306,9 +306,10 @@ __global__ __launch_bounds__(W4Geo<NR>::NTH, W4Geo<NR>::LAUNCH_WPE) void wino4_m
   // covers only the per-lane offset, not the uniform soffset)
   // (a __device__ helper: a lambda returning a buffer resource silently drops the kernel's
   // host launch stub)
-  // LDS targets are re-derived inside each issue from one laundered wave-uniform offset
-  // (launder()): precomputed, the ~50 per-stage piece addresses overflow the scalar
-  // registers and come back by a VALU readlane each
+  // LDS targets are re-derived once per issue group from one laundered wave-uniform offset
+  // (launder()): precomputed per stage, the piece addresses overflow the scalar registers
+  // and come back by a VALU readlane each. A wave's weight pieces are contiguous, so one
+  // target, one soffset and one descriptor serve them all
 
 
   // ---- patch of one K step: 4 channels, [18 rows][68] (66 columns + 2 spare) at channel
@@ -370,22 +371,34 @@ __global__ __launch_bounds__(W4Geo<NR>::NTH, W4Geo<NR>::LAUNCH_WPE) void wino4_m
   for (int x = 0; x < 18; ++x) acc[x][0] = acc[x][1] = floatx4{0.f, 0.f, 0.f, 0.f};
 
   // K step g (co tile ct0 + g / K4, channels 4 (g % K4)..+3): weight slice (18 pieces of
-  // 1 KiB, pieces w, w + 8, w + 16 of wave w) and patch into its stage by LDS-DMA; every
+  // 1 KiB: wave w copies the contiguous pieces WC w .. WC w + WC - 1, WC = 18 / NW, from one
+  // LDS target and one soffset with the piece in the instruction offset, which the hardware
+  // adds to the global and to the LDS address alike; the two left over go to waves 0 and 1,
+  // the other waves issue a padding piece) and patch into its stage by LDS-DMA; every
   // wave issues the same number of pieces per step (the padding ones read out of range
   // into the dummy target), so the ring's waits are counted: kPer per step
   // (weights of global step g are slice g of the block's weight image: no division; ks =
   // g % K4 is tracked by the caller)
   auto issue_w = [&](int g, bool live, float* st) {
     if (!(DBG & 2)) {
+      constexpr int WC = Geo::WPI - 1, REST = 18 - WC * NW;
+      static_assert(REST > 0 && REST <= NW, "one remainder piece per wave at the most");
       const int wv = launder(wave);
-      const int sw = live ? (ct0 * K4 + g) * kW4SW * 4 + wv * 1024 : 0;  // piece wv's bytes
-#pragma unroll
-      for (int i = 0; i < Geo::WPI; ++i) {
-        const bool real = wv + NW * i < 18;
-        __builtin_amdgcn_raw_ptr_buffer_load_lds(
-            rsrc_or_zero(w_img, wbytes, live && real), (lds_ptr_t)(real ? st + Geo::SPATCH + wv * 256 + NW * 256 * i : dummy), 16, lane * 16,
-            real ? sw + NW * 1024 * i : 0, 0, 0);
+      const int sw = ((ct0 * K4 + g) * kW4SW + wv * (WC * 256)) * 4;  // the wave's first piece
+      const auto r = rsrc_or_zero(w_img, wbytes, live);
+      float* t = st + Geo::SPATCH + wv * (WC * 256);
+      static_assert(WC == 2 || WC == 4, "the contiguous pieces below");
+      __builtin_amdgcn_raw_ptr_buffer_load_lds(r, (lds_ptr_t)t, 16, lane * 16, sw, 0, 0);
+      __builtin_amdgcn_raw_ptr_buffer_load_lds(r, (lds_ptr_t)t, 16, lane * 16, sw, 1024, 0);
+      if constexpr (WC == 4) {
+        __builtin_amdgcn_raw_ptr_buffer_load_lds(r, (lds_ptr_t)t, 16, lane * 16, sw, 2048, 0);
+        __builtin_amdgcn_raw_ptr_buffer_load_lds(r, (lds_ptr_t)t, 16, lane * 16, sw, 3072, 0);
       }
+      const bool real = wv < REST;
+      __builtin_amdgcn_raw_ptr_buffer_load_lds(
+          rsrc_or_zero(w_img, wbytes, live && real),
+          (lds_ptr_t)(real ? st + Geo::SPATCH + (WC * NW + wv) * 256 : dummy), 16, lane * 16,
+          sw + (WC * NW - (WC - 1) * wv) * 1024, 0, 0);
     }
   };
   auto issue_p = [&](int ks, bool live, float* st) {

@@ -39,7 +39,6 @@
 namespace rpst {
 namespace {
 
-__device__ __forceinline__ int q_mask(int v, bool ok) { return v & -(int)ok; }
 // acc += a * b on v_mfma_f32_16x16x4_f32 with the accumulator tied in place ("+v"). The
 // builtin's untied form lets the register allocator rename every accumulator tuple each K
 // step (dst != srcC): with 144 accumulator registers that costs 60-100 more and spills.
@@ -63,15 +62,20 @@ __device__ __forceinline__ void q_mfma(floatx4& acc, float a, float b) {
 __device__ __forceinline__ unsigned q_lds_addr(const float* p) {
   return (unsigned)(uintptr_t)(const __attribute__((address_space(3))) float*)p;
 }
-__device__ __forceinline__ void q_dma16(__amdgpu_buffer_rsrc_t r, const float* lds, unsigned voff,
+// m0: the LDS byte address lane 0 writes; OFF: the instruction offset, which gfx950 adds to the
+// global and to the LDS address alike (LDS address = LDS base + M0 + OFF + 16 lane; checked by
+// tests/test_gpu_conv_ring.py, which fails with M0 advanced by OFF as well), so a wave's
+// contiguous pieces share one M0 value and one soffset
+template <int OFF>
+__device__ __forceinline__ void q_dma16(__amdgpu_buffer_rsrc_t r, unsigned m0, unsigned voff,
                                         int soff) {
-  asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tbuffer_load_dwordx4 %1, %2, %3 offen lds"
-               :: "s"(q_lds_addr(lds)), "v"(voff), "s"(r), "s"(soff) : "memory");
+  asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tbuffer_load_dwordx4 %1, %2, %3 offen offset:%4 lds"
+               :: "s"(m0), "v"(voff), "s"(r), "s"(soff), "i"(OFF) : "memory");
 }
-__device__ __forceinline__ void q_dma4(__amdgpu_buffer_rsrc_t r, const float* lds, unsigned voff,
+__device__ __forceinline__ void q_dma4(__amdgpu_buffer_rsrc_t r, unsigned m0, unsigned voff,
                                        int soff) {
   asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tbuffer_load_dword %1, %2, %3 offen lds"
-               :: "s"(q_lds_addr(lds)), "v"(voff), "s"(r), "s"(soff) : "memory");
+               :: "s"(m0), "v"(voff), "s"(r), "s"(soff) : "memory");
 }
 __device__ __forceinline__ void q_lds_barrier() {
   asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
@@ -539,44 +543,54 @@ __global__ __launch_bounds__(kQNTH, 1) void wino4q_mfma_kernel(ConvArgs a) {
 #pragma unroll
   for (int i = 0; i < kQSlow; ++i) poffs[i][tid] = poff[i];
 
-  // weight slice of step g (the block's co tiles' slices are consecutive) into stage stg:
-  // pieces w + 8 i of its 36 1-KiB pieces; pieces 32-35 come from waves 0-3, waves 4-7 issue
-  // a padding piece into the dummy. Dead steps (g >= G) read zero records.
+  // weight slice of a step (the block's co tiles' slices are consecutive) into the stage at
+  // LDS address stg: the stage is a verbatim copy of the slice's 36 1-KiB pieces, wave w
+  // copies the contiguous pieces 4 w .. 4 w + 3 (i < 4: one m0, one soffset, the piece in the
+  // instruction offset) and, for w < 4, piece 32 + w (i = 4); waves 4-7 issue a padding piece
+  // into the dummy instead, so every wave issues kQWPI pieces and the counted waits hold.
+  // Everything but the stage is wave-uniform and constant for a step: wso = the byte offset
+  // of the wave's first piece (a running value, + one slice per step), live = the step
+  // exists (dead steps and padding pieces read zero records; the range check takes the
+  // voffset and the instruction offset, not the soffset, so that one is not masked).
   constexpr int DBG = RPST_W4Q_DBG;
-  auto issue_w = [&](int g, float* stg, int i) {
+  const int wl = wave * 4096;            // the wave's pieces inside a slice / a stage (bytes)
+  const bool real4 = wave < 4;
+  const int w4 = 32768 + wave * 1024;    // piece 32 + w
+  const unsigned dummy_a = q_lds_addr(dummy);
+  int wso = wl;
+  auto issue_w = [&](bool live, unsigned stg, auto Ic) {
+    constexpr int I = decltype(Ic)::value;
     if (DBG & 2) return;
-    const int wv = launder(wave);
-    const int pc = wv + 8 * i;
-    const bool live = g < G;
-    const int so = q_mask((g * kQWS + pc * 256) * 4, live);
-    if (i < 4) {
-      q_dma16(rsrc_or_zero(w_img, wbytes, live), stg + pc * 256, lane * 16, so);
+    if constexpr (I < 4) {
+      q_dma16<1024 * I>(rsrc_or_zero(w_img, wbytes, live), stg + wl, lane * 16, wso);
     } else {
-      const bool real = pc < 36;
-      q_dma16(rsrc_or_zero(w_img, wbytes, live && real), real ? stg + pc * 256 : dummy, lane * 16,
-              q_mask(so, real));
+      q_dma16<0>(rsrc_or_zero(w_img, wbytes, live && real4), real4 ? stg + w4 : dummy_a,
+                 lane * 16, wso + (w4 - wl));
     }
   };
-  // every patch piece of this wave for step g (K step ks) into stage stg
-  auto issue_p = [&](auto WIDEc, int g, int ks, float* stg) {
+  // every patch piece of this wave for one step into the stage at LDS address stg; pso = the
+  // byte offset of the wave's channel (a running value: + 4 channels per step, back to the
+  // wave's first channel at a co tile's end; a co tile has whole K steps, Cin % 16 == 0)
+  const unsigned pstep = 4u * in_plane * 4u;
+  const int pbase = (int)((unsigned)(wave >> 1) * in_plane * 4u);
+  const bool h1 = (wave & 1) != 0;
+  const int pl = (wave >> 1) * (kQCS * 4) + (h1 ? (wide ? 2048 : kQSlow * 256) : 0);
+  int pso = pbase;
+  auto issue_p = [&](auto WIDEc, bool live, unsigned stg) {
     constexpr bool WIDE = decltype(WIDEc)::value;
     if (DBG & 1) return;
-    const int wv = launder(wave);
-    const int c = 4 * ks + (wv >> 1);
-    const bool ok = g < G && c < a.Cin;
-    const auto r = rsrc_or_zero(in_img, oob, ok);
-    const int so = q_mask((int)((unsigned)c * in_plane * 4u), ok);
-    float* xs = stg + (wv >> 1) * kQCS;
-    const bool h1 = (wv & 1) != 0;
+    const auto r = rsrc_or_zero(in_img, oob, live);
+    // (pl opaque here: precomputed per stage and piece, the targets overflow the scalar
+    // registers and come back by a v_readlane each; derived, a piece costs one s_add)
+    const unsigned xs = stg + launder(pl);
     if constexpr (WIDE) {
-      q_dma16(r, xs + (h1 ? 512 : 0), poffs[0][tid], so);
-      q_dma16(r, h1 ? dummy : xs + 256, poffs[1][tid], so);
+      q_dma16<0>(r, xs, poffs[0][tid], pso);
+      q_dma16<0>(r, h1 ? dummy_a : xs + 1024, poffs[1][tid], pso);
     } else {
 #pragma unroll
-      for (int i = 0; i < kQSlow - 1; ++i)
-        q_dma4(r, xs + 64 * (h1 ? kQSlow + i : i), poffs[i][tid], so);
-      q_dma4(r, xs + 64 * (h1 ? 2 * kQSlow - 1 : kQSlow - 1), poffs[kQSlow - 1][tid], so);
+      for (int i = 0; i < kQSlow; ++i) q_dma4(r, xs + 256 * i, poffs[i][tid], pso);
     }
+    pso += (int)pstep;
   };
   // before step x's barrier: W(x) (issued in step x - 1 ahead of its patch group) and
   // everything older have landed; that youngest patch group (2 / 6 pieces) stays in flight
@@ -618,12 +632,15 @@ __global__ __launch_bounds__(kQNTH, 1) void wino4q_mfma_kernel(ConvArgs a) {
   };
   // ---- prologue: P(0), P(1), W(0), P(2), P(3) -------------------------------------------
   auto prologue = [&](auto WIDEc) {
-    issue_p(WIDEc, 0, 0, ps0);
-    issue_p(WIDEc, 1, 1, ps1);
-#pragma unroll
-    for (int i = 0; i < kQWPI; ++i) issue_w(0, ws0, i);
-    issue_p(WIDEc, 2, 2, ps2);
-    issue_p(WIDEc, 3, 3, ps3);
+    issue_p(WIDEc, true, q_lds_addr(ps0));
+    issue_p(WIDEc, true, q_lds_addr(ps1));
+    issue_w(true, q_lds_addr(ws0), std::integral_constant<int, 0>{});
+    issue_w(true, q_lds_addr(ws0), std::integral_constant<int, 1>{});
+    issue_w(true, q_lds_addr(ws0), std::integral_constant<int, 2>{});
+    issue_w(true, q_lds_addr(ws0), std::integral_constant<int, 3>{});
+    issue_w(true, q_lds_addr(ws0), std::integral_constant<int, 4>{});
+    issue_p(WIDEc, true, q_lds_addr(ps2));
+    issue_p(WIDEc, true, q_lds_addr(ps3));
   };
   if (wide) prologue(std::true_type{});
   else prologue(std::false_type{});
@@ -699,6 +716,11 @@ __global__ __launch_bounds__(kQNTH, 1) void wino4q_mfma_kernel(ConvArgs a) {
     auto step = [&](float* wsx, float* psn, float* wsn, float* psx, float* pfx, int ks,
                     bool first) {
       wait_ring(first);
+      // the step's DMA bookkeeping, once: W(x + 1) and P(x + 4) exist; their soffsets
+      const bool wlive = x + 1 < G, plive = x + 4 < G;
+      wso += kQWS * 4;
+      if (first && ks + 4 == K4) pso = pbase;  // P(x + 4) .. P(x + 7) open the next co tile
+      const unsigned wsn_a = q_lds_addr(wsn), psx_a = q_lds_addr(psx);
       if (DBG & 16) asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
       else q_lds_barrier();  // W(x), P(x + 1) complete; every wave is done with step x - 1
       constexpr int ord[9] = {0, 3, 6, 1, 4, 7, 2, 5, 8};
@@ -719,12 +741,15 @@ __global__ __launch_bounds__(kQNTH, 1) void wino4q_mfma_kernel(ConvArgs a) {
         q_mfma<0>(acc[p][1], w4[p].y, V[p]);
         q_mfma<0>(acc[p][2], w4[p].z, V[p]);
         q_mfma<0>(acc[p][3], w4[p].w, V[p]);
-        if (q >= kQWG0 && q < kQWG0 + kQWPI) issue_w(x + 1, wsn, q - kQWG0);
+        if (q == kQWG0) issue_w(wlive, wsn_a, std::integral_constant<int, 0>{});
+        if (q == kQWG0 + 1) issue_w(wlive, wsn_a, std::integral_constant<int, 1>{});
+        if (q == kQWG0 + 2) issue_w(wlive, wsn_a, std::integral_constant<int, 2>{});
+        if (q == kQWG0 + 3) issue_w(wlive, wsn_a, std::integral_constant<int, 3>{});
+        if (q == kQWG0 + 4) issue_w(wlive, wsn_a, std::integral_constant<int, 4>{});
         // P(x + 4): K step ks + 4 of this co tile, or of the next one
         if (q == kQPG) {
-          const int k4 = ks + 4 < K4 ? ks + 4 : ks + 4 - K4;
-          if (wide) issue_p(std::true_type{}, x + 4, k4, psx);
-          else issue_p(std::false_type{}, x + 4, k4, psx);
+          if (wide) issue_p(std::true_type{}, plive, psx_a);
+          else issue_p(std::false_type{}, plive, psx_a);
         }
         // pipelined transform of P(x + 1): rows at groups 0-4, column j's row pass at
         // groups 5, 6 and (after its MFMAs) 8
