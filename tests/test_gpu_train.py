@@ -309,6 +309,50 @@ def _is_gbias(name):  # exactly zero: softmax(F^T (G + b)) does not depend on b
     return name.endswith(".g.bias")
 
 
+def test_stack_backward_mixed(cuda):
+    """rpst.autograd._stack_backward on a stack that mixes what the families use apart: a
+    reflect 3x3 + ReLU, a 1x1 + ReLU (its dgrad takes no ReLU mask), an upsampled bias-free
+    reflect 3x3 + LeakyReLU, a zero-pad 3x3, on an odd-height, ragged-width input. Every
+    parameter gradient and the input gradient against float64 CPU autograd of the same
+    nn.Sequential, per-tensor rel-L2 max(1e-4, 3 x its fp32 distance) (_floor_bars)."""
+    from rpst import autograd as A
+    from rpst import plan, synth
+    nn = torch.nn
+    seq = nn.Sequential(nn.ReflectionPad2d(1), nn.Conv2d(3, 8, 3), nn.ReLU(),
+                        nn.Conv2d(8, 8, 1), nn.ReLU(),
+                        nn.Upsample(scale_factor=2, mode='nearest'), nn.ReflectionPad2d(1),
+                        nn.Conv2d(8, 6, 3, bias=False), nn.LeakyReLU(0.2),
+                        nn.Conv2d(6, 5, 3, padding=1))
+    synth_(seq, 81)
+    x = torch.from_numpy(synth.image(82, (2, 3, 7, 10)))
+    g = gen(83, (2, 5, 14, 20))
+
+    def cpu_grads(dtype):
+        m = copy.deepcopy(seq).to(dtype)
+        xd = x.to(dtype).requires_grad_()
+        m(xd).backward(g.to(dtype))
+        return dict({k: p.grad for k, p in m.named_parameters()}, input=xd.grad)
+
+    g64 = cpu_grads(torch.float64)
+    bars = _floor_bars(cpu_grads(torch.float32), g64)
+    seq = seq.to(cuda)
+    steps = plan.compile_layers(seq.children())
+    with torch.no_grad():
+        _, saved = A._run_steps_saving(steps, x.to(cuda))
+        grads, grads0 = {}, {}
+        dx = A._stack_backward(steps, saved, g.to(cuda), grads, need_input_grad=True)
+        assert A._stack_backward(steps, saved, g.to(cuda), grads0, need_input_grad=False) is None
+    named = dict(seq.named_parameters())
+    assert sorted(named) == sorted(k for k in g64 if k != "input")
+    assert set(grads) == {id(p) for p in named.values()}  # no entry for the absent bias
+    got = dict({k: grads[id(p)] for k, p in named.items()}, input=dx)
+    for k, gref in g64.items():
+        print(f"stack backward mixed {k}: {rel_l2(got[k], gref):.3e} (bar {bars[k]:.3e})")
+        assert rel_l2(got[k], gref) < bars[k], (k, rel_l2(got[k], gref), bars[k])
+    # without an input gradient: the same parameter gradients, no dgrad of the first conv
+    assert set(grads0) == set(grads) and all(torch.equal(grads0[k], grads[k]) for k in grads)
+
+
 def _sam_model(seed, img, cuda):
     import network as net
     m = net.SAModel(dict(SAM_CFG), copy.deepcopy(net.vgg), 0, img)
@@ -407,9 +451,10 @@ def test_samodel_training_gradients_match_reference(cuda, golden):
 @pytest.mark.parametrize("mode", ["aea", "relu"])
 @pytest.mark.parametrize("shape", [(2, 64, 8, 8), (1, 32, 4, 4)])
 def test_adaptive_sanet_backward(cuda, mode, shape):
-    """rpst.autograd._adaptive_sanet_forward / _backward (1x1 convs, mean_variance_norm, the
-    AEA-clamped attention and the f_psi MLP on rpst_adaptive_attention_backward) against
-    float64 autograd of oracle.adaptive_sanet on the same fp32 inputs."""
+    """rpst.autograd._sanet_forward / _sanet_backward on an AdaptiveSANet (1x1 convs,
+    mean_variance_norm, the AEA-clamped attention and the f_psi MLP on
+    rpst_adaptive_attention_backward) against float64 autograd of oracle.adaptive_sanet on
+    the same fp32 inputs."""
     import network as net
     from rpst import autograd as A
     n, C, h, w = shape
@@ -427,9 +472,9 @@ def test_adaptive_sanet_backward(cuda, mode, shape):
     bars = _floor_bars({k: v.grad for k, v in sd32.items()}, {k: v.grad for k, v in sd.items()})
     m = m.to(cuda)
     with torch.no_grad():
-        out, saved = A._adaptive_sanet_forward(m, c.to(cuda), s.to(cuda))
+        out, saved = A._sanet_forward(m, c.to(cuda), s.to(cuda))
         grads = {}
-        A._adaptive_sanet_backward(m, saved, g.to(cuda), grads)
+        A._sanet_backward(m, saved, g.to(cuda), grads)
     assert rel_l2(out, ref.detach()) < 1e-5, rel_l2(out, ref.detach())
     worst = 0.0
     for name, p in m.named_parameters():
