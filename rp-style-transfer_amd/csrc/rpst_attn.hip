@@ -17,7 +17,6 @@
 // contiguous (RK: row-major rows with k contiguous; KR: k-rows with m/n contiguous).
 // Register prefetch of tile t+1 overlaps the MFMAs of tile t.
 #include <algorithm>
-#include <cstdlib>
 
 #include "rpst_common.h"
 
@@ -325,13 +324,36 @@ __global__ __launch_bounds__(256) void rowstats_kernel(const float* __restrict__
   }
 }
 
+// What a call site asks of the GEMM: each operand once as pointer, leading dimension and
+// batch stride (elements), the rest by name. launch_gemm lays it out as the kernel's GemmArgs.
+template <class T>
+struct MatT {
+  T* p;
+  int ld;
+  int64_t stride;
+};
+using Mat = MatT<const float>;
+struct GemmReq {
+  Mat A, B;
+  MatT<float> C;
+  int M, N, K;
+  RowVec rv = {};
+  int64_t sV = 0;  // batch stride of rv's vectors and of colscale
+  const float* colscale = nullptr;
+  const float* colbias = nullptr;
+  int act = 0;
+  int ks = 1, kc = 0;
+  int accum = 0;
+};
+
 template <int ALAY, int BLAY, int BX>
-static void launch_gemm(const GemmArgs& g, int batch, hipStream_t st) {
-  static const int mw_env = [] {
-    const char* e = std::getenv("RPST_GEMM_MW");  // A/B: 1 = 128-row tiles everywhere
-    return e && *e ? std::atoi(e) : 0;
-  }();
-  const int mw = mw_env == 1 ? 1 : (g.M >= 256 ? 2 : 1);
+static void launch_gemm(const GemmReq& r, int batch, hipStream_t st) {
+  const GemmArgs g{.A = r.A.p, .B = r.B.p, .C = r.C.p, .rv = r.rv, .colscale = r.colscale,
+                   .colbias = r.colbias, .act = r.act, .M = r.M, .N = r.N, .K = r.K,
+                   .lda = r.A.ld, .ldb = r.B.ld, .ldc = r.C.ld, .sA = r.A.stride,
+                   .sB = r.B.stride, .sC = r.C.stride, .sV = r.sV, .ks = r.ks, .kc = r.kc,
+                   .accum = r.accum};
+  const int mw = g.M >= 256 ? 2 : 1;
   dim3 grid((g.N + kGBN - 1) / kGBN, (g.M + 128 * mw - 1) / (128 * mw), batch * g.ks);
   auto aligned = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; };
   // 16-B loads need the contiguous dim, the leading dim and the batch stride % 4 == 0
@@ -376,14 +398,20 @@ __global__ __launch_bounds__(256) void softmax_bwd_logits_kernel(const float* __
   for (int i = lane; i < L; i += 64) d[i] = expf(s[i] - m) * inv * (d[i] - dot);
 }
 
-// out[i] = sum_b in[b][i] (fixed order over b)
-__global__ void batch_sum_kernel(const float* __restrict__ in, float* __restrict__ out,
-                                 int64_t per, int nb) {
-  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+// out[b][i] = sum_j part[b * n + j][i], j first to last (b = blockIdx.y)
+__global__ void partial_sum_kernel(const float* __restrict__ part, float* __restrict__ out,
+                                   int64_t per, int n) {
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
   if (i >= per) return;
-  float s = 0.f;
-  for (int b = 0; b < nb; ++b) s += in[(int64_t)b * per + i];
-  out[i] = s;
+  const float* p = part + (int64_t)blockIdx.y * n * per + i;
+  float acc = p[0];
+  for (int j = 1; j < n; ++j) acc += p[j * per];
+  out[blockIdx.y * per + i] = acc;
+}
+static int partial_sum(const float* part, float* out, int64_t per, int n, int B, const char* what,
+                       hipStream_t st) {
+  partial_sum_kernel<<<dim3((unsigned)((per + 255) / 256), B), 256, 0, st>>>(part, out, per, n);
+  return launch_status(what);
 }
 
 // db[c] = sum_{b, p} dy[b][c][p]: one block per channel (a launch of C blocks fills the chip
@@ -636,8 +664,10 @@ __global__ __launch_bounds__(256) void clamp_head_kernel(const float* __restrict
 }
 
 // AEALRelu second softmax: per row, m2 = max_j relu(P_ij - c_i), inv2 = 1 / sum_j
-// exp(relu(P_ij - c_i) - m2), with P_ij = exp(S_ij - m_i) inv_i formed exactly as the
-// GEMM staging forms it. One wave per row.
+// exp(relu(P_ij - c_i) - m2). LOGITS: the row holds S and P_ij = exp(S_ij - m_i) inv_i is
+// formed exactly as the GEMM staging forms it; else the row holds P itself (a given attention
+// matrix: aea_apply_kernel's mode 1; rmax and rinv unused). One wave per row.
+template <bool LOGITS>
 __global__ __launch_bounds__(256) void rowstats_relu_kernel(
     const float* __restrict__ S, const float* __restrict__ rmax, const float* __restrict__ rinv,
     const float* __restrict__ clamp, float* __restrict__ m2, float* __restrict__ inv2,
@@ -646,12 +676,13 @@ __global__ __launch_bounds__(256) void rowstats_relu_kernel(
   const int lane = threadIdx.x & 63;
   if (row >= rows) return;
   const float* s = S + row * L;
-  const float m = rmax[row], inv = rinv[row], c = clamp[row];
+  const float m = LOGITS ? rmax[row] : 0.f, inv = LOGITS ? rinv[row] : 0.f, c = clamp[row];
+  auto p = [&](int i) { return LOGITS ? expf(s[i] - m) * inv : s[i]; };
   float mx = -INFINITY;
-  for (int i = lane; i < L; i += 64) mx = fmaxf(mx, fmaxf(expf(s[i] - m) * inv - c, 0.f));
+  for (int i = lane; i < L; i += 64) mx = fmaxf(mx, fmaxf(p(i) - c, 0.f));
   mx = wave_max(mx);
   float sum = 0.f;
-  for (int i = lane; i < L; i += 64) sum += expf(fmaxf(expf(s[i] - m) * inv - c, 0.f) - mx);
+  for (int i = lane; i < L; i += 64) sum += expf(fmaxf(p(i) - c, 0.f) - mx);
   sum = wave_sum(sum);
   if (lane == 0) {
     m2[row] = mx;
@@ -695,25 +726,13 @@ __global__ __launch_bounds__(256) void aea_apply_kernel(const float* __restrict_
   out[idx] = mode == 0 ? 1.f / (1.f + expf(-(scale * d))) : expf(fmaxf(d, 0.f) - m2[r]) * inv2[r];
 }
 
-// Row max / inverse sum of exp(relu(fx - c) - max) for aea_apply_kernel's mode 1.
-__global__ __launch_bounds__(256) void rowstats_relu_plain_kernel(
-    const float* __restrict__ fx, const float* __restrict__ clamp, float* __restrict__ m2,
-    float* __restrict__ inv2, int64_t rows, int L) {
-  const int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
-  const int lane = threadIdx.x & 63;
-  if (row >= rows) return;
-  const float* s = fx + row * L;
-  const float c = clamp[row];
-  float mx = -INFINITY;
-  for (int i = lane; i < L; i += 64) mx = fmaxf(mx, fmaxf(s[i] - c, 0.f));
-  mx = wave_max(mx);
-  float sum = 0.f;
-  for (int i = lane; i < L; i += 64) sum += expf(fmaxf(s[i] - c, 0.f) - mx);
-  sum = wave_sum(sum);
-  if (lane == 0) {
-    m2[row] = mx;
-    inv2[row] = 1.f / sum;
-  }
+// f_psi's head over the B * HW rows of Z (both clamp_values* forms end here)
+static int clamp_head(const float* Z, const float* w2, const float* b2, int hid, int mode,
+                      float from, float interval, float* clamp, int B, int HW, hipStream_t st) {
+  const int64_t rows = (int64_t)B * HW;
+  clamp_head_kernel<<<(unsigned)((rows + 3) / 4), 256, 0, st>>>(Z, w2, b2, clamp, rows, hid,
+                                                               mode, from, interval);
+  return launch_status("clamp_head_kernel");
 }
 
 // clamp[b, i] = head(LeakyReLU(A[b, i, :] W1^T + b1)) (AEAModule.f_psi over affinity rows)
@@ -721,14 +740,11 @@ static int clamp_values(const float* A, const float* w1, const float* b1, const 
                         const float* b2, int hid, int mode, float from, float interval,
                         float* Z, float* clamp, int B, int HW, hipStream_t st) {
   // Z[b][i][n] = sum_j A[b][i][j] W1[n][j] + b1[n]: M = HW (i), N = hid (n), K = HW (j)
-  GemmArgs gz{A, w1, Z, {}, nullptr, b1, 1, HW, hid, HW, HW, HW, hid,
-              (int64_t)HW * HW, 0, (int64_t)HW * hid, 0};
-  launch_gemm<LAY_RK, LAY_RK, BX_NONE>(gz, B, st);
+  launch_gemm<LAY_RK, LAY_RK, BX_NONE>({.A = {A, HW, (int64_t)HW * HW}, .B = {w1, HW, 0},
+                                        .C = {Z, hid, (int64_t)HW * hid}, .M = HW, .N = hid,
+                                        .K = HW, .colbias = b1, .act = 1}, B, st);
   if (int e = launch_status("gemm_f32_kernel(Z=A W1^T)")) return e;
-  const int64_t rows = (int64_t)B * HW;
-  clamp_head_kernel<<<(unsigned)((rows + 3) / 4), 256, 0, st>>>(Z, w2, b2, clamp, rows, hid,
-                                                               mode, from, interval);
-  return launch_status("clamp_head_kernel");
+  return clamp_head(Z, w2, b2, hid, mode, from, interval, clamp, B, HW, st);
 }
 
 // K chunks of T = sn W1^T (C x hidden per image, K = HW): its grid is C/256 x hidden/128
@@ -739,17 +755,6 @@ static int clamp_t_ks(int HW) { return HW >= 2048 ? 4 : 1; }
 static size_t clamp_t_floats(int B, int C, int HW, int hidden) {
   const int ks = clamp_t_ks(HW);
   return (size_t)B * C * hidden * (ks > 1 ? 1 + ks : 1);
-}
-// out[b][i] = sum_j part[b * ks + j][i] (fixed order over j)
-__global__ void ksum_kernel(const float* __restrict__ part, float* __restrict__ out,
-                            int64_t per, int ks, int B) {
-  const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  if (t >= per * B) return;
-  const int64_t b = t / per, i = t - b * per;
-  const float* p = part + b * ks * per + i;
-  float acc = p[0];
-  for (int j = 1; j < ks; ++j) acc += p[j * per];
-  out[t] = acc;
 }
 
 // The clamp values without the affinity matrix: f_psi's first Linear only ever sees
@@ -763,29 +768,22 @@ static int clamp_values_factored(const float* cn, const float* sn, const float* 
                                  int mode, float from, float interval, float* T, float* Z,
                                  float* clamp, int B, int C, int HW, hipStream_t st) {
   const int ks = clamp_t_ks(HW);
-  const int64_t per = (int64_t)C * hid;
-  GemmArgs gt{sn, w1, ks > 1 ? T + (size_t)B * per : T, {}, nullptr, nullptr, 0, C, hid, HW,
-              HW, HW, hid, (int64_t)C * HW, 0, per, 0};
-  if (ks > 1) {
-    gt.ks = ks;
-    gt.kc = (HW + ks - 1) / ks;
-    gt.kc = (gt.kc + 31) / 32 * 32;
-  }
-  launch_gemm<LAY_RK, LAY_RK, BX_NONE>(gt, B, st);
+  const int kc = ks > 1 ? ((HW + ks - 1) / ks + 31) / 32 * 32 : 0;
+  const int64_t per = (int64_t)C * hid, fhw = (int64_t)C * HW;
+  float* Tpart = ks > 1 ? T + (size_t)B * per : T;
+  // T[b][c][n] = sum_j sn[b][c][j] W1[n][j], or its ks partials over chunks of kc pixels
+  launch_gemm<LAY_RK, LAY_RK, BX_NONE>({.A = {sn, HW, fhw}, .B = {w1, HW, 0},
+                                        .C = {Tpart, hid, per}, .M = C, .N = hid,
+                                        .K = HW, .ks = ks, .kc = kc}, B, st);
   if (int e = launch_status("gemm_f32_kernel(T=sn W1^T)")) return e;
-  if (ks > 1) {
-    ksum_kernel<<<(unsigned)((per * B + 255) / 256), 256, 0, st>>>(T + (size_t)B * per, T, per,
-                                                                   ks, B);
-    if (int e = launch_status("ksum_kernel(T)")) return e;
-  }
-  GemmArgs gz{cn, T, Z, {}, nullptr, b1, 1, HW, hid, C, HW, hid, hid,
-              (int64_t)C * HW, (int64_t)C * hid, (int64_t)HW * hid, 0};
-  launch_gemm<LAY_KR, LAY_KR, BX_NONE>(gz, B, st);
+  if (ks > 1)
+    if (int e = partial_sum(Tpart, T, per, ks, B, "partial_sum_kernel(T)", st)) return e;
+  // Z[b][i][n] = sum_c cn[b][c][i] T[b][c][n] + b1[n]
+  launch_gemm<LAY_KR, LAY_KR, BX_NONE>({.A = {cn, HW, fhw}, .B = {T, hid, per},
+                                        .C = {Z, hid, (int64_t)HW * hid}, .M = HW, .N = hid,
+                                        .K = C, .colbias = b1, .act = 1}, B, st);
   if (int e = launch_status("gemm_f32_kernel(Z=cn^T T)")) return e;
-  const int64_t rows = (int64_t)B * HW;
-  clamp_head_kernel<<<(unsigned)((rows + 3) / 4), 256, 0, st>>>(Z, w2, b2, clamp, rows, hid,
-                                                               mode, from, interval);
-  return launch_status("clamp_head_kernel");
+  return clamp_head(Z, w2, b2, hid, mode, from, interval, clamp, B, HW, st);
 }
 
 static int col_norms(const float* c, const float* s, float* cn, float* sn, int B, int C, int HW,
@@ -798,16 +796,26 @@ static int col_norms(const float* c, const float* s, float* cn, float* sn, int B
 
 static int affinity(const float* c, const float* s, float* out, float* cn, float* sn, int B,
                     int C, int HW, hipStream_t st) {
-  const unsigned nb = (unsigned)((int64_t)B * ((HW + 63) / 64));
-  colnorm_kernel<<<nb, 256, 0, st>>>(c, cn, B, C, HW);
-  colnorm_kernel<<<nb, 256, 0, st>>>(s, sn, B, C, HW);
-  if (int e = launch_status("colnorm_kernel")) return e;
+  if (int e = col_norms(c, s, cn, sn, B, C, HW, st)) return e;
   const int64_t fhw = (int64_t)C * HW;
   // A[b][i][j] = sum_c cn[b][c][i] sn[b][c][j]
-  GemmArgs ga{cn, sn, out, {}, nullptr, nullptr, 0, HW, HW, C, HW, HW, HW,
-              fhw, fhw, (int64_t)HW * HW, 0};
-  launch_gemm<LAY_KR, LAY_KR, BX_NONE>(ga, B, st);
+  launch_gemm<LAY_KR, LAY_KR, BX_NONE>({.A = {cn, HW, fhw}, .B = {sn, HW, fhw},
+                                        .C = {out, HW, (int64_t)HW * HW}, .M = HW, .N = HW,
+                                        .K = C}, B, st);
   return launch_status("gemm_f32_kernel(A=cn^T sn)");
+}
+
+// S[b][i][j] = sum_c F[b][c][i] G[b][c][j] for the n query columns i that Fq holds (all of
+// them, or one chunk: F + q0), and the softmax statistics of its B * n rows
+static int logits_rowstats(Mat Fq, int n, Mat G, float* S, float* rmax, float* rinv, int B, int C,
+                           const char* what, hipStream_t st) {
+  const int HWs = G.ld;
+  launch_gemm<LAY_KR, LAY_KR, BX_NONE>({.A = Fq, .B = G, .C = {S, HWs, (int64_t)n * HWs},
+                                        .M = n, .N = HWs, .K = C}, B, st);
+  if (int e = launch_status(what)) return e;
+  const int64_t rows = (int64_t)B * n;
+  rowstats_kernel<<<(unsigned)((rows + 3) / 4), 256, 0, st>>>(S, rmax, rinv, rows, HWs);
+  return launch_status("rowstats_kernel");
 }
 
 }  // namespace rpst
@@ -841,18 +849,13 @@ extern "C" int rpst_sanet_attention(const float* F, const float* G, const float*
   float* rmax = S + (size_t)B * HW * HW;
   float* rinv = rmax + (size_t)B * HW;
   const int64_t fhw = (int64_t)C * HW;
-  // S[b][i][j] = sum_c F[b][c][i] G[b][c][j]
-  GemmArgs g1{F, G, S, {}, nullptr, nullptr, 0, HW, HW, C, HW, HW, HW,
-               fhw, fhw, (int64_t)HW * HW, 0};
-  launch_gemm<LAY_KR, LAY_KR, BX_NONE>(g1, B, st);
-  if (int e = launch_status("gemm_f32_kernel(S=F^T G)")) return e;
-  const int64_t rows = (int64_t)B * HW;
-  rowstats_kernel<<<(unsigned)((rows + 3) / 4), 256, 0, st>>>(S, rmax, rinv, rows, HW);
-  if (int e = launch_status("rowstats_kernel")) return e;
+  if (int e = logits_rowstats({F, HW, fhw}, HW, {G, HW, fhw}, S, rmax, rinv, B, C,
+                              "gemm_f32_kernel(S=F^T G)", st))
+    return e;
   // O[b][c][i] = (1/l_i) sum_j H[b][c][j] exp(S[b][i][j] - m_i)
-  GemmArgs g2{H, S, O, {rmax, nullptr, nullptr, nullptr, 0.f}, rinv, nullptr, 0,
-               C, HW, HW, HW, HW, HW, fhw, (int64_t)HW * HW, fhw, HW};
-  launch_gemm<LAY_RK, LAY_RK, BX_EXP>(g2, B, st);
+  launch_gemm<LAY_RK, LAY_RK, BX_EXP>({.A = {H, HW, fhw}, .B = {S, HW, (int64_t)HW * HW},
+                                       .C = {O, HW, fhw}, .M = C, .N = HW, .K = HW,
+                                       .rv = {.m = rmax}, .sV = HW, .colscale = rinv}, B, st);
   return launch_status("gemm_f32_kernel(O=H P^T)");
 }
 
@@ -901,14 +904,42 @@ extern "C" int rpst_aea_clamp(const float* x, const float* fx, const float* w1,
     return e;
   const int64_t rows = (int64_t)B * HW;
   if (mode == 1) {
-    rowstats_relu_plain_kernel<<<(unsigned)((rows + 3) / 4), 256, 0, st>>>(fx, out_clamp, m2,
-                                                                           inv2, rows, HW);
-    if (int e = launch_status("rowstats_relu_plain_kernel")) return e;
+    rowstats_relu_kernel<false><<<(unsigned)((rows + 3) / 4), 256, 0, st>>>(
+        fx, nullptr, nullptr, out_clamp, m2, inv2, rows, HW);
+    if (int e = launch_status("rowstats_relu_kernel(fx)")) return e;
   }
   const int64_t n = rows * HW;
   aea_apply_kernel<<<(unsigned)((n + 255) / 256), 256, 0, st>>>(fx, out_clamp, m2, inv2, out_fx,
                                                                 rows, HW, mode, scale);
   return launch_status("aea_apply_kernel");
+}
+
+// After the logits S (B * HW rows, softmax statistics rmax / rinv) and the clamp values: the
+// relu softmax statistics (mode 1; into m2 / inv2), the maps the caller keeps, its copy of the
+// clamp values. S == nullptr (flash path, no map kept): the copy only.
+static int adaptive_claims(const float* S, const float* rmax, const float* rinv,
+                           const float* clamp, float* m2, float* inv2, float scale, int mode,
+                           float* claim_value, float* claim_before, float* claim_after, int B,
+                           int HW, hipStream_t st) {
+  const int64_t rows = (int64_t)B * HW, n = rows * HW;
+  if (S && mode == 1) {
+    rowstats_relu_kernel<true><<<(unsigned)((rows + 3) / 4), 256, 0, st>>>(S, rmax, rinv, clamp,
+                                                                           m2, inv2, rows, HW);
+    if (int e = launch_status("rowstats_relu_kernel")) return e;
+  }
+  if (claim_before || claim_after) {
+    const RowVec rv{.m = rmax, .inv = rinv, .clamp = clamp, .m2 = m2, .scale = scale};
+    claim_maps_kernel<<<(unsigned)((n + 255) / 256), 256, 0, st>>>(
+        S, rv, inv2, mode, claim_before, claim_after, rows, HW);
+    if (int e = launch_status("claim_maps_kernel")) return e;
+  }
+  if (claim_value &&
+      hipMemcpyAsync(claim_value, clamp, sizeof(float) * rows, hipMemcpyDeviceToDevice, st) !=
+          hipSuccess) {
+    set_error("adaptive_attention: claim_value copy failed");
+    return RPST_EHIP;
+  }
+  return RPST_OK;
 }
 
 // the logits' region first holds T = sn W1^T (C x hidden per image): whichever is larger.
@@ -959,85 +990,141 @@ extern "C" int rpst_adaptive_attention(const float* F, const float* G, const flo
   if (int e = clamp_values_factored(cn, sn, w1, b1, w2, b2, hidden, mode, from, interval, S, Z,
                                     clamp, B, C, HW, st))
     return e;
-  const int64_t fhw = (int64_t)C * HW;
-  const int64_t rows = (int64_t)B * HW;
+  const Mat Fm{F, HW, (int64_t)C * HW}, Gm{G, HW, (int64_t)C * HW}, Hm{H, HW, (int64_t)C * HW};
   if (sanet_flash_ok(C, HW)) {
     // 2. pass 1: softmax row statistics of S = F^T G, S never written (rpst_flash.hip)
     if (int e = adaptive_flash_stats(F, G, B, C, HW, rmax, rinv, st)) return e;
-    if (claim_before || claim_after) {
-      // the maps the caller keeps: S formed in its own (B, HW, HW) buffer and transformed in
-      // place, with pass 1's statistics
-      // (row statistics of this S itself: pass 1's, from the flash kernel's summation order,
-      // would put the maps ~1e-5 off the logits they transform, amplified by the slope-50
-      // sigmoid)
-      float* Sx = claim_before ? claim_before : claim_after;
-      float* cmax = inv2 + (size_t)B * HW;
-      float* cinv = cmax + (size_t)B * HW;
-      GemmArgs g1{F, G, Sx, {}, nullptr, nullptr, 0, HW, HW, C, HW, HW, HW,
-                  fhw, fhw, (int64_t)HW * HW, 0};
-      launch_gemm<LAY_KR, LAY_KR, BX_NONE>(g1, B, st);
-      if (int e = launch_status("gemm_f32_kernel(S=F^T G, claims)")) return e;
-      rowstats_kernel<<<(unsigned)((rows + 3) / 4), 256, 0, st>>>(Sx, cmax, cinv, rows, HW);
-      if (int e = launch_status("rowstats_kernel")) return e;
-      if (mode == 1) {
-        rowstats_relu_kernel<<<(unsigned)((rows + 3) / 4), 256, 0, st>>>(Sx, cmax, cinv, clamp,
-                                                                         m2, inv2, rows, HW);
-        if (int e = launch_status("rowstats_relu_kernel")) return e;
-      }
-      const RowVec rv{cmax, cinv, clamp, m2, scale};
-      const int64_t n = rows * HW;
-      claim_maps_kernel<<<(unsigned)((n + 255) / 256), 256, 0, st>>>(Sx, rv, inv2, mode,
-                                                                     claim_before, claim_after,
-                                                                     rows, HW);
-      if (int e = launch_status("claim_maps_kernel")) return e;
-    }
-    if (claim_value &&
-        hipMemcpyAsync(claim_value, clamp, sizeof(float) * rows, hipMemcpyDeviceToDevice, st) !=
-            hipSuccess) {
-      set_error("adaptive_attention: claim_value copy failed");
-      return RPST_EHIP;
-    }
+    // the maps the caller keeps: S formed in its own (B, HW, HW) buffer and transformed in
+    // place, with the row statistics of this S itself (pass 1's, from the flash kernel's
+    // summation order, would put the maps ~1e-5 off the logits they transform, amplified by
+    // the slope-50 sigmoid)
+    float* Sx = claim_before ? claim_before : claim_after;
+    float* cmax = inv2 + (size_t)B * HW;
+    float* cinv = cmax + (size_t)B * HW;
+    if (Sx)
+      if (int e = logits_rowstats(Fm, HW, Gm, Sx, cmax, cinv, B, C,
+                                  "gemm_f32_kernel(S=F^T G, claims)", st))
+        return e;
+    if (int e = adaptive_claims(Sx, cmax, cinv, clamp, m2, inv2, scale, mode, claim_value,
+                                claim_before, claim_after, B, HW, st))
+      return e;
     // 3. pass 2: S recomputed per key block, Q formed in registers, O = H Q^T
     return adaptive_flash_apply(F, G, H, O, B, C, HW, rmax, rinv, clamp, mode, scale, st);
   }
   // 2. logits S = F^T G and softmax row statistics (sanet.py:114-117)
-  GemmArgs g1{F, G, S, {}, nullptr, nullptr, 0, HW, HW, C, HW, HW, HW,
-              fhw, fhw, (int64_t)HW * HW, 0};
-  launch_gemm<LAY_KR, LAY_KR, BX_NONE>(g1, B, st);
-  if (int e = launch_status("gemm_f32_kernel(S=F^T G)")) return e;
-  rowstats_kernel<<<(unsigned)((rows + 3) / 4), 256, 0, st>>>(S, rmax, rinv, rows, HW);
-  if (int e = launch_status("rowstats_kernel")) return e;
-  RowVec rv{rmax, rinv, clamp, m2, scale};
-  if (mode == 1) {
-    rowstats_relu_kernel<<<(unsigned)((rows + 3) / 4), 256, 0, st>>>(S, rmax, rinv, clamp, m2,
-                                                                     inv2, rows, HW);
-    if (int e = launch_status("rowstats_relu_kernel")) return e;
-  }
-  if (claim_before || claim_after) {
-    const int64_t n = rows * HW;
-    claim_maps_kernel<<<(unsigned)((n + 255) / 256), 256, 0, st>>>(S, rv, inv2, mode,
-                                                                   claim_before, claim_after,
-                                                                   rows, HW);
-    if (int e = launch_status("claim_maps_kernel")) return e;
-  }
-  if (claim_value) {
-    if (hipMemcpyAsync(claim_value, clamp, sizeof(float) * rows, hipMemcpyDeviceToDevice, st) !=
-        hipSuccess) {
-      set_error("adaptive_attention: claim_value copy failed");
-      return RPST_EHIP;
-    }
-  }
-  // 3. O[b][c][i] = sum_j H[b][c][j] Q[b][i][j], Q formed while S is staged (sanet.py:122-124)
-  if (mode == 0) {
-    GemmArgs g2{H, S, O, rv, nullptr, nullptr, 0, C, HW, HW, HW, HW, HW,
-                fhw, (int64_t)HW * HW, fhw, HW};
-    launch_gemm<LAY_RK, LAY_RK, BX_AEA>(g2, B, st);
-  } else {
-    GemmArgs g2{H, S, O, rv, inv2, nullptr, 0, C, HW, HW, HW, HW, HW,
-                fhw, (int64_t)HW * HW, fhw, HW};
-    launch_gemm<LAY_RK, LAY_RK, BX_AEAR>(g2, B, st);
-  }
+  if (int e = logits_rowstats(Fm, HW, Gm, S, rmax, rinv, B, C, "gemm_f32_kernel(S=F^T G)", st))
+    return e;
+  if (int e = adaptive_claims(S, rmax, rinv, clamp, m2, inv2, scale, mode, claim_value,
+                              claim_before, claim_after, B, HW, st))
+    return e;
+  // 3. O[b][c][i] = sum_j H[b][c][j] Q[b][i][j], Q formed while S is staged (sanet.py:122-124);
+  //    relu: its 1 / l2_i is the column scale
+  const GemmReq g2{.A = Hm, .B = {S, HW, (int64_t)HW * HW}, .C = {O, HW, Hm.stride}, .M = C,
+                   .N = HW, .K = HW,
+                   .rv = {.m = rmax, .inv = rinv, .clamp = clamp, .m2 = m2, .scale = scale},
+                   .sV = HW, .colscale = mode == 0 ? nullptr : inv2};
+  if (mode == 0) launch_gemm<LAY_RK, LAY_RK, BX_AEA>(g2, B, st);
+  else launch_gemm<LAY_RK, LAY_RK, BX_AEAR>(g2, B, st);
   return launch_status("gemm_f32_kernel(O=H Q^T)");
+}
+
+// ---- attention backward over query chunks (sanet.py:86-94, 100-138 under autograd) ------
+// S and dP are formed for qc queries (full rows) at a time: per chunk S_q = F_q^T G, the row
+// statistics, dH += dO_q P_q (P formed while S_q is staged), dP_q = dO_q^T H, dS_q = P (dP -
+// rowsum(dP P)) in place (softmax_bwd_logits_kernel: whole rows, so every row of dS sums to
+// zero to rounding), dF_q = G dS_q^T, dG += F_q dS_q; dH and dG sum the chunks in order.
+// 10 HW^2 C FLOP per image whatever qc is, and S, its statistics and dS do not depend on qc
+// bit for bit (the GEMM's k order does not depend on M). qc = HWc is the single pass with S and
+// dP whole (rpst_sanet_attention_backward); the chunked entry points use kAttnQC and need no
+// B x HW x HW workspace. (2048: the dF_q GEMM's grid is C/256 x qc/128 tiles per image -- at
+// 1024 queries, C = 512 and B = 8 only 128 workgroups, and the SAModel training step ran 2.8 %
+// slower than the single pass; at 2048 0.6 %, profiles/r05/attn_bwd_qc.log.)
+constexpr int kAttnQC = 2048;
+
+struct WalkScratch {
+  float *S, *dP;        // [B][qc][HWs] each
+  float *rmax, *rinv;   // [B][qc]
+};
+// The AdaptiveSANet part of the walk: the attention is Q = AEA(P, clamp), so P in the dH
+// product becomes Q, and the row pass goes from dQ to dS and dc (aea_bwd_rows_kernel).
+struct WalkAdaptive {
+  const float* clamp;            // (B, HW) clamp values
+  int mode;                      // 0 AEAModule, 1 AEALReluModule
+  float scale;
+  float* dc;                     // (B, HW) out: the gradient at the clamp values
+  float *clq, *m2, *inv2, *dcq;  // chunk-local [B][qc] each
+};
+// launch_status labels of the five GEMMs, as each entry point reports them
+struct WalkNames {
+  const char *s, *dh, *dp, *df, *dg;
+};
+constexpr WalkNames kChunkNames{"gemm_f32_kernel(S_q=F_q^T G)", "gemm_f32_kernel(dH+=dO_q P_q)",
+                                "gemm_f32_kernel(dP_q=dO_q^T H)",
+                                "gemm_f32_kernel(dF_q=G dS_q^T)",
+                                "gemm_f32_kernel(dG+=F_q dS_q)"};
+
+static int attention_backward_walk(const float* F, const float* G, const float* H,
+                                   const float* dO, float* dF, float* dG, float* dH, int B, int C,
+                                   int HWc, int HWs, int qc, const WalkScratch& w,
+                                   const WalkAdaptive* ad, const WalkNames& nm, hipStream_t st) {
+  const int64_t fc = (int64_t)C * HWc, fs = (int64_t)C * HWs;
+  const Mat Gm{G, HWs, fs}, Hm{H, HWs, fs};
+  for (int q0 = 0; q0 < HWc; q0 += qc) {
+    const int n = std::min(qc, HWc - q0);
+    const int64_t sn = (int64_t)n * HWs, rows = (int64_t)B * n;
+    const unsigned rb = (unsigned)((rows + 255) / 256), wb = (unsigned)((rows + 3) / 4);
+    const Mat Fq{F + q0, HWc, fc}, dOq{dO + q0, HWc, fc}, Sq{w.S, HWs, sn}, dSq{w.dP, HWs, sn};
+    if (int e = logits_rowstats(Fq, n, Gm, w.S, w.rmax, w.rinv, B, C, nm.s, st)) return e;
+    RowVec rv{.m = w.rmax, .inv = w.rinv};
+    if (ad) {
+      rows_gather_kernel<<<rb, 256, 0, st>>>(ad->clamp, ad->clq, B, HWc, q0, n);
+      if (int e = launch_status("rows_gather_kernel")) return e;
+      if (ad->mode == 1) {
+        rowstats_relu_kernel<true><<<wb, 256, 0, st>>>(w.S, w.rmax, w.rinv, ad->clq, ad->m2,
+                                                       ad->inv2, rows, HWs);
+        if (int e = launch_status("rowstats_relu_kernel")) return e;
+      }
+      rv = {.m = w.rmax, .inv = w.rinv, .clamp = ad->clq, .m2 = ad->m2, .scale = ad->scale,
+            .inv2 = ad->inv2};
+    }
+    // dH += dO_q P_q (adaptive: Q_q), formed from S_q while staged (KR: its row is the k index)
+    const GemmReq gh{.A = dOq, .B = Sq, .C = {dH, HWs, fs}, .M = C, .N = HWs, .K = n, .rv = rv,
+                     .sV = n, .accum = q0 > 0};
+    if (!ad) launch_gemm<LAY_RK, LAY_KR, BX_PROB>(gh, B, st);
+    else if (ad->mode == 0) launch_gemm<LAY_RK, LAY_KR, BX_AEA>(gh, B, st);
+    else launch_gemm<LAY_RK, LAY_KR, BX_AEARQ>(gh, B, st);
+    if (int e = launch_status(nm.dh)) return e;
+    // dP_q = dO_q^T H (adaptive: dQ_q), then the row pass writes dS_q over it
+    launch_gemm<LAY_KR, LAY_KR, BX_NONE>({.A = dOq, .B = Hm, .C = {w.dP, HWs, sn}, .M = n,
+                                          .N = HWs, .K = C}, B, st);
+    if (int e = launch_status(nm.dp)) return e;
+    if (!ad) {
+      softmax_bwd_logits_kernel<<<wb, 256, 0, st>>>(w.S, w.rmax, w.rinv, w.dP, rows, HWs);
+      if (int e = launch_status("softmax_bwd_logits_kernel")) return e;
+    } else {
+      aea_bwd_rows_kernel<<<wb, 256, 0, st>>>(w.S, rv, w.dP, ad->dcq, ad->mode, rows, HWs);
+      if (int e = launch_status("aea_bwd_rows_kernel")) return e;
+      rows_scatter_kernel<<<rb, 256, 0, st>>>(ad->dcq, ad->dc, B, HWc, q0, n);
+      if (int e = launch_status("rows_scatter_kernel")) return e;
+    }
+    // dF_q = G dS_q^T
+    launch_gemm<LAY_RK, LAY_RK, BX_NONE>({.A = Gm, .B = dSq, .C = {dF + q0, HWc, fc}, .M = C,
+                                          .N = n, .K = HWs}, B, st);
+    if (int e = launch_status(nm.df)) return e;
+    // dG += F_q dS_q
+    launch_gemm<LAY_RK, LAY_KR, BX_NONE>({.A = Fq, .B = dSq, .C = {dG, HWs, fs}, .M = C,
+                                          .N = HWs, .K = n, .accum = q0 > 0}, B, st);
+    if (int e = launch_status(nm.dg)) return e;
+  }
+  return RPST_OK;
+}
+
+// S_q, dP_q and their two row vectors, in this order
+static WalkScratch sanet_walk_scratch(void* workspace, int B, int qc, int HWs) {
+  float* S = static_cast<float*>(workspace);
+  float* dP = S + (size_t)B * qc * HWs;
+  float* rmax = dP + (size_t)B * qc * HWs;
+  return {.S = S, .dP = dP, .rmax = rmax, .rinv = rmax + (size_t)B * qc};
 }
 
 extern "C" size_t rpst_sanet_attention_backward_workspace_size(int B, int HWc, int HWs) {
@@ -1057,65 +1144,18 @@ extern "C" int rpst_sanet_attention_backward(const float* F, const float* G, con
     set_error("sanet_attention_backward: workspace too small");
     return RPST_EWORKSPACE;
   }
-  hipStream_t st = as_stream(stream);
-  const int64_t ss = (int64_t)HWc * HWs, fc = (int64_t)C * HWc, fs = (int64_t)C * HWs;
-  float* S = static_cast<float*>(workspace);
-  float* dP = S + (size_t)B * ss;
-  float* rmax = dP + (size_t)B * ss;
-  float* rinv = rmax + (size_t)B * HWc;
-  // S = F^T G; row statistics of the softmax
-  GemmArgs g1{F, G, S, {}, nullptr, nullptr, 0, HWc, HWs, C, HWc, HWs, HWs, fc, fs, ss, 0};
-  launch_gemm<LAY_KR, LAY_KR, BX_NONE>(g1, B, st);
-  if (int e = launch_status("gemm_f32_kernel(S=F^T G)")) return e;
-  const int64_t rows = (int64_t)B * HWc;
-  rowstats_kernel<<<(unsigned)((rows + 3) / 4), 256, 0, st>>>(S, rmax, rinv, rows, HWs);
-  if (int e = launch_status("rowstats_kernel")) return e;
-  // dH = dO P: P formed from S while staged (KR: the row of P is the k index)
-  GemmArgs gh{dO, S, dH, {rmax, rinv, nullptr, nullptr, 0.f}, nullptr, nullptr, 0,
-              C, HWs, HWc, HWc, HWs, HWs, fc, ss, fs, HWc};
-  launch_gemm<LAY_RK, LAY_KR, BX_PROB>(gh, B, st);
-  if (int e = launch_status("gemm_f32_kernel(dH=dO P)")) return e;
-  // dP = dO^T H, then dS = P (dP - rowsum(dP P)) in place
-  GemmArgs gp{dO, H, dP, {}, nullptr, nullptr, 0, HWc, HWs, C, HWc, HWs, HWs, fc, fs, ss, 0};
-  launch_gemm<LAY_KR, LAY_KR, BX_NONE>(gp, B, st);
-  if (int e = launch_status("gemm_f32_kernel(dP=dO^T H)")) return e;
-  softmax_bwd_logits_kernel<<<(unsigned)((rows + 3) / 4), 256, 0, st>>>(S, rmax, rinv, dP, rows,
-                                                                        HWs);
-  if (int e = launch_status("softmax_bwd_logits_kernel")) return e;
-  // dF = G dS^T, dG = F dS
-  GemmArgs gf{G, dP, dF, {}, nullptr, nullptr, 0, C, HWc, HWs, HWs, HWs, HWc, fs, ss, fc, 0};
-  launch_gemm<LAY_RK, LAY_RK, BX_NONE>(gf, B, st);
-  if (int e = launch_status("gemm_f32_kernel(dF=G dS^T)")) return e;
-  GemmArgs gg{F, dP, dG, {}, nullptr, nullptr, 0, C, HWs, HWc, HWc, HWs, HWs, fc, ss, fs, 0};
-  launch_gemm<LAY_RK, LAY_KR, BX_NONE>(gg, B, st);
-  return launch_status("gemm_f32_kernel(dG=F dS)");
-}
-
-// ---- SANet attention backward over query chunks (no B x HW x HW workspace) -------------
-// The same gradients with S and dP formed for attn_qc() = 2048 queries (full rows) at a time:
-// per chunk S_q = F_q^T G, the row statistics, dH += dO_q P_q (P formed while S_q is staged),
-// dP_q = dO_q^T H, dS_q = P (dP - rowsum(dP P)) in place (softmax_bwd_logits_kernel: whole
-// rows, so every row of dS sums to zero to rounding as in the single pass), dF_q = G dS_q^T,
-// dG += F_q dS_q; dH and dG sum the chunks in order. S, its statistics and dS are the single
-// pass's bit for bit (the GEMM's k order does not depend on M); 10 HW^2 C FLOP per image like
-// the single pass. Workspace: S_q and dP_q (2 B qc HWs) + 2 B qc row vectors. (2048: the dF_q
-// GEMM's grid is C/256 x qc/128 tiles per image -- at 1024 queries, C = 512 and B = 8 only 128
-// workgroups, and the SAModel training step ran 2.8 % slower than the single pass; at 2048
-// 0.6 %, profiles/r05/attn_bwd_qc.log.)
-// (RPST_ATTN_QC overrides the chunk: A/B against the single pass, tests.)
-static int attn_qc() {
-  static const int qc = [] {
-    const char* e = std::getenv("RPST_ATTN_QC");
-    const int v = (e && *e) ? std::atoi(e) : 2048;
-    return v >= 16 ? v / 4 * 4 : 2048;
-  }();
-  return qc;
+  constexpr WalkNames names{"gemm_f32_kernel(S=F^T G)", "gemm_f32_kernel(dH=dO P)",
+                            "gemm_f32_kernel(dP=dO^T H)", "gemm_f32_kernel(dF=G dS^T)",
+                            "gemm_f32_kernel(dG=F dS)"};
+  return attention_backward_walk(F, G, H, dO, dF, dG, dH, B, C, HWc, HWs, HWc,
+                                 sanet_walk_scratch(workspace, B, HWc, HWs), nullptr, names,
+                                 as_stream(stream));
 }
 
 extern "C" size_t rpst_sanet_attention_backward_chunked_workspace_size(int B, int C, int HWc,
                                                                        int HWs) {
   if (B <= 0 || C <= 0 || HWc <= 0 || HWs <= 0) return 0;
-  const size_t qc = (size_t)std::min(HWc, attn_qc());
+  const size_t qc = (size_t)std::min(HWc, kAttnQC);
   return sizeof(float) * (2 * (size_t)B * qc * HWs + 2 * (size_t)B * qc);
 }
 
@@ -1134,41 +1174,10 @@ extern "C" int rpst_sanet_attention_backward_chunked(const float* F, const float
     set_error("sanet_attention_backward_chunked: workspace too small");
     return RPST_EWORKSPACE;
   }
-  hipStream_t st = as_stream(stream);
-  const int qc = std::min(HWc, attn_qc());
-  const int64_t fc = (int64_t)C * HWc, fs = (int64_t)C * HWs, sq = (int64_t)qc * HWs;
-  float* Sq = static_cast<float*>(workspace);
-  float* dPq = Sq + (size_t)B * sq;
-  float* rmax = dPq + (size_t)B * sq;
-  float* rinv = rmax + (size_t)B * qc;
-  for (int q0 = 0; q0 < HWc; q0 += qc) {
-    const int n = std::min(qc, HWc - q0);
-    const int64_t sn = (int64_t)n * HWs, rows = (int64_t)B * n;
-    GemmArgs g1{F + q0, G, Sq, {}, nullptr, nullptr, 0, n, HWs, C, HWc, HWs, HWs, fc, fs, sn, 0};
-    launch_gemm<LAY_KR, LAY_KR, BX_NONE>(g1, B, st);
-    if (int e = launch_status("gemm_f32_kernel(S_q=F_q^T G)")) return e;
-    rowstats_kernel<<<(unsigned)((rows + 3) / 4), 256, 0, st>>>(Sq, rmax, rinv, rows, HWs);
-    if (int e = launch_status("rowstats_kernel")) return e;
-    GemmArgs gh{dO + q0, Sq, dH, {rmax, rinv, nullptr, nullptr, 0.f}, nullptr, nullptr, 0,
-                C, HWs, n, HWc, HWs, HWs, fc, sn, fs, n};
-    gh.accum = q0 > 0;
-    launch_gemm<LAY_RK, LAY_KR, BX_PROB>(gh, B, st);
-    if (int e = launch_status("gemm_f32_kernel(dH+=dO_q P_q)")) return e;
-    GemmArgs gp{dO + q0, H, dPq, {}, nullptr, nullptr, 0, n, HWs, C, HWc, HWs, HWs, fc, fs, sn, 0};
-    launch_gemm<LAY_KR, LAY_KR, BX_NONE>(gp, B, st);
-    if (int e = launch_status("gemm_f32_kernel(dP_q=dO_q^T H)")) return e;
-    softmax_bwd_logits_kernel<<<(unsigned)((rows + 3) / 4), 256, 0, st>>>(Sq, rmax, rinv, dPq,
-                                                                          rows, HWs);
-    if (int e = launch_status("softmax_bwd_logits_kernel")) return e;
-    GemmArgs gf{G, dPq, dF + q0, {}, nullptr, nullptr, 0, C, n, HWs, HWs, HWs, HWc, fs, sn, fc, 0};
-    launch_gemm<LAY_RK, LAY_RK, BX_NONE>(gf, B, st);
-    if (int e = launch_status("gemm_f32_kernel(dF_q=G dS_q^T)")) return e;
-    GemmArgs gg{F + q0, dPq, dG, {}, nullptr, nullptr, 0, C, HWs, n, HWc, HWs, HWs, fc, sn, fs, 0};
-    gg.accum = q0 > 0;
-    launch_gemm<LAY_RK, LAY_KR, BX_NONE>(gg, B, st);
-    if (int e = launch_status("gemm_f32_kernel(dG+=F_q dS_q)")) return e;
-  }
-  return RPST_OK;
+  const int qc = std::min(HWc, kAttnQC);
+  return attention_backward_walk(F, G, H, dO, dF, dG, dH, B, C, HWc, HWs, qc,
+                                 sanet_walk_scratch(workspace, B, qc, HWs), nullptr, kChunkNames,
+                                 as_stream(stream));
 }
 
 // K (pixel) chunks per image of the 1x1 weight gradient: the per-image GEMM has only
@@ -1204,13 +1213,12 @@ extern "C" int rpst_conv1x1_wgrad(const float* x, const float* dy, float* dw, fl
   const int ksmax = wgrad1x1_ks(N, Cin, Cout);
   const int64_t kc = std::max<int64_t>(64, ((HW + ksmax - 1) / ksmax + 63) / 64 * 64);
   const int ks = (int)((HW + kc - 1) / kc);
-  GemmArgs g{dy, x, part, {}, nullptr, nullptr, 0, Cout, Cin, (int)HW, (int)HW, (int)HW, Cin,
-             (int64_t)Cout * HW, (int64_t)Cin * HW, (int64_t)Cout * Cin, 0, ks, (int)kc};
-  launch_gemm<LAY_RK, LAY_RK, BX_NONE>(g, N, st);
-  if (int e = launch_status("gemm_f32_kernel(dW=dY X^T)")) return e;
   const int64_t per = (int64_t)Cout * Cin;
-  batch_sum_kernel<<<(unsigned)((per + 255) / 256), 256, 0, st>>>(part, dw, per, N * ks);
-  if (int e = launch_status("batch_sum_kernel")) return e;
+  launch_gemm<LAY_RK, LAY_RK, BX_NONE>({.A = {dy, (int)HW, Cout * HW}, .B = {x, (int)HW, Cin * HW},
+                                        .C = {part, Cin, per}, .M = Cout, .N = Cin, .K = (int)HW,
+                                        .ks = ks, .kc = (int)kc}, N, st);
+  if (int e = launch_status("gemm_f32_kernel(dW=dY X^T)")) return e;
+  if (int e = partial_sum(part, dw, per, N * ks, 1, "partial_sum_kernel(dW)", st)) return e;
   if (db) {
     channel_sum_kernel<<<Cout, 256, 0, st>>>(dy, db, N, Cout, HW);
     return launch_status("channel_sum_kernel");
@@ -1221,7 +1229,7 @@ extern "C" int rpst_conv1x1_wgrad(const float* x, const float* dy, float* dw, fl
 extern "C" size_t rpst_adaptive_attention_backward_workspace_size(int B, int C, int HW,
                                                                   int hidden) {
   if (B <= 0 || C <= 0 || HW <= 0 || hidden <= 0) return 0;
-  const size_t qc = (size_t)std::min(HW, attn_qc());
+  const size_t qc = (size_t)std::min(HW, kAttnQC);
   const size_t chunks = ((size_t)B * HW + kColChunk - 1) / kColChunk;
   // (the first region holds T and then R, C x hidden per image, never the affinity) + S and
   // dQ of one query chunk + the per-image dW1 partials and the column-sum chunk partials
@@ -1251,7 +1259,7 @@ extern "C" int rpst_adaptive_attention_backward(
     return RPST_EWORKSPACE;
   }
   hipStream_t st = as_stream(stream);
-  const int qc = std::min(HW, attn_qc());
+  const int qc = std::min(HW, kAttnQC);
   const int64_t fhw = (int64_t)C * HW, rows = (int64_t)B * HW, sq = (int64_t)qc * HW;
   float* Aff = static_cast<float*>(workspace);  // T, then R (C x hidden per image)
   float* Sq = Aff + clamp_t_floats(B, C, HW, hidden);  // S and dQ of one query chunk
@@ -1277,45 +1285,17 @@ extern "C" int rpst_adaptive_attention_backward(
   if (int e = clamp_values_factored(cn, sn, w1, b1, w2, b2, hidden, mode, from, interval, Aff,
                                     Z, clamp, B, C, HW, st))
     return e;
-  // attention part over query chunks of whole rows (as rpst_sanet_attention_backward_chunked):
-  // S_q, its softmax / relu-softmax statistics, dH += dO_q Q_q, dQ_q = dO_q^T H -> dS_q and
-  // dc (aea_bwd_rows_kernel on whole rows), dF_q = G dS_q^T, dG += F_q dS_q
-  for (int q0 = 0; q0 < HW; q0 += qc) {
-    const int n = std::min(qc, HW - q0);
-    const int64_t sn_ = (int64_t)n * HW, rq = (int64_t)B * n;
-    const unsigned rb = (unsigned)((rq + 255) / 256), wb = (unsigned)((rq + 3) / 4);
-    GemmArgs g1{F + q0, G, Sq, {}, nullptr, nullptr, 0, n, HW, C, HW, HW, HW, fhw, fhw, sn_, 0};
-    launch_gemm<LAY_KR, LAY_KR, BX_NONE>(g1, B, st);
-    if (int e = launch_status("gemm_f32_kernel(S_q=F_q^T G)")) return e;
-    rowstats_kernel<<<wb, 256, 0, st>>>(Sq, rmax, rinv, rq, HW);
-    if (int e = launch_status("rowstats_kernel")) return e;
-    rows_gather_kernel<<<rb, 256, 0, st>>>(clamp, clq, B, HW, q0, n);
-    if (int e = launch_status("rows_gather_kernel")) return e;
-    if (mode == 1) {
-      rowstats_relu_kernel<<<wb, 256, 0, st>>>(Sq, rmax, rinv, clq, m2, inv2, rq, HW);
-      if (int e = launch_status("rowstats_relu_kernel")) return e;
-    }
-    RowVec rv{rmax, rinv, clq, m2, scale, inv2};
-    GemmArgs gh{dO + q0, Sq, dH, rv, nullptr, nullptr, 0, C, HW, n, HW, HW, HW, fhw, sn_, fhw, n};
-    gh.accum = q0 > 0;
-    if (mode == 0) launch_gemm<LAY_RK, LAY_KR, BX_AEA>(gh, B, st);
-    else launch_gemm<LAY_RK, LAY_KR, BX_AEARQ>(gh, B, st);
-    if (int e = launch_status("gemm_f32_kernel(dH+=dO_q Q_q)")) return e;
-    GemmArgs gq{dO + q0, H, dQq, {}, nullptr, nullptr, 0, n, HW, C, HW, HW, HW, fhw, fhw, sn_, 0};
-    launch_gemm<LAY_KR, LAY_KR, BX_NONE>(gq, B, st);
-    if (int e = launch_status("gemm_f32_kernel(dQ_q=dO_q^T H)")) return e;
-    aea_bwd_rows_kernel<<<wb, 256, 0, st>>>(Sq, rv, dQq, dcq, mode, rq, HW);
-    if (int e = launch_status("aea_bwd_rows_kernel")) return e;
-    rows_scatter_kernel<<<rb, 256, 0, st>>>(dcq, dc, B, HW, q0, n);
-    if (int e = launch_status("rows_scatter_kernel")) return e;
-    GemmArgs gf{G, dQq, dF + q0, {}, nullptr, nullptr, 0, C, n, HW, HW, HW, HW, fhw, sn_, fhw, 0};
-    launch_gemm<LAY_RK, LAY_RK, BX_NONE>(gf, B, st);
-    if (int e = launch_status("gemm_f32_kernel(dF_q=G dS_q^T)")) return e;
-    GemmArgs gg{F + q0, dQq, dG, {}, nullptr, nullptr, 0, C, HW, n, HW, HW, HW, fhw, sn_, fhw, 0};
-    gg.accum = q0 > 0;
-    launch_gemm<LAY_RK, LAY_KR, BX_NONE>(gg, B, st);
-    if (int e = launch_status("gemm_f32_kernel(dG+=F_q dS_q)")) return e;
-  }
+  // attention part over query chunks of whole rows: S_q, its softmax / relu-softmax
+  // statistics, dH += dO_q Q_q, dQ_q = dO_q^T H -> dS_q and dc, dF_q = G dS_q^T, dG += F_q dS_q
+  const WalkAdaptive ad{.clamp = clamp, .mode = mode, .scale = scale, .dc = dc, .clq = clq,
+                        .m2 = m2, .inv2 = inv2, .dcq = dcq};
+  WalkNames names = kChunkNames;
+  names.dh = "gemm_f32_kernel(dH+=dO_q Q_q)";
+  names.dp = "gemm_f32_kernel(dQ_q=dO_q^T H)";
+  if (int e = attention_backward_walk(F, G, H, dO, dF, dG, dH, B, C, HW, HW, qc,
+                                      {.S = Sq, .dP = dQq, .rmax = rmax, .rinv = rinv}, &ad,
+                                      names, st))
+    return e;
   // f_psi: dt, du, then dW1 = du^T Aff over all B * HW query rows (one GEMM), the column sums
   fpsi_bwd_rows_kernel<<<(unsigned)((rows + 3) / 4), 256, 0, st>>>(Z, w2, b2, dc, dt, du, rows,
                                                                    hidden, mode, interval);
@@ -1323,17 +1303,18 @@ extern "C" int rpst_adaptive_attention_backward(
   // dW1 = du^T A per image with A = cn^T sn never formed: R = cn du (C x hidden, K = HW),
   // then dW1_b = R^T sn (K = C), then the B partials summed in order
   float* R = Aff;
-  GemmArgs gr{cn, du, R, {}, nullptr, nullptr, 0, C, hidden, HW, HW, hidden, hidden,
-              fhw, (int64_t)HW * hidden, (int64_t)C * hidden, 0};
-  launch_gemm<LAY_RK, LAY_KR, BX_NONE>(gr, B, st);
+  const int64_t nr = (int64_t)C * hidden, nw1 = (int64_t)hidden * HW;
+  // R[b][c][n] = sum_i cn[b][c][i] du[b][i][n]
+  launch_gemm<LAY_RK, LAY_KR, BX_NONE>({.A = {cn, HW, fhw}, .B = {du, hidden, nw1},
+                                        .C = {R, hidden, nr}, .M = C, .N = hidden, .K = HW}, B,
+                                       st);
   if (int e = launch_status("gemm_f32_kernel(R_b=cn_b du_b)")) return e;
-  GemmArgs gw{R, sn, w1part, {}, nullptr, nullptr, 0, hidden, HW, C, hidden, HW, HW,
-              (int64_t)C * hidden, fhw, (int64_t)hidden * HW, 0};
-  launch_gemm<LAY_KR, LAY_KR, BX_NONE>(gw, B, st);
+  // w1part[b][n][j] = sum_c R[b][c][n] sn[b][c][j]
+  launch_gemm<LAY_KR, LAY_KR, BX_NONE>({.A = {R, hidden, nr}, .B = {sn, HW, fhw},
+                                        .C = {w1part, HW, nw1}, .M = hidden, .N = HW, .K = C}, B,
+                                       st);
   if (int e = launch_status("gemm_f32_kernel(dW1_b=R_b^T sn_b)")) return e;
-  const int64_t nw1 = (int64_t)hidden * HW;
-  batch_sum_kernel<<<(unsigned)((nw1 + 255) / 256), 256, 0, st>>>(w1part, dw1, nw1, B);
-  if (int e = launch_status("batch_sum_kernel(dW1)")) return e;
+  if (int e = partial_sum(w1part, dw1, nw1, B, 1, "partial_sum_kernel(dW1)", st)) return e;
   const int chunks = (int)((rows + kColChunk - 1) / kColChunk);
   fpsi_colsum_part_kernel<<<dim3((unsigned)((hidden + 1 + 255) / 256), (unsigned)chunks), 256, 0,
                             st>>>(Z, du, dt, cpart, rows, hidden);

@@ -5,6 +5,7 @@
 // accvgpr moves and pinned the whole VGPR file, so the LDS operand reads could not be
 // issued ahead of the MFMAs that use them).
 #include <cstdlib>
+#include <cstring>
 
 #include "rpst_common.h"
 
@@ -99,7 +100,7 @@ struct AttnRows {
   float* out_inv;
 };
 
-template <int C, bool PIPE, int AM = AM_SOFTMAX>
+template <int C, int AM>
 __global__ __launch_bounds__(256, 1) void sanet_flash_kernel(const float* __restrict__ F,
                                                              const float* __restrict__ G,
                                                              const float* __restrict__ H,
@@ -151,19 +152,13 @@ __global__ __launch_bounds__(256, 1) void sanet_flash_kernel(const float* __rest
     }
   };
   static_assert(NQ / 8 == 2 * PPW, "one DMA piece per MFMA group of scores()");
+  // the prologue's G(0), all pieces at once (as PPW calls of piece the kernel compiles to
+  // other code: profiles/attn_refactor/device_asm.log)
   auto issue_g = [&](int k0, float* gs) {
 #pragma unroll
     for (int jj = 0; jj < PPW; ++jj) {
       const int j = wave * PPW + jj;
       __builtin_amdgcn_raw_ptr_buffer_load_lds(rG, (attn_lds_ptr_t)(gs + 256 * j), 16, (int)(voffG + (unsigned)(16 * j * HW + k0) * 4u), 0,
-                                               0, 0);
-    }
-  };
-  auto issue_h = [&](int k0, float* hs) {
-#pragma unroll
-    for (int jj = 0; jj < PPW; ++jj) {
-      const int j = wave * PPW + jj;
-      __builtin_amdgcn_raw_ptr_buffer_load_lds(rH, (attn_lds_ptr_t)(hs + 256 * j), 16, (int)(voffH + (unsigned)(16 * j * HW + k0) * 4u), 0,
                                                0, 0);
     }
   };
@@ -304,42 +299,26 @@ __global__ __launch_bounds__(256, 1) void sanet_flash_kernel(const float* __rest
     }
   };
   constexpr bool useH = AM != AM_STATS;
-  if constexpr (!PIPE) {
-    if (useH) issue_h(0, Hs0);
-    auto step = [&](int kb, const float* gs, const float* hs, float* gn, float* hn) {
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // this block's key tile kb has landed
-      __builtin_amdgcn_s_barrier();                     // ... for every wave; the other
-      // (the other buffers are free: step kb - 1 is done everywhere)
-      const int k1 = kb + 1 < nk ? (kb + 1) * kFBN : -1;
-      softmax(kb, scores(kb, gs, [&](int t) { piece(t, k1, gn, useH ? k1 : -1, hn); }));
-      update(hs);
-    };
-    for (int kb = 0; kb < nk; kb += 2) {
-      step(kb, Gs0, Hs0, Gs1, Hs1);
-      if (kb + 1 < nk) step(kb + 1, Gs1, Hs1, Gs0, Hs0);
+  // software pipeline over key blocks: iteration kb computes S(kb), then the O update of
+  // block kb - 1 (whose P is in registers), then the softmax of kb, so the softmax's
+  // shuffle / exp latency sits behind the update's MFMAs. H lags G by one block: H(kb) is
+  // loaded in iteration kb into the buffer of H(kb - 2) and consumed in iteration kb + 1.
+  auto step = [&](int kb, const float* gs, const float* hprev, float* gn, float* hcur) {
+    if (!(RPST_FLDBG & 2)) {
+      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // G(kb), H(kb - 1) have landed
+      __builtin_amdgcn_s_barrier();
     }
-  } else {
-    // software pipeline over key blocks: iteration kb computes S(kb), then the O update of
-    // block kb - 1 (whose P is in registers), then the softmax of kb, so the softmax's
-    // shuffle / exp latency sits behind the update's MFMAs. H lags G by one block: H(kb) is
-    // loaded in iteration kb into the buffer of H(kb - 2) and consumed in iteration kb + 1.
-    auto step = [&](int kb, const float* gs, const float* hprev, float* gn, float* hcur) {
-      if (!(RPST_FLDBG & 2)) {
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // G(kb), H(kb - 1) have landed
-        __builtin_amdgcn_s_barrier();
-      }
-      const int kg = kb + 1 < nk ? (kb + 1) * kFBN : -1,
-                kh = useH && kb < nk ? kb * kFBN : -1;
-      floatx4 sc = {0.f, 0.f, 0.f, 0.f};
-      if (kb < nk) sc = scores(kb, gs, [&](int t) { piece(t, kg, gn, kh, hcur); });
-      // (the last iteration has no scores and no DMA left: kg, kh < 0)
-      if (kb >= 1) update(hprev);
-      if (kb < nk) softmax(kb, sc);
-    };
-    for (int kb = 0; kb <= nk; kb += 2) {
-      step(kb, Gs0, Hs1, Gs1, Hs0);
-      if (kb + 1 <= nk) step(kb + 1, Gs1, Hs0, Gs0, Hs1);
-    }
+    const int kg = kb + 1 < nk ? (kb + 1) * kFBN : -1,
+              kh = useH && kb < nk ? kb * kFBN : -1;
+    floatx4 sc = {0.f, 0.f, 0.f, 0.f};
+    if (kb < nk) sc = scores(kb, gs, [&](int t) { piece(t, kg, gn, kh, hcur); });
+    // (the last iteration has no scores and no DMA left: kg, kh < 0)
+    if (kb >= 1) update(hprev);
+    if (kb < nk) softmax(kb, sc);
+  };
+  for (int kb = 0; kb <= nk; kb += 2) {
+    step(kb, Gs0, Hs1, Gs1, Hs0);
+    if (kb + 1 <= nk) step(kb + 1, Gs1, Hs0, Gs0, Hs1);
   }
   // the row sum over the four lane groups holding a query's keys; O / l
   if constexpr (AM != AM_AEA) l_run = rows4_sum(l_run);
@@ -360,215 +339,60 @@ __global__ __launch_bounds__(256, 1) void sanet_flash_kernel(const float* __rest
   }
 }
 
-// 8-wave form (two waves per SIMD): waves w and w + 4 own the same 16 queries and split the
-// channels, wave w + 4 c in [C/2, C): each computes the partial S^T over its channel half (its Q
-// half in registers, C / 8 per lane), the halves are exchanged through LDS (one barrier) and
-// summed in the same order by both, so both run the identical online softmax; then each
-// accumulates O for its own channel half (C / 8 accumulator registers per lane). Twice the
-// waves of sanet_flash_kernel at half the registers: a SIMD's two waves hide each other's LDS
-// and softmax latency. RPST_SANET_FLASH=2 selects it.
-template <int C>
-__global__ __launch_bounds__(512, 1) void sanet_flash8_kernel(const float* __restrict__ F,
-                                                              const float* __restrict__ G,
-                                                              const float* __restrict__ H,
-                                                              float* __restrict__ O, int HW,
-                                                              int qblocks) {
-  constexpr int CH = C / 2;            // channels per wave
-  constexpr int NQ = CH / 4;           // Q registers per lane
-  constexpr int NMB = CH / 16;         // O accumulators
-  constexpr int TILE = C * kFBN;
-  constexpr int PPW = TILE / 256 / 8;  // DMA pieces per wave per tile
-  static_assert(PPW >= 1 && TILE % 2048 == 0, "C in {128, 256, 512}");
-  __shared__ __attribute__((aligned(16))) float Gs0[TILE];
-  __shared__ __attribute__((aligned(16))) float Gs1[TILE];
-  __shared__ __attribute__((aligned(16))) float Hs0[TILE];
-  __shared__ __attribute__((aligned(16))) float Hs1[TILE];
-  __shared__ __attribute__((aligned(16))) float xs[8 * 64 * 4];  // partial S^T exchange
-
-  const int bid = attn_xcd_swizzle(blockIdx.x, (int)gridDim.x);
-  const int b = bid / qblocks, qb = bid - b * qblocks;
-  const int tid = threadIdx.x, lane = tid & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int qw = wave & 3, half = wave >> 2;
-  const int g = lane >> 4, lq = lane & 15;
-  const int q = qb * kFBM + qw * 16 + lq;
-  const int c0 = half * CH;
-  const int64_t plane = (int64_t)C * HW;
-  const float* Fb = F + b * plane;
-  const unsigned bytes = (unsigned)(plane * 4);
-  const auto rG = __builtin_amdgcn_make_buffer_rsrc((void*)(G + b * plane), (short)0, (int)bytes, 0x00020000);
-  const auto rH = __builtin_amdgcn_make_buffer_rsrc((void*)(H + b * plane), (short)0, (int)bytes, 0x00020000);
-  const int prow = lane >> 2, pseg = lane & 3;
-  const unsigned voffG = (unsigned)(prow * HW + 4 * pseg) * 4u;
-  const unsigned voffH = (unsigned)(prow * HW + 4 * (pseg ^ ((lane >> 4) & 3))) * 4u;
-  auto issue = [&](int k0, float* gs, float* hs) {
-#pragma unroll
-    for (int jj = 0; jj < PPW; ++jj) {
-      const int j = wave * PPW + jj;
-      const unsigned so = (unsigned)(16 * j * HW + k0) * 4u;
-      __builtin_amdgcn_raw_ptr_buffer_load_lds(rG, (attn_lds_ptr_t)(gs + 256 * j), 16, (int)(voffG + so), 0, 0, 0);
-      __builtin_amdgcn_raw_ptr_buffer_load_lds(rH, (attn_lds_ptr_t)(hs + 256 * j), 16, (int)(voffH + so), 0, 0, 0);
-    }
-  };
-  const int nk = (HW + kFBN - 1) / kFBN;
-  issue(0, Gs0, Hs0);
-
-  float qv[NQ];
-#pragma unroll
-  for (int s = 0; s < NQ; ++s) qv[s] = q < HW ? Fb[(int64_t)(c0 + 4 * s + g) * HW + q] : 0.f;
-  floatx4 acc[NMB];
-#pragma unroll
-  for (int mb = 0; mb < NMB; ++mb) acc[mb] = floatx4{0.f, 0.f, 0.f, 0.f};
-  float m_run = -INFINITY, l_run = 0.f;
-  const int hsw = 4 * (g ^ ((lq >> 2) & 3));
-  float* xmine = xs + (wave * 64 + lane) * 4;
-  const float* xpart = xs + ((wave ^ 4) * 64 + lane) * 4;
-
-  auto step = [&](int kb, const float* gs, const float* hs, float* gn, float* hn) {
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __builtin_amdgcn_s_barrier();
-    if (kb + 1 < nk) issue((kb + 1) * kFBN, gn, hn);
-    floatx4 s0 = {0.f, 0.f, 0.f, 0.f}, s1 = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-    for (int s = 0; s < NQ; s += 2) {
-      const float a0 = gs[(c0 + 4 * s + g) * kFBN + lq];
-      const float a1 = gs[(c0 + 4 * s + 4 + g) * kFBN + lq];
-      s0 = __builtin_amdgcn_mfma_f32_16x16x4f32(a0, qv[s], s0, 0, 0, 0);
-      s1 = __builtin_amdgcn_mfma_f32_16x16x4f32(a1, qv[s + 1], s1, 0, 0, 0);
-    }
-    const floatx4 mine = s0 + s1;
-    *reinterpret_cast<floatx4*>(xmine) = mine;
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_s_barrier();
-    const floatx4 other = *reinterpret_cast<const floatx4*>(xpart);
-    // the same sum in both waves: channel half 0's partial first
-    const floatx4 sf = half == 0 ? mine + other : other + mine;
-    const int kbase = kb * kFBN + 4 * g;
-    float sv[4], mx = -INFINITY;
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      sv[r] = kbase + r < HW ? sf[r] : -INFINITY;
-      mx = fmaxf(mx, sv[r]);
-    }
-    mx = fmaxf(mx, __shfl_xor(mx, 16, 64));
-    mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
-    const float m_new = fmaxf(m_run, mx);
-    const float alpha = m_run == -INFINITY ? 0.f : expf(m_run - m_new);
-    float p[4], ps = 0.f;
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      p[r] = expf(sv[r] - m_new);
-      ps += p[r];
-    }
-    l_run = fmaf(l_run, alpha, ps);
-    m_run = m_new;
-    if (__builtin_amdgcn_ballot_w64(alpha != 1.f)) {
-#pragma unroll
-      for (int mb = 0; mb < NMB; ++mb) acc[mb] *= alpha;
-    }
-#pragma unroll
-    for (int mb = 0; mb < NMB; ++mb) {
-      const float4 h4 = *reinterpret_cast<const float4*>(hs + (c0 + 16 * mb + lq) * kFBN + hsw);
-      acc[mb] = __builtin_amdgcn_mfma_f32_16x16x4f32(h4.x, p[0], acc[mb], 0, 0, 0);
-      acc[mb] = __builtin_amdgcn_mfma_f32_16x16x4f32(h4.y, p[1], acc[mb], 0, 0, 0);
-      acc[mb] = __builtin_amdgcn_mfma_f32_16x16x4f32(h4.z, p[2], acc[mb], 0, 0, 0);
-      acc[mb] = __builtin_amdgcn_mfma_f32_16x16x4f32(h4.w, p[3], acc[mb], 0, 0, 0);
-    }
-  };
-  for (int kb = 0; kb < nk; kb += 2) {
-    step(kb, Gs0, Hs0, Gs1, Hs1);
-    if (kb + 1 < nk) step(kb + 1, Gs1, Hs1, Gs0, Hs0);
-  }
-  l_run += __shfl_xor(l_run, 16, 64);
-  l_run += __shfl_xor(l_run, 32, 64);
-  if (q < HW) {
-    const float inv = 1.f / l_run;
-    float* Ob = O + b * plane + q;
-#pragma unroll
-    for (int mb = 0; mb < NMB; ++mb)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) Ob[(int64_t)(c0 + 16 * mb + 4 * g + r) * HW] = acc[mb][r] * inv;
-  }
-}
-
-// flash path (RPST_SANET_FLASH=0: the two-GEMM path with S in the workspace, A/B)
-static int sanet_flash_mode() {
-  static const int on = [] {
+// RPST_SANET_FLASH=0 takes the two-GEMM path with S in the workspace instead (the A/B of the
+// two paths at the workload shape); any other value, or none, the flash kernel
+static bool sanet_flash_on() {
+  static const bool on = [] {
     const char* e = std::getenv("RPST_SANET_FLASH");
-    return (e && *e) ? std::atoi(e) : 1;
+    return !(e && std::strcmp(e, "0") == 0);
   }();
   return on;
 }
 bool sanet_flash_ok(int C, int HW) {
-  return sanet_flash_mode() != 0 && (C == 64 || C == 128 || C == 256 || C == 512) &&
-         HW % 4 == 0 && (int64_t)C * HW * 4 < (1LL << 31);
+  return sanet_flash_on() && (C == 64 || C == 128 || C == 256 || C == 512) && HW % 4 == 0 &&
+         (int64_t)C * HW * 4 < (1LL << 31);
 }
 
-int sanet_flash(const float* F, const float* G, const float* H, float* O, int B, int C,
-                       int HW, hipStream_t st) {
+// One workgroup per (image, 64 queries) of sanet_flash_kernel<C, AM>.
+template <int AM>
+static int flash_launch(const float* F, const float* G, const float* H, float* O, int B, int C,
+                        int HW, const AttnRows& rows, hipStream_t st) {
   const int qblocks = (HW + kFBM - 1) / kFBM;
   const int64_t nb = (int64_t)B * qblocks;
-  RPST_REQUIRE(nb <= 0x7fffffffLL, "sanet_attention: grid too large");
-  if (sanet_flash_mode() == 2 && C >= 128) {
-    switch (C) {
-      case 128: sanet_flash8_kernel<128><<<(unsigned)nb, 512, 0, st>>>(F, G, H, O, HW, qblocks); break;
-      case 256: sanet_flash8_kernel<256><<<(unsigned)nb, 512, 0, st>>>(F, G, H, O, HW, qblocks); break;
-      default: sanet_flash8_kernel<512><<<(unsigned)nb, 512, 0, st>>>(F, G, H, O, HW, qblocks); break;
-    }
-    return launch_status("sanet_flash8_kernel");
+  RPST_REQUIRE(nb <= 0x7fffffffLL, "%s: grid too large",
+               AM == AM_SOFTMAX ? "sanet_attention" : "adaptive_attention");
+  const unsigned grid = (unsigned)nb;
+  switch (C) {
+    case 64: sanet_flash_kernel<64, AM><<<grid, 256, 0, st>>>(F, G, H, O, HW, qblocks, rows); break;
+    case 128: sanet_flash_kernel<128, AM><<<grid, 256, 0, st>>>(F, G, H, O, HW, qblocks, rows); break;
+    case 256: sanet_flash_kernel<256, AM><<<grid, 256, 0, st>>>(F, G, H, O, HW, qblocks, rows); break;
+    default: sanet_flash_kernel<512, AM><<<grid, 256, 0, st>>>(F, G, H, O, HW, qblocks, rows); break;
   }
-#define RPST_FLASH_GO(P)                                                                      \
-  switch (C) {                                                                                \
-    case 64: sanet_flash_kernel<64, P><<<(unsigned)nb, 256, 0, st>>>(F, G, H, O, HW, qblocks, {}); break;   \
-    case 128: sanet_flash_kernel<128, P><<<(unsigned)nb, 256, 0, st>>>(F, G, H, O, HW, qblocks, {}); break; \
-    case 256: sanet_flash_kernel<256, P><<<(unsigned)nb, 256, 0, st>>>(F, G, H, O, HW, qblocks, {}); break; \
-    default: sanet_flash_kernel<512, P><<<(unsigned)nb, 256, 0, st>>>(F, G, H, O, HW, qblocks, {}); break;  \
-  }
-  if (sanet_flash_mode() == 3) RPST_FLASH_GO(false)
-  else RPST_FLASH_GO(true)
-#undef RPST_FLASH_GO
-  return launch_status("sanet_flash_kernel");
+  return launch_status(AM == AM_SOFTMAX ? "sanet_flash_kernel"
+                       : AM == AM_STATS ? "sanet_flash_kernel(stats)"
+                                        : "sanet_flash_kernel(adaptive)");
+}
+
+int sanet_flash(const float* F, const float* G, const float* H, float* O, int B, int C, int HW,
+                hipStream_t st) {
+  return flash_launch<AM_SOFTMAX>(F, G, H, O, B, C, HW, {}, st);
 }
 
 // AdaptiveSANet attention without S (sanet.py:100-124): pass 1 writes each query's softmax
 // statistics (rm, rinv: B x HW each), pass 2 recomputes S per key block and accumulates
 // O = H Q^T with the clamp applied in registers. mode 0 = AEAModule, 1 = AEALReluModule.
-template <int AM>
-static void adaptive_flash_launch(int C, unsigned nb, hipStream_t st, const float* F,
-                                  const float* G, const float* H, float* O, int HW, int qblocks,
-                                  const AttnRows& rows) {
-  switch (C) {
-    case 64: sanet_flash_kernel<64, true, AM><<<nb, 256, 0, st>>>(F, G, H, O, HW, qblocks, rows); break;
-    case 128: sanet_flash_kernel<128, true, AM><<<nb, 256, 0, st>>>(F, G, H, O, HW, qblocks, rows); break;
-    case 256: sanet_flash_kernel<256, true, AM><<<nb, 256, 0, st>>>(F, G, H, O, HW, qblocks, rows); break;
-    default: sanet_flash_kernel<512, true, AM><<<nb, 256, 0, st>>>(F, G, H, O, HW, qblocks, rows); break;
-  }
-}
-
 int adaptive_flash_stats(const float* F, const float* G, int B, int C, int HW, float* rm,
                          float* rinv, hipStream_t st) {
-  const int qblocks = (HW + kFBM - 1) / kFBM;
-  const int64_t nb = (int64_t)B * qblocks;
-  RPST_REQUIRE(nb <= 0x7fffffffLL, "adaptive_attention: grid too large");
-  AttnRows rows{};
-  rows.out_m = rm;
-  rows.out_inv = rinv;
-  adaptive_flash_launch<AM_STATS>(C, (unsigned)nb, st, F, G, nullptr, nullptr, HW, qblocks, rows);
-  return launch_status("sanet_flash_kernel(stats)");
+  return flash_launch<AM_STATS>(F, G, nullptr, nullptr, B, C, HW, {.out_m = rm, .out_inv = rinv},
+                                st);
 }
 
 int adaptive_flash_apply(const float* F, const float* G, const float* H, float* O, int B, int C,
                          int HW, const float* rm, const float* rinv, const float* clamp, int mode,
                          float scale, hipStream_t st) {
-  const int qblocks = (HW + kFBM - 1) / kFBM;
-  const int64_t nb = (int64_t)B * qblocks;
-  RPST_REQUIRE(nb <= 0x7fffffffLL, "adaptive_attention: grid too large");
-  const AttnRows rows{rm, rinv, clamp, scale, nullptr, nullptr};
-  if (mode == 0)
-    adaptive_flash_launch<AM_AEA>(C, (unsigned)nb, st, F, G, H, O, HW, qblocks, rows);
-  else
-    adaptive_flash_launch<AM_AEAR>(C, (unsigned)nb, st, F, G, H, O, HW, qblocks, rows);
-  return launch_status("sanet_flash_kernel(adaptive)");
+  const AttnRows rows{.m = rm, .inv = rinv, .c = clamp, .scale = scale};
+  return mode == 0 ? flash_launch<AM_AEA>(F, G, H, O, B, C, HW, rows, st)
+                   : flash_launch<AM_AEAR>(F, G, H, O, B, C, HW, rows, st);
 }
 
 }  // namespace rpst

@@ -3,7 +3,8 @@ training path of sanet.py:82-99 under autograd): dF, dG, dH 
 float64 torch autograd of O = H softmax(F^T G)^T, with a ragged last query chunk (HW = 2400
 = 2048 + 352), two chunks at C = 512 (HW = 4096), HWc != HWs (1200 queries, 2100 keys) and
 one chunk (HW = 600). Tolerance rel-L2 1e-5 (fp32 vs fp64, logits of moderate spread).
-The workspace has no B x HW x HW term."""
+The workspace has no B x HW x HW term. The single pass (rpst_sanet_attention_backward, S and
+dP whole) is the same walk with one chunk: checked against the chunked entry bit for bit."""
 import pytest
 import torch
 
@@ -47,6 +48,45 @@ def test_sanet_attention_backward_chunked(cuda, shape):
     # (fp64: ~1e-16; fp32 rounding of the 4096-term sums reads ~1e-5 of max|dG|)
     gsum = dG.double().sum(-1).abs().max() / dG.double().abs().max()
     assert gsum < 5e-5, float(gsum)
+
+
+@pytest.mark.parametrize("shape", [(1, 16, 2100, 68), (2, 48, 72, 100)])
+def test_sanet_attention_backward_single_pass(cuda, shape):
+    """rpst_sanet_attention_backward (S and dP whole) against the chunked entry and float64
+    autograd. (1, 16, 2100, 68) crosses the 2048-query seam (2048 + 52 queries) with a tiny S;
+    (2, 48, 72, 100) is one chunk with C, HWc and HWs all ragged against the 128 x 128 x 32
+    tile. dF is bit-equal between the two on both shapes: each dF column's sums run over the
+    keys only, in the same order, and dS does not depend on the chunk. dG and dH sum over the
+    queries, so they are bit-equal only where there is one chunk. Tolerance rel-L2 1e-5 as
+    above (torch fp32 against float64 reads 2.7e-7 to 4.4e-7 on these gradients on a CPU)."""
+    from rpst import _lib, ops
+    B, C, hw, hws = shape
+    g = torch.Generator(device=cuda).manual_seed(3)
+    F = torch.randn((B, C, hw), device=cuda, generator=g) * (2.0 / C ** 0.5)
+    G = torch.randn((B, C, hws), device=cuda, generator=g)
+    H = torch.randn((B, C, hws), device=cuda, generator=g)
+    dO = torch.randn((B, C, hw), device=cuda, generator=g)
+    refs = _ref_grads(F, G, H, dO)[1:]
+    lib = _lib.load()
+    single = lib.rpst_sanet_attention_backward_workspace_size(B, hw, hws)
+    assert single == 4 * (2 * B * hw * hws + 2 * B * hw), single
+    chunked = lib.rpst_sanet_attention_backward_chunked_workspace_size(B, C, hw, hws)
+    got = {}
+    for fn, nbytes in (("rpst_sanet_attention_backward", single),
+                       ("rpst_sanet_attention_backward_chunked", chunked)):
+        ws = torch.empty(nbytes, device=cuda, dtype=torch.uint8)
+        got[fn] = tuple(torch.empty_like(x) for x in (F, G, H))
+        _lib.call(fn, F.data_ptr(), G.data_ptr(), H.data_ptr(), dO.data_ptr(),
+                  *(x.data_ptr() for x in got[fn]), B, C, hw, hws, ws.data_ptr(), nbytes,
+                  ops._stream(F))
+        for x, ref, name in zip(got[fn], refs, ("dF", "dG", "dH")):
+            print(fn, shape, name, rel_l2(x, ref))
+            assert rel_l2(x, ref) < 1e-5, (fn, name, rel_l2(x, ref))
+    one, many = got.values()
+    assert torch.equal(one[0], many[0]), "dF"
+    if hw <= 2048:
+        assert torch.equal(one[1], many[1]), "dG"
+        assert torch.equal(one[2], many[2]), "dH"
 
 
 @pytest.mark.parametrize("mode", ("aea", "relu"))
