@@ -79,6 +79,36 @@ int rpst_mean_variance_norm(const float* feat, float* out, int N, int C, int64_t
                             float eps, void* workspace, size_t workspace_bytes,
                             rpst_stream_t stream);
 
+/* ---- a2m: adaptive_instance_normalization_with_segment  network/base.py:421-530 ----
+ * AdaIN per segmentation label (`use_mask: True`, inference only). Label maps are uint8
+ * (N, HW), already resized to the feature size; each image uses its own pair of maps.
+ *
+ * rpst_segment_plan: per image, counts of every label in both maps and the validity rule of
+ * compute_label_info (base.py:433-438): valid iff c > 10 and s > 10 and c/s < 100 and
+ * s/c < 100. plan is int32 [N][256][4] = (content count, style count, valid flag, 0) per
+ * label. It depends on the maps only, so one plan serves every feature level of that size.
+ *
+ * rpst_masked_adain_params: params is fp32 [N][C][256][4] = (mean_c, std_c, std_s, mean_s)
+ * per (image, channel, label), statistics over that label's pixels as in a1 (fp64 sums,
+ * std = sqrt(var_unbiased + eps)). Rows of invalid or absent labels are pass-through:
+ * std_c = -1. content (N,C,HWc), style (N,C,HWs). params must be 16-byte aligned.
+ * Workspace: rpst_masked_adain_workspace_size(N, C).
+ *
+ * rpst_masked_adain_apply: out = [skip +] ((x - mean_c) / std_c * std_s + mean_s) where the
+ * pixel's row is not pass-through, out = [skip +] x elsewhere (bit-exact copy without skip).
+ * skip_or_null: the running decoder feature of MultiScaleAdaINRPNet.decode (adain_rp.py:301)
+ * or NULL. content / skip / out (N,C,HW), c_seg (N,HW). */
+int rpst_segment_plan(const uint8_t* c_seg, const uint8_t* s_seg, int N, int64_t HWc,
+                      int64_t HWs, int32_t* plan, rpst_stream_t stream);
+size_t rpst_masked_adain_workspace_size(int N, int C);
+int rpst_masked_adain_params(const float* content, const float* style, const uint8_t* c_seg,
+                             const uint8_t* s_seg, const int32_t* plan, int N, int C,
+                             int64_t HWc, int64_t HWs, float eps, float* params,
+                             void* workspace, size_t workspace_bytes, rpst_stream_t stream);
+int rpst_masked_adain_apply(const float* content, const float* skip_or_null,
+                            const uint8_t* c_seg, const float* params, float* out, int N, int C,
+                            int64_t HW, rpst_stream_t stream);
+
 /* ---- a3/a5/a6/a12: Conv2d (3x3 or 1x1, stride 1) + bias [+ReLU] [+residual] -------
  * nn.Conv2d(k=3, padding=1) + ReLU         base.py:363-396 (RP encoder / decoder)
  * ReflectionPad2d(1) + Conv2d(k=3) [+ReLU] base.py:25-111, sanet.py:146-147,162-192

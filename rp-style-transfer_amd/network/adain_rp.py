@@ -18,7 +18,8 @@ from rpst.plan import KernelSequential
 
 from .base import (BaseNet, Conv2dBlock, SourceNet, StackType,  # noqa: F401 (star exports)
                    adaptive_instance_normalization, build_decrease_depth_rp_blocks,
-                   build_increase_depth_rp_blocks, calc_mean_std, mse, rp_constant_conv_blocks,
+                   build_increase_depth_rp_blocks, calc_mean_std, masked_adain_batch, mse,
+                   rp_constant_conv_blocks, segment_maps,
                    rp_deeper_conv_blocks, rp_shallower_conv_blocks)
 from .base import adaptive_instance_normalization as AdaIN  # noqa: F401 (reference alias)
 
@@ -144,13 +145,19 @@ class MultiScaleAdaINRPNet(AdaINRPNet):
     block's output is kept; decoding starts from AdaIN of the deepest level and, before
     each next decoder block, adds AdaIN of the next shallower level (adain_rp.py:291-302).
     Constant ('constant') and deeper/shallower ('deeper') stacks of Conv2dBlocks
-    (reflect pad, LeakyReLU 0.2). shuffle / sort / use_mask are not on the kernel path.
+    (reflect pad, LeakyReLU 0.2). shuffle / sort are not on the kernel path.
 
     test() runs the shared encoder once over [content; style]; each encoder block emits
     calc_mean_std of its output from its last conv's epilogue; the decoder's first conv
     applies AdaIN while staging its input and every later block's first conv forms
     stylized + AdaIN(c_i, s_i) in its loader (RPST_IN_ADD_ADAIN), so no AdaIN or sum
-    tensor is ever written."""
+    tensor is ever written.
+
+    use_mask (test / decode only, adain_rp.py:286-319): every level's AdaIN is taken per
+    segmentation label (masks resized to the image size, which every level shares, so the
+    label counts and validity are planned once); the masked kernels write stylized +
+    AdaINSeg(c_i, s_i) once per level and the decoder block reads it as a plain input. The
+    encoder then emits no epilogue statistics."""
 
     def __init__(self, config, vgg_encoder) -> None:
         super().__init__(config, vgg_encoder)
@@ -183,10 +190,10 @@ class MultiScaleAdaINRPNet(AdaINRPNet):
             self.rp_shared_encoder.load_state_dict(state_dict['encoder'])
             self.rp_decoder.load_state_dict(state_dict['decoder'])
 
-    def _kernel_path_check(self, use_mask):
-        if use_mask or self._sort or self._shuffle:
+    def _kernel_path_check(self):
+        if self._sort or self._shuffle:
             raise NotImplementedError(
-                "MultiScaleAdaINRPNet: shuffle / sort / use_mask have no rpst kernel path")
+                "MultiScaleAdaINRPNet: shuffle / sort have no rpst kernel path")
 
     def encode_rp_intermediate(self, input):
         results = [input]
@@ -197,15 +204,27 @@ class MultiScaleAdaINRPNet(AdaINRPNet):
     def test(self, content, style, iterations=0, bid=0, c_mask_path=None, s_mask_path=None):
         self.eval()
         with torch.no_grad():
-            self._kernel_path_check(self.config['use_mask'])
+            self._kernel_path_check()
             if not FUSED_ADAIN:
                 content_feats = self.encode_rp_intermediate(content)
                 style_feats = self.encode_rp_intermediate(style)
                 stylized = self.decode(content_feats, style_feats,
-                                       use_mask=self.config['use_mask'])
+                                       use_mask=self.config['use_mask'],
+                                       c_mask_path=c_mask_path, s_mask_path=s_mask_path)
                 self.train()
                 return stylized
             n = content.shape[0]
+            if self.config['use_mask']:
+                x, x2 = content, style
+                feats = []  # feature over 2n per encoder block, no statistics
+                for blk in self.rp_shared_encoder:
+                    x = plan.run(_block_plan(blk), x, x2=x2)
+                    x2 = None
+                    feats.append(x)
+                y = self.decode([f[:n] for f in feats], [f[n:] for f in feats], True,
+                                c_mask_path, s_mask_path)
+                self.train()
+                return y
             x, x2 = content, style  # the first block reads both in place (no concat)
             levels = []  # (feature over 2n, mean, std) per encoder block
             for blk in self.rp_shared_encoder:
@@ -228,8 +247,23 @@ class MultiScaleAdaINRPNet(AdaINRPNet):
 
     def decode(self, content_feats, style_feats, use_mask=False, c_mask_path=None, s_mask_path=None):
         """adain_rp.py:291-302, op by op: AdaIN kernels, then each block with the skip
-        sum formed in its first conv's loader."""
-        self._kernel_path_check(use_mask)
+        sum formed in its first conv's loader. use_mask: per-label AdaIN at every level
+        (do_mask_stylized), the skip sum formed by the masked apply kernel."""
+        self._kernel_path_check()
+        if use_mask:
+            # all levels share H x W: decode the masks and plan the labels once
+            n, dev = content_feats[-1].shape[0], content_feats[-1].device
+            c_seg = segment_maps(c_mask_path, n, content_feats[-1].shape[2:], dev)
+            s_seg = segment_maps(s_mask_path, n, style_feats[-1].shape[2:], dev)
+            stylized, seg_plan = masked_adain_batch(content_feats[-1], style_feats[-1], c_seg,
+                                                    s_seg)
+            stylized = self.rp_decoder[0](stylized)
+            for i, (content_feat, style_feat) in enumerate(
+                    list(zip(content_feats[:-1], style_feats[:-1]))[::-1]):
+                fused, _ = masked_adain_batch(content_feat, style_feat, c_seg, s_seg,
+                                              skip=stylized, plan=seg_plan)
+                stylized = self.rp_decoder[i + 1](fused)
+            return stylized
         stylized = AdaIN(content_feats[-1], style_feats[-1])
         stylized = self.rp_decoder[0](stylized)
         for i, (content_feat, style_feat) in enumerate(
@@ -248,7 +282,7 @@ class MultiScaleAdaINRPNet(AdaINRPNet):
         no_grad it is evaluated op by op."""
         assert 0 <= alpha <= 1
         if torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters()):
-            self._kernel_path_check(self.config['use_mask'])
+            self._kernel_path_check()
             from rpst.autograd import multiscale_losses
             return multiscale_losses(self, content, style)
         content_feats = self.encode_rp_intermediate(content)

@@ -7,7 +7,8 @@ Same names, signatures, module structure and state_dict keys as the reference:
   build_decrease_depth_rp_blocks   network/base.py:382-396
   calc_mean_std                    network/base.py:399-407
   adaptive_instance_normalization  network/base.py:410-418
-  BaseNet                          network/base.py:533-559
+  adaptive_instance_normalization_with_segment  network/base.py:421-530 (batched)
+  BaseNet                         network/base.py:533-559
   StackType, Conv2dBlock           network/base.py:18-23, 114-198
   rp_deeper/shallower/constant_conv_blocks  network/base.py:229-311
   SourceNet (classic AdaIN)        network/base.py:562-649
@@ -247,6 +248,42 @@ def decode_adain(decoder_seq, feats, mean, std, n):
                     first_aux=aux, first_in_op=ops.IN_ADAIN)
 
 
+def adaptive_instance_normalization_with_segment(content_feat, style_feat, content_seg_path,
+                                                 style_seg_path):
+    """Per-label AdaIN of one image pair (base.py:494-530): features (1, C, h, w), one mask
+    path each (or a uint8 label map (h, w) already at the feature size)."""
+    def one(m):
+        return m[None] if torch.is_tensor(m) else [m]
+    return masked_adain_batch(content_feat, style_feat, one(content_seg_path),
+                              one(style_seg_path))[0]
+
+
+def segment_maps(mask, n, hw, device):
+    """The label maps of a batch at feature size hw = (h, w): `mask` is a list of n mask
+    paths, loaded as get_segment_and_info does (base.py:450-451), or label maps already
+    decoded to that size, uint8 (n, h, w) -> uint8 (n, h, w) on `device`."""
+    if torch.is_tensor(mask):
+        if mask.dtype != torch.uint8 or tuple(mask.shape) != (n, hw[0], hw[1]):
+            raise ValueError(f"decoded masks must be uint8 {(n, hw[0], hw[1])}, got "
+                             f"{mask.dtype} {tuple(mask.shape)}")
+        return mask.to(device)
+    from rpst.imageio import load_segments
+    if mask is None or len(mask) != n:
+        raise ValueError(f"use_mask needs one mask path per image of the batch ({n})")
+    return load_segments(list(mask), (hw[1], hw[0])).to(device)
+
+
+def masked_adain_batch(content_feat, style_feat, c_mask_path, s_mask_path, skip=None, plan=None):
+    """do_mask_stylized (base.py:595-601, adain_rp.py:313-319) for the whole batch in one
+    launch sequence, [skip +] the result; image n uses masks n -> (fused, plan)."""
+    n = content_feat.shape[0]
+    c_seg = segment_maps(c_mask_path, n, content_feat.shape[2:], content_feat.device)
+    s_seg = segment_maps(s_mask_path, n, style_feat.shape[2:], style_feat.device)
+    if plan is None:
+        plan = ops.segment_plan(c_seg, s_seg)
+    return ops.masked_adain(content_feat, style_feat, c_seg, s_seg, skip=skip, plan=plan), plan
+
+
 FUSED = True  # test(): AdaIN fused into the neighbouring convs (False: op by op)
 
 
@@ -272,8 +309,14 @@ class SourceNet(BaseNet):
 
     def test(self, content, style, iterations=0, bid=0, c_mask_path=None, s_mask_path=None):
         with torch.no_grad():
-            if self.config['use_mask']:
-                raise NotImplementedError("SourceNet: masked AdaIN has no rpst kernel")
+            if FUSED and self.config['use_mask']:
+                # encoder once over [content; style], no epilogue statistics: the per-label
+                # ones need the label maps; the fused feature is written once
+                encs = [self.enc_1, self.enc_2, self.enc_3, self.enc_4]
+                n = content.shape[0]
+                feats = encode_both(encs, content, style)
+                t, _ = masked_adain_batch(feats[:n], feats[n:], c_mask_path, s_mask_path)
+                return self.decoder(t)
             if FUSED:
                 # encoder once over [content; style]; relu4_1 statistics from the last
                 # conv's epilogue; AdaIN applied while the decoder stages its input
@@ -287,9 +330,16 @@ class SourceNet(BaseNet):
 
     def decode(self, content_feats, style_feats, use_mask=False, c_mask_path=None, s_mask_path=None):
         if use_mask:
-            raise NotImplementedError("SourceNet: masked AdaIN has no rpst kernel")
-        t = adaptive_instance_normalization(content_feats[-1], style_feats[-1])
+            t = self.do_mask_stylized(content_feats[-1], style_feats[-1], c_mask_path,
+                                      s_mask_path)
+        else:
+            t = adaptive_instance_normalization(content_feats[-1], style_feats[-1])
         return self.decoder(t)
+
+    def do_mask_stylized(self, content_feat, style_feat, c_mask_path, s_mask_path):
+        """base.py:595-601: per-label AdaIN, image n with masks n (paths, or uint8 label maps
+        (N, h, w) already at the feature size)."""
+        return masked_adain_batch(content_feat, style_feat, c_mask_path, s_mask_path)[0]
 
     def encode_with_intermediate(self, input):
         results = [input]

@@ -30,6 +30,11 @@ SIGNATURES = {
     "rpst_adain_workspace_size": (_SZ, [_I, _I]),
     "rpst_adain": (_I, [_P, _P, _P, _I, _I, _I64, _F, _P, _SZ, _P]),
     "rpst_mean_variance_norm": (_I, [_P, _P, _I, _I, _I64, _F, _P, _SZ, _P]),
+    "rpst_segment_plan": (_I, [_P, _P, _I, _I64, _I64, _P, _P]),
+    "rpst_masked_adain_workspace_size": (_SZ, [_I, _I]),
+    "rpst_masked_adain_params": (_I, [_P, _P, _P, _P, _P, _I, _I, _I64, _I64, _F, _P, _P, _SZ,
+                                      _P]),
+    "rpst_masked_adain_apply": (_I, [_P, _P, _P, _P, _P, _I, _I, _I64, _P]),
     "rpst_conv2d_packed_size": (_SZ, [_I, _I, _I]),
     "rpst_conv2d_pack": (_I, [_P, _P, _I, _I, _I, _P]),
     "rpst_conv2d_grid_threads": (_I64, [_I, _I, _I, _I, _I, _I, _I]),

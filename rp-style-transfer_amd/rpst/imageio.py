@@ -62,7 +62,7 @@ class PairedDataset:
 
 class PhotorealisticPairedDataset(PairedDataset):
     """datasets/base.py:89-131: style/tar<content name without 'in'>, masks under
-    labelme_segmentation/<stem>.png (paths only; the masked networks are out of scope)."""
+    labelme_segmentation/<stem>.png (paths only; Pipeline(masks=True) decodes them)."""
 
     def __init__(self, root: str):
         super().__init__(root)
@@ -89,6 +89,27 @@ def load_image(path: str, size: int) -> np.ndarray:
         if im.size != (size, size):
             im = im.resize((size, size), Image.BILINEAR)
         return np.asarray(im, dtype=np.uint8).copy()
+
+
+def load_segment(path: str, size: Tuple[int, int]) -> np.ndarray:
+    """get_segment_and_info's mask load (network/base.py:450-451): np.asarray(Image.open(path)
+    .resize((w, h))) -> uint8 (h, w). PIL's default resample applies, as in the reference:
+    nearest for palette ('P') PNGs, bicubic for greyscale ('L') ones, whose in-between
+    values along region borders are labels like any other."""
+    from PIL import Image
+    with Image.open(path) as im:
+        seg = np.asarray(im.resize((int(size[0]), int(size[1]))))
+    if seg.ndim != 2:
+        raise ValueError(f"segmentation mask {path} decodes to shape {seg.shape}; a label map "
+                         "must be 2-D (palette or greyscale PNG)")
+    if seg.dtype != np.uint8:
+        raise ValueError(f"segmentation mask {path} decodes to {seg.dtype}; labels must be uint8")
+    return np.ascontiguousarray(seg)
+
+
+def load_segments(paths: Sequence[str], size: Tuple[int, int]) -> torch.Tensor:
+    """One mask per batch image, each resized to (w, h) -> uint8 tensor (N, h, w)."""
+    return torch.from_numpy(np.stack([load_segment(p, size) for p in paths]))
 
 
 def save_png(arr: np.ndarray, path: str, level: int = 6) -> None:
@@ -197,15 +218,24 @@ class Pipeline:
     check: called before the LAST batch's files are queued (e.g. WCTRPNet.check, which waits
     for and raises on that batch's deferred WCT status). Every earlier batch is checked by
     the model itself before its files are queued: its status is raised during the next
-    batch's stylize() call (ops.WCTStatusWatch), which runs before that batch's writes."""
+    batch's stylize() call (ops.WCTStatusWatch), which runs before that batch's writes.
+
+    masks=True (`use_mask: True`, a dataset whose items carry mask paths): the two
+    segmentation masks of every pair are decoded on the decode threads beside the images
+    (load_segment, resized to mask_size = (w, h), the feature size the network fuses at;
+    default the image size), uploaded with the pixels, and the call becomes
+    stylize(content, style, c_seg, s_seg) with uint8 (N, h, w) label maps on the device."""
 
     BACKLOG = 3
 
     def __init__(self, stylize: Callable[[torch.Tensor, torch.Tensor], torch.Tensor],
                  device, img_size: int, batch_size: int = 1, num_workers: int = 4,
                  cat: bool = True, png_level: int = 6, encode_workers: Optional[int] = None,
-                 png_strategy: str = "default", check: Optional[Callable[[], None]] = None):
+                 png_strategy: str = "default", check: Optional[Callable[[], None]] = None,
+                 masks: bool = False, mask_size: Optional[Tuple[int, int]] = None):
         self.stylize = stylize
+        self.masks = masks
+        self.mask_size = tuple(mask_size) if mask_size else (img_size, img_size)
         self.check = check
         self.device = torch.device(device)
         self.img_size = img_size
@@ -227,7 +257,19 @@ class Pipeline:
         def load(k, j, path):
             pix[k, j] = load_image(path, self.img_size)
         futs = [pool.submit(load, k, j, it[k]) for j, it in enumerate(items) for k in (0, 1)]
-        return items, pinned, futs
+        seg_pinned = None
+        if self.masks:
+            w, h = self.mask_size
+            seg_pinned = torch.empty((2, len(idx), h, w), dtype=torch.uint8, pin_memory=True)
+            seg = seg_pinned.numpy()
+
+            def load_seg(k, j, path):
+                if not path:
+                    raise ValueError("Pipeline(masks=True): the dataset item has no mask path")
+                seg[k, j] = load_segment(path, (w, h))
+            futs += [pool.submit(load_seg, k, j, it[4 + k]) for j, it in enumerate(items)
+                     for k in (0, 1)]
+        return items, pinned, futs, seg_pinned
 
     def run(self, dataset, out_dir: str, log: Optional[Callable[[str], None]] = None) -> int:
         os.makedirs(out_dir, exist_ok=True)
@@ -252,7 +294,7 @@ class Pipeline:
             for k in range(len(batches)):
                 if k + 1 < len(batches):  # decode the next batch while this one runs
                     pending.append(self._decode_start(readers, dataset, batches[k + 1]))
-                items, pinned, futs = pending.pop(0)
+                items, pinned, futs, seg_pinned = pending.pop(0)
                 t0 = clock()
                 for f in futs:
                     f.result()
@@ -260,11 +302,18 @@ class Pipeline:
                 st["wait_decode"] += t1 - t0
                 with torch.cuda.stream(copy_stream):
                     dev_u8 = pinned.to(self.device, non_blocking=True)
+                    dev_seg = None
+                    if seg_pinned is not None:
+                        dev_seg = seg_pinned.to(self.device, non_blocking=True)
                 compute = torch.cuda.current_stream(self.device)
                 compute.wait_stream(copy_stream)
                 dev_u8.record_stream(compute)
                 content, style = to_tensor(dev_u8[0]), to_tensor(dev_u8[1])
-                stylized = self.stylize(content, style)
+                if dev_seg is not None:
+                    dev_seg.record_stream(compute)
+                    stylized = self.stylize(content, style, dev_seg[0], dev_seg[1])
+                else:
+                    stylized = self.stylize(content, style)
                 outs = [to_uint8(stylized)]
                 if self.cat:
                     outs.append(grid_uint8([content, style, stylized]))

@@ -144,6 +144,109 @@ def adaptive_instance_normalization(content: torch.Tensor, style: torch.Tensor,
     return out
 
 
+SEG_LABELS = 256  # rows per image of a segment plan / per plane of masked AdaIN params
+
+
+def _check_seg(seg: torch.Tensor, n: int, like: torch.Tensor) -> torch.Tensor:
+    _check(seg, dtype=torch.uint8)
+    if seg.dim() != 3 or seg.shape[0] != n:
+        raise ValueError(f"rpst: label map must be uint8 (N={n}, h, w), got {tuple(seg.shape)}")
+    if seg.device != like.device:
+        raise RuntimeError(f"rpst: tensors on different devices ({like.device} vs {seg.device})")
+    return _c(seg)
+
+
+def segment_plan(c_seg: torch.Tensor, s_seg: torch.Tensor) -> torch.Tensor:
+    """compute_label_info (network/base.py:421-439) on the GPU for N image pairs: uint8 label
+    maps (N, hc, wc) and (N, hs, ws) -> int32 (N, 256, 4) = (content count, style count,
+    valid, 0) per label. Stays on the device; one plan serves every feature level."""
+    if c_seg.dim() != 3:
+        raise ValueError(f"rpst: label map must be uint8 (N, h, w), got {tuple(c_seg.shape)}")
+    n = c_seg.shape[0]
+    c_seg, s_seg = _check_seg(c_seg, n, c_seg), _check_seg(s_seg, n, c_seg)
+    plan = torch.empty((n, SEG_LABELS, 4), device=c_seg.device, dtype=torch.int32)
+    hwc, hws = c_seg[0].numel(), s_seg[0].numel()
+    with _traced(f"segplan {hwc}px N{n}", 0.0, 1.0 * n * (hwc + hws)):
+        _lib.call("rpst_segment_plan", c_seg.data_ptr(), s_seg.data_ptr(), n, hwc, hws,
+                  plan.data_ptr(), _stream(c_seg))
+    return plan
+
+
+def _masked_args(content, style, c_seg, s_seg, plan):
+    assert content.dim() == 4 and style.dim() == 4
+    _check(content, style)
+    if content.shape[:2] != style.shape[:2]:
+        raise ValueError("rpst: content and style differ in N or C")
+    content, style = _c(content), _c(style)
+    n = content.shape[0]
+    c_seg, s_seg = _check_seg(c_seg, n, content), _check_seg(s_seg, n, content)
+    if tuple(c_seg.shape[1:]) != tuple(content.shape[2:]) or \
+            tuple(s_seg.shape[1:]) != tuple(style.shape[2:]):
+        raise ValueError("rpst: label maps must have their feature's (h, w): "
+                         f"{tuple(c_seg.shape[1:])} vs {tuple(content.shape[2:])}, "
+                         f"{tuple(s_seg.shape[1:])} vs {tuple(style.shape[2:])}")
+    if plan is None:
+        plan = segment_plan(c_seg, s_seg)
+    else:
+        _check(plan, dtype=torch.int32)
+        if tuple(plan.shape) != (n, SEG_LABELS, 4) or plan.device != content.device:
+            raise ValueError(f"rpst: segment plan must be int32 ({n}, 256, 4) on the tensors' "
+                             "device")
+        plan = _c(plan)
+    return content, style, c_seg, s_seg, plan
+
+
+def masked_adain_params(content: torch.Tensor, style: torch.Tensor, c_seg: torch.Tensor,
+                        s_seg: torch.Tensor, plan: Optional[torch.Tensor] = None,
+                        eps: float = 1e-5) -> torch.Tensor:
+    """Per-label AdaIN statistics (network/base.py:465-491 for every valid label at once):
+    -> fp32 (N, C, 256, 4) = (mean_c, std_c, std_s, mean_s) per (image, channel, label);
+    rows of invalid or absent labels are pass-through (std_c = -1)."""
+    return _masked_params(*_masked_args(content, style, c_seg, s_seg, plan), eps)
+
+
+def _masked_params(content, style, c_seg, s_seg, plan, eps):
+    N, C = content.shape[:2]
+    hwc, hws = c_seg[0].numel(), s_seg[0].numel()
+    params = torch.empty((N, C, SEG_LABELS, 4), device=content.device, dtype=torch.float32)
+    nbytes = _lib.load().rpst_masked_adain_workspace_size(N, C)
+    ws = torch.empty(nbytes, device=content.device, dtype=torch.uint8)
+    with _traced(f"masked stats C{C} {hwc}px N{N}", 0.0, (4.0 * C + 1) * N * (hwc + hws)):
+        _lib.call("rpst_masked_adain_params", content.data_ptr(), style.data_ptr(),
+                  c_seg.data_ptr(), s_seg.data_ptr(), plan.data_ptr(), N, C, hwc, hws, eps,
+                  params.data_ptr(), ws.data_ptr(), nbytes, _stream(content))
+    return params
+
+
+def masked_adain(content: torch.Tensor, style: torch.Tensor, c_seg: torch.Tensor,
+                 s_seg: torch.Tensor, skip: Optional[torch.Tensor] = None,
+                 plan: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None,
+                 eps: float = 1e-5) -> torch.Tensor:
+    """adaptive_instance_normalization_with_segment (network/base.py:494-530) for a batch,
+    image n with its own label maps c_seg[n], s_seg[n] (uint8, already at the features'
+    sizes): [skip +] the content with every validly labelled pixel re-normalised to its
+    label's style statistics; other pixels are copied (plan + stats + apply launches)."""
+    content, style, c_seg, s_seg, plan = _masked_args(content, style, c_seg, s_seg, plan)
+    if skip is not None:
+        _check(skip)
+        if skip.shape != content.shape or skip.device != content.device:
+            raise ValueError("rpst: skip must have the content's shape and device")
+        skip = _c(skip)
+    params = _masked_params(content, style, c_seg, s_seg, plan, eps)
+    N, C = content.shape[:2]
+    hw = c_seg[0].numel()
+    if out is None:
+        out = torch.empty_like(content)
+    elif out.shape != content.shape or not out.is_contiguous() or out.dtype != torch.float32 \
+            or out.device != content.device:
+        raise ValueError("rpst: out must be a contiguous fp32 tensor of the content's shape")
+    with _traced(f"masked apply C{C} {hw}px N{N}", 0.0,
+                 ((3.0 if skip is not None else 2.0) * 4 * C + 1) * N * hw):
+        _lib.call("rpst_masked_adain_apply", content.data_ptr(), _ptr(skip), c_seg.data_ptr(),
+                  params.data_ptr(), out.data_ptr(), N, C, hw, _stream(content))
+    return out
+
+
 def mean_variance_norm(feat: torch.Tensor, eps: float = 1e-5) -> torch.Tensor:
     """network/sanet.py:20-24 on the GPU."""
     assert feat.dim() == 4

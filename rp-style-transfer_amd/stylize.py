@@ -7,7 +7,9 @@ test_dataset, batch_size, num_workers, output, start_iter, model options; loaded
 yaml.safe_load), builds the network from this package, loads `vgg` (weights_only) and
 stylises every pair of `test_dir` into `<output>/test/test_output/{cn}-{sn}.png` and
 `{cn}-{sn}-cat.png` through rpst.imageio.Pipeline (decode / PNG encode on host threads,
-ToTensor and save_image's pixel path on the GPU).
+ToTensor and save_image's pixel path on the GPU). With `use_mask: True` and
+`test_dataset: photoreal` the pipeline also decodes each pair's two segmentation masks and
+`src` / `multi_adain` stylise per label.
 
 Differences from test.py, by design: no TensorBoard writer, no per-step cv2 import, the
 test.py:135 `iterations=i` NameError is not reproduced (iterations=0 is passed), and
@@ -33,6 +35,19 @@ logging.basicConfig(level=logging.INFO,
 logger = logging.getLogger("stylize")
 
 OUT_OF_SCOPE = ("sel_multi_adain", "ld_adain", "ld_adain2", "mrf", "spade")
+
+
+MASKED_NETWORKS = ("src", "multi_adain")  # networks whose test() honours use_mask
+
+
+def mask_size(kind, img_size):
+    """(w, h) of the feature the masked AdaIN runs on: relu4_1 for SourceNet (three ceil-mode
+    2x2 pools), the image itself for the resolution-preserving stacks."""
+    s = img_size
+    if kind == "src":
+        for _ in range(3):
+            s = (s + 1) // 2
+    return (s, s)
 
 
 def build_network(opt, synthetic_seed=None):
@@ -101,14 +116,22 @@ def main(argv=None) -> int:
     network.eval()
     dataset = DATASETS[opt["test_dataset"]](opt["test_dir"])
 
-    def stylize(content, style):
-        return network.test(content, style)
+    # use_mask (test.py:128-136 passes the dataset's mask paths on): the two networks whose
+    # test() reads them get the label maps decoded ahead by the pipeline
+    masks = bool(opt.get("use_mask")) and opt["network"] in MASKED_NETWORKS
+    if masks and opt["test_dataset"] != "photoreal":
+        raise ValueError("use_mask: True needs test_dataset: photoreal (the dataset with "
+                         "labelme_segmentation masks)")
+
+    def stylize(content, style, c_seg=None, s_seg=None):
+        return network.test(content, style, c_mask_path=c_seg, s_mask_path=s_seg)
 
     with torch.cuda.device(device):
         n = Pipeline(stylize, device, opt["img_size"], opt.get("batch_size", 1),
                      opt.get("num_workers", 4), png_level=args.png_compress_level,
                      png_strategy=args.png_strategy, encode_workers=args.encode_workers,
-                     check=getattr(network, "check", None)).run(
+                     check=getattr(network, "check", None), masks=masks,
+                     mask_size=mask_size(opt["network"], opt["img_size"])).run(
                          dataset, str(out_dir), log=logger.info)
     logger.info(f"stylised {n} pairs into {out_dir}")
     return 0

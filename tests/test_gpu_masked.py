@@ -1,0 +1,320 @@
+"""Segmentation-masked AdaIN on the GPU: the plan / params / apply kernels against the
+float64 restatement (tests/masked_ref.py) and the reference goldens
+(tests/golden/masked.*), the two networks' masked test() against the goldens, and the
+pipeline with masks."""
+import copy
+import os
+
+import numpy as np
+import pytest
+import torch
+
+import masked_ref as M
+from helpers import (SOURCE_CONFIG, TOL_NET, TOL_NET_MAXABS, TOL_STATS, max_abs_ratio,
+                     multiscale_config, rel_l2, synth_)
+
+pytestmark = pytest.mark.gpu
+
+
+def _dev(a, cuda):
+    return torch.from_numpy(np.ascontiguousarray(a)).to(cuda)
+
+
+# ---- segment_plan ------------------------------------------------------------------------
+def _map_of(counts, shape, seed):
+    """A label map of `shape` holding exactly counts[label] pixels of each label, shuffled."""
+    flat = np.concatenate([np.full(n, lab, np.uint8) for lab, n in counts.items()])
+    assert flat.size == shape[0] * shape[1], (flat.size, shape)
+    return np.random.default_rng(seed).permutation(flat).reshape(shape)
+
+
+# label: (content count, style count) -> valid?
+PLAN_CASE = {
+    0: (20, 20, 1),       # label 0
+    255: (30, 30, 1),     # label 255
+    1: (10, 50, 0),       # 10 pixels: not more than 10
+    2: (11, 11, 1),       # 11 pixels
+    3: (1100, 11, 0),     # c / s exactly 100
+    4: (1099, 11, 1),     # just under
+    7: (11, 1100, 0),     # s / c exactly 100
+    8: (11, 1099, 1),
+    5: (50, 0, 0),        # content only
+    6: (0, 50, 0),        # style only
+}
+
+
+@pytest.mark.parametrize("pad", [0, 1])  # HW a multiple of 4 (32-bit label loads) or not
+def test_segment_plan_counts_and_flags(cuda, pad):
+    from rpst import ops
+    c_counts = {lab: v[0] for lab, v in PLAN_CASE.items() if v[0]}
+    s_counts = {lab: v[1] for lab, v in PLAN_CASE.items() if v[1]}
+    # filler label 9 brings the maps to (h, w); the style map has another size
+    c_shape, s_shape = (34 + pad, 70), (50, 48 + pad)
+    c_counts[9] = c_shape[0] * c_shape[1] - sum(c_counts.values())
+    s_counts[9] = s_shape[0] * s_shape[1] - sum(s_counts.values())
+    assert (c_shape[0] * c_shape[1]) % 4 == (2 * pad) % 4
+    c0, s0 = _map_of(c_counts, c_shape, 1), _map_of(s_counts, s_shape, 2)
+    # image 1: other masks (piecewise constant, labels 0 / 3 / 200 in rows)
+    c1 = np.repeat(np.array([0, 3, 200, 3, 0], np.uint8), [5, 9, 10, 6, c_shape[0] - 30])
+    c1 = np.tile(c1[:, None], (1, c_shape[1]))
+    s1 = np.full(s_shape, 3, np.uint8)
+    s1[:2, :5] = 200  # 10 pixels of 200 in the style: not valid
+    plan = ops.segment_plan(_dev(np.stack([c0, c1]), cuda), _dev(np.stack([s0, s1]), cuda))
+    assert plan.dtype == torch.int32 and tuple(plan.shape) == (2, 256, 4)
+    plan = plan.cpu().numpy()
+    for n, (c, s) in enumerate([(c0, s0), (c1, s1)]):
+        assert np.array_equal(plan[n, :, :3], M.label_counts(c, s)), n
+    for lab, (cc, sc, valid) in PLAN_CASE.items():
+        assert tuple(plan[0, lab, :3]) == (cc, sc, valid), lab
+    assert plan[1, 3, 2] == 1 and plan[1, 200, 2] == 0 and plan[1, 0, 2] == 0
+    assert plan[1, 0, 0] == (c_shape[0] - 25) * c_shape[1]
+
+
+def test_masked_ops_reject_cpu_tensors():
+    from rpst import ops
+    seg = torch.zeros((1, 4, 4), dtype=torch.uint8)
+    x = torch.zeros((1, 2, 4, 4))
+    with pytest.raises(RuntimeError, match="ROCm GPU only"):
+        ops.segment_plan(seg, seg)
+    with pytest.raises(RuntimeError, match="ROCm GPU only"):
+        ops.masked_adain(x, x, seg, seg)
+
+
+# ---- masked_adain_params -----------------------------------------------------------------
+def _op_cases(g):
+    return [(i, str(g[f"op{i}_name"])) for i in range(int(g["n_ops"]))]
+
+
+@pytest.fixture(scope="module")
+def op_refs(golden):
+    """Float64 restatement of every golden op case, computed once: case -> (rows (N, C, 256,
+    4), counts (N, 256, 3))."""
+    g = golden("masked")
+    refs = {}
+    for i, _ in _op_cases(g):
+        per = [M.masked_params(g[f"op{i}_c"][n], g[f"op{i}_s"][n], g[f"op{i}_cseg"][n],
+                               g[f"op{i}_sseg"][n]) for n in range(g[f"op{i}_c"].shape[0])]
+        refs[i] = (np.stack([p[0] for p in per]), np.stack([p[1] for p in per]))
+    return refs
+
+
+def test_op_cases_cover_the_shapes(golden):
+    g = golden("masked")
+    shapes = {tuple(g[f"op{i}_c"].shape) for i, _ in _op_cases(g)}
+    assert {(2, 8, 24, 40), (1, 3, 13, 9), (1, 40, 17, 33)} <= shapes
+    assert any(g[f"op{i}_c"].shape[2:] != g[f"op{i}_s"].shape[2:] for i, _ in _op_cases(g))
+
+
+def test_masked_adain_params_vs_float64(cuda, golden, op_refs):
+    from rpst import ops
+    g = golden("masked")
+    for i, name in _op_cases(g):
+        c, s = _dev(g[f"op{i}_c"], cuda), _dev(g[f"op{i}_s"], cuda)
+        cseg, sseg = _dev(g[f"op{i}_cseg"], cuda), _dev(g[f"op{i}_sseg"], cuda)
+        got = ops.masked_adain_params(c, s, cseg, sseg).cpu().numpy()
+        rows, counts = op_refs[i]
+        assert got.shape == rows.shape
+        valid = counts[:, None, :, 2].astype(bool) & np.ones(rows.shape[:3], bool)
+        assert valid.any()
+        err = rel_l2(got[valid], rows[valid])
+        print(f"params {name}: rel-L2 {err:.3e} over {int(valid.sum())} rows")
+        assert err < TOL_STATS, (name, err)
+        # every row of a label that is not valid is the pass-through row, exactly
+        assert np.array_equal(got[~valid], rows[~valid]), name
+        if name.startswith("sizes"):
+            assert c.shape[2:] != s.shape[2:]
+
+
+def test_single_label_agrees_with_calc_mean_std(cuda, golden):
+    """One label over the whole map: the per-label statistics are the plane's, and sit within
+    1 ulp of calc_mean_std's (the guarantee rpst_stats.hip states)."""
+    from rpst import ops
+    g = golden("masked")
+    i = [k for k, name in _op_cases(g) if name.startswith("single")][0]
+    c, s = _dev(g[f"op{i}_c"], cuda), _dev(g[f"op{i}_s"], cuda)
+    lab = int(g[f"op{i}_cseg"][0, 0, 0])
+    assert (g[f"op{i}_cseg"] == lab).all() and (g[f"op{i}_sseg"] == lab).all()
+    p = ops.masked_adain_params(c, s, _dev(g[f"op{i}_cseg"], cuda),
+                                _dev(g[f"op{i}_sseg"], cuda))[:, :, lab].cpu().numpy()
+    cm, cs = (t.cpu().numpy().reshape(p.shape[:2]) for t in ops.calc_mean_std(c))
+    sm, ss = (t.cpu().numpy().reshape(p.shape[:2]) for t in ops.calc_mean_std(s))
+    for got, ref in ((p[..., 0], cm), (p[..., 1], cs), (p[..., 2], ss), (p[..., 3], sm)):
+        assert (np.abs(got - ref) <= np.spacing(np.abs(ref))).all()
+
+
+# ---- masked_adain ------------------------------------------------------------------------
+def test_masked_adain_vs_reference_goldens(cuda, golden, op_refs):
+    from rpst import ops
+    g = golden("masked")
+    for i, name in _op_cases(g):
+        c, s = _dev(g[f"op{i}_c"], cuda), _dev(g[f"op{i}_s"], cuda)
+        cseg, sseg = _dev(g[f"op{i}_cseg"], cuda), _dev(g[f"op{i}_sseg"], cuda)
+        out = ops.masked_adain(c, s, cseg, sseg)
+        err = rel_l2(out, g[f"op{i}_out"])
+        print(f"masked_adain {name}: rel-L2 {err:.3e}")
+        assert err < TOL_STATS, (name, err)
+        # pixels of labels that are not valid are the content's, bit for bit
+        counts = op_refs[i][1]
+        keep = np.stack([~counts[n][:, 2].astype(bool)[g[f"op{i}_cseg"][n]]
+                         for n in range(c.shape[0])])
+        keep = torch.from_numpy(keep).to(cuda)[:, None].expand_as(c)
+        if not name.startswith(("stripes", "single")):
+            assert keep.any() and not keep.all()
+        assert torch.equal(out[keep], c[keep]), name
+        assert not torch.equal(out[~keep], c[~keep]), name
+        # two runs give the same bits
+        assert torch.equal(out, ops.masked_adain(c, s, cseg, sseg)), name
+        # with a skip tensor: skip + (the result without), rounded once in fp32
+        skip = torch.from_numpy(np.random.default_rng(i).standard_normal(
+            tuple(c.shape)).astype(np.float32)).to(cuda)
+        plan = ops.segment_plan(cseg, sseg)
+        with_skip = ops.masked_adain(c, s, cseg, sseg, skip=skip, plan=plan)
+        assert torch.equal(with_skip, skip + out), name
+        # out= is honoured
+        buf = torch.empty_like(c)
+        assert ops.masked_adain(c, s, cseg, sseg, plan=plan, out=buf) is buf
+        assert torch.equal(buf, out)
+
+
+def test_masked_adain_batch_independent(cuda, golden):
+    from rpst import ops
+    g = golden("masked")
+    c, s = _dev(g["op0_c"], cuda), _dev(g["op0_s"], cuda)
+    cseg, sseg = _dev(g["op0_cseg"], cuda), _dev(g["op0_sseg"], cuda)
+    assert c.shape[0] == 2
+    both = ops.masked_adain(c, s, cseg, sseg)
+    for n in range(2):
+        one = ops.masked_adain(c[n:n + 1], s[n:n + 1], cseg[n:n + 1], sseg[n:n + 1])
+        assert torch.equal(both[n:n + 1], one), n
+
+
+# ---- networks ----------------------------------------------------------------------------
+def _mask_paths(tmp_path, tag, files, mode):
+    return [M.write_mask_png(str(tmp_path / f"{tag}_{mode}_{b}.png"), files[b], mode)
+            for b in range(files.shape[0])]
+
+
+def _check_net(y, ref, what):
+    err, mx = rel_l2(y, ref), max_abs_ratio(y, ref)
+    print(f"{what}: rel-L2 {err:.3e} max-abs {mx:.3e}")
+    assert err < TOL_NET and mx < TOL_NET_MAXABS, (what, err, mx)
+
+
+@pytest.mark.parametrize("mode", ["L", "P"])
+def test_multiscale_masked_golden(cuda, golden, tmp_path, mode):
+    import network as net
+    import network.adain_rp as arp
+    g = golden("masked")
+    m = net.MultiScaleAdaINRPNet(dict(multiscale_config(8, 5, 0), use_mask=True),
+                                 copy.deepcopy(net.vgg))
+    assert np.array_equal(synth_(m, int(g["ms_seed"])), g["ms_checksum"])
+    m = m.to(cuda)
+    c, s = _dev(g["ms_content"], cuda), _dev(g["ms_style"], cuda)
+    cps = _mask_paths(tmp_path, "c", g["ms_cfile"], mode)
+    sps = _mask_paths(tmp_path, "s", g["ms_sfile"], mode)
+    y = m.test(c, s, c_mask_path=cps, s_mask_path=sps)
+    _check_net(y, g[f"ms_out_{mode}"], f"multiscale fused {mode}")
+    # already-decoded label maps: the same bits as the paths
+    cseg, sseg = _dev(g[f"ms_cseg_{mode}"], cuda), _dev(g[f"ms_sseg_{mode}"], cuda)
+    assert torch.equal(m.test(c, s, c_mask_path=cseg, s_mask_path=sseg), y)
+    assert torch.equal(m.test(c, s, c_mask_path=cseg.cpu(), s_mask_path=sseg.cpu()), y)
+    # op by op: test() with FUSED_ADAIN off goes through decode(..., use_mask=True)
+    arp.FUSED_ADAIN = False
+    try:
+        plain = m.test(c, s, c_mask_path=cps, s_mask_path=sps)
+    finally:
+        arp.FUSED_ADAIN = True
+    _check_net(plain, g[f"ms_out_{mode}"], f"multiscale op-by-op {mode}")
+    with torch.no_grad():
+        cf, sf = m.encode_rp_intermediate(c), m.encode_rp_intermediate(s)
+        dec =m.decode(cf, sf, use_mask=True, c_mask_path=cps, s_mask_path=sps)
+    assert torch.equal(dec, plain)
+
+
+def test_multiscale_unmasked_unchanged_and_sort_still_raises(cuda, golden):
+    """use_mask False ignores the mask arguments; shuffle / sort keep raising."""
+    import network as net
+    g = golden("masked")
+    m = net.MultiScaleAdaINRPNet(multiscale_config(8, 5, 0), copy.deepcopy(net.vgg))
+    synth_(m, int(g["ms_seed"]))
+    m = m.to(cuda)
+    c, s = _dev(g["ms_content"], cuda), _dev(g["ms_style"], cuda)
+    cseg = _dev(g["ms_cseg_P"], cuda)
+    assert torch.equal(m.test(c, s), m.test(c, s, c_mask_path=cseg, s_mask_path=cseg))
+    cfg = dict(multiscale_config(8, 5, 0), use_mask=True, sort=True)
+    m2 = net.MultiScaleAdaINRPNet(cfg, copy.deepcopy(net.vgg)).to(cuda)
+    with pytest.raises(NotImplementedError):
+        m2.test(c, s, c_mask_path=cseg, s_mask_path=cseg)
+
+
+@pytest.mark.parametrize("mode", ["L", "P"])
+def test_sourcenet_masked_golden(cuda, golden, tmp_path, mode):
+    import network as net
+    import network.base as base
+    g = golden("masked")
+    m = net.SourceNet(dict(SOURCE_CONFIG, use_mask=True), copy.deepcopy(net.vgg))
+    assert np.array_equal(synth_(m, int(g["src_seed"])), g["src_checksum"])
+    m = m.to(cuda)
+    c, s = _dev(g["src_content"], cuda), _dev(g["src_style"], cuda)
+    cps = _mask_paths(tmp_path, "c", g["src_cfile"], mode)
+    sps = _mask_paths(tmp_path, "s", g["src_sfile"], mode)
+    y = m.test(c, s, c_mask_path=cps, s_mask_path=sps)
+    _check_net(y, g[f"src_out_{mode}"], f"sourcenet fused {mode}")
+    cseg, sseg = _dev(g[f"src_cseg_{mode}"], cuda), _dev(g[f"src_sseg_{mode}"], cuda)
+    assert tuple(cseg.shape) == (1, 8, 6)
+    assert torch.equal(m.test(c, s, c_mask_path=cseg, s_mask_path=sseg), y)
+    base.FUSED = False
+    try:
+        plain = m.test(c, s, c_mask_path=cps, s_mask_path=sps)
+    finally:
+        base.FUSED = True
+    _check_net(plain, g[f"src_out_{mode}"], f"sourcenet op-by-op {mode}")
+
+
+# ---- pipeline ----------------------------------------------------------------------------
+def _photoreal_tree(root, size, mask_size, modes):
+    """Two pairs: content/in<k>.png, style/tar<k>.png, labelme_segmentation/<stem>.png."""
+    from PIL import Image
+    rng = np.random.default_rng(11)
+    for d in ("content", "style", "labelme_segmentation"):
+        os.makedirs(os.path.join(root, d), exist_ok=True)
+    for k, mode in enumerate(modes):
+        for d, stem in (("content", f"in{k}"), ("style", f"tar{k}")):
+            a = rng.integers(0, 256, size=(size, size, 3), dtype=np.uint8)
+            Image.fromarray(a, "RGB").save(os.path.join(root, d, stem + ".png"))
+            M.write_mask_png(os.path.join(root, "labelme_segmentation", stem + ".png"),
+                             M.blocks_mask(mask_size, mask_size, [0, 60, 120, 180], 20 + k), mode)
+
+
+def test_pipeline_with_masks_matches_direct_test(cuda, tmp_path):
+    import yaml
+    from PIL import Image
+
+    import stylize
+    from rpst.imageio import PhotorealisticPairedDataset, load_image, to_tensor, to_uint8
+    root = str(tmp_path / "data")
+    _photoreal_tree(root, 40, 64, ["L", "P"])  # images 40 -> 32, masks 64 -> 32
+    cfg = dict(multiscale_config(8, 3, 0), network="multi_adain", vgg="unused", use_mask=True,
+               img_size=32, test_dir=root, test_dataset="photoreal", batch_size=2,
+               num_workers=2, output=str(tmp_path / "out"))
+    cfg_path = str(tmp_path / "cfg.yaml")
+    with open(cfg_path, "w") as f:
+        yaml.safe_dump(cfg, f)
+    assert stylize.main(["--config", cfg_path, "--synthetic-weights", "5"]) == 0
+    m = stylize.build_network(cfg, synthetic_seed=5).to(cuda)
+    ds = PhotorealisticPairedDataset(root)
+    assert len(ds) == 2
+    out_dir = tmp_path / "out" / "test" / "test_output"
+    for i in range(len(ds)):
+        cp, sp, cn, sn, cm, sm = ds.item(i)
+        c = to_tensor(_dev(load_image(cp, 32)[None], cuda))
+        s = to_tensor(_dev(load_image(sp, 32)[None], cuda))
+        y = m.test(c, s, c_mask_path=[cm], s_mask_path=[sm])
+        ref = to_uint8(y)[0].cpu().numpy()
+        got = np.asarray(Image.open(out_dir / f"{cn}-{sn}.png"))
+        assert np.array_equal(got, ref), (cn, sn)
+        # the masks matter: the unmasked network writes other pixels
+        m.config["use_mask"] = False
+        assert not np.array_equal(to_uint8(m.test(c, s))[0].cpu().numpy(), ref)
+        m.config["use_mask"] = True
+        assert (out_dir / f"{cn}-{sn}-cat.png").exists()
