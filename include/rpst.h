@@ -201,6 +201,37 @@ int rpst_conv2d_stats_store(const float* input, const float* aux, const float* p
                             int store_n, void* workspace, size_t workspace_bytes,
                             rpst_stream_t stream);
 
+/* SE channel attention of Conv2dBlock(attention='se') in eval mode (SEBottleneck,
+ * network/attention.py:25-66, built at network/base.py:177-179). With every BatchNorm folded
+ * into the conv before it (running statistics), the block is
+ *   h1 = relu(conv1(x)), h2 = relu(conv2(h1)), u = conv3(h2),
+ *   gate = sigmoid(fc_b relu(fc_a mean_HW(u))), out = relu(gate * u + x),
+ * and runs as rpst_conv2d (1x1), rpst_conv2d_stats (3x3; its `mean` is mean_HW(h2)), then the
+ * two calls below. u is never written: the pool of a 1x1 conv's output is the conv of the
+ * pooled input.
+ *
+ * The gate (SELayer, attention.py:17-22): mean_h2 (N, C) = per-(n, c) mean of h2; w3 (C, C)
+ * and b3 (C) = conv3 with bn3 folded, unpacked; fc_a (R, C), fc_b (C, R) = se.fc.0 / se.fc.2
+ * weights, R >= 1. gate (N, C) = sigmoid(fc_b relu(fc_a (w3 mean_h2 + b3))), accumulated in
+ * fp64 in a fixed order (no atomics): one launch, one workgroup per image. C <= 1024,
+ * R <= 64. */
+int rpst_se_gate(const float* mean_h2, const float* w3, const float* b3, const float* fc_a,
+                 const float* fc_b, float* gate, int N, int C, int R, rpst_stream_t stream);
+
+/* The conv that ends the block (attention.py:56-64): out = relu(gate[n, co] * (conv(input) +
+ * bias[co]) + residual), gate (N, Cout), residual and out (N, Cout, H, W). The gate is loaded
+ * once per output row beside the bias and the residual joins before the ReLU, in the direct
+ * kernel's epilogue. mean / std_out (N*Cout floats each; both NULL: not computed) receive
+ * calc_mean_std (base.py:399-407) of `out` as rpst_conv2d_stats returns it: from the
+ * statistics epilogue for Cout <= 64, from a reduction of the written output above that.
+ * Workspace: rpst_conv2d_gated_workspace_size bytes (may be 0; unused when mean is NULL).
+ * ksize must be 1 (RPST_EINVAL otherwise: no other gated kernel is built). */
+size_t rpst_conv2d_gated_workspace_size(int N, int Cin, int H, int W, int Cout, int ksize);
+int rpst_conv2d_gated(const float* input, const float* packed_weight, const float* bias,
+                      const float* gate, const float* residual, float* out, int N, int Cin,
+                      int H, int W, int Cout, int ksize, float* mean, float* std_out, float eps,
+                      void* workspace, size_t workspace_bytes, rpst_stream_t stream);
+
 /* MultiScaleAdaINRPNet skip fusion (adain_rp.py:301): out = act(conv(pad(x + AdaIN(c))) +
  * bias), x = `stylized` and c = `content` both (N,Cin,H,W), AdaIN with the calc_mean_std
  * statistics `params` = [mean_c | mean_s | std_c | std_s] (4*N*Cin floats, as

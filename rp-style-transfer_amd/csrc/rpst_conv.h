@@ -11,7 +11,8 @@ constexpr int kTW = 32;  // pixels per N sub-tile = one row segment
 
 struct ConvArgs {
   const float* in;
-  const float* aux;
+  const float* aux;   // (conv_mfma_kernel<GATED>, a 1x1 conv without a loader operator: the SE
+                      // gate per (n, co), N*Cout floats; rpst_conv2d_gated)
   const float* aux2;  // RPST_IN_ADD_ADAIN: the content feature c (N,Cin,H,W)
   const float* wpk;
   const float* bias;

@@ -33,7 +33,10 @@ namespace rpst {
 
 // CKK = input channels per kernel chunk (divides the packing chunk K::CK);
 // DB = double-buffered LDS (one barrier per chunk instead of two).
-template <int KS, int BM, int TH, int WM, int WN, int INOP, int NTH, int CKK, bool DB>
+// GATED: the SE epilogue out = relu(gate[n][co] * (acc + bias) + res) of rpst_conv2d_gated
+// (a 1x1 conv; the gate arrives in a.aux), compiled for launch_conv_gated's tiles only.
+template <int KS, int BM, int TH, int WM, int WN, int INOP, int NTH, int CKK, bool DB,
+          bool GATED = false>
 __global__ __launch_bounds__(NTH, 2) void conv_mfma_kernel(ConvArgs a) {
   using K = ConvK<KS>;
   constexpr int PCK = K::CK, TAPS = K::TAPS;
@@ -238,6 +241,23 @@ __global__ __launch_bounds__(NTH, 2) void conv_mfma_kernel(ConvArgs a) {
       if (co >= a.Cout) continue;
       const float b = a.bias ? a.bias[co] : 0.f;
       const int64_t pbase = ((int64_t)n * a.Cout + co) * a.H * a.W;
+      if constexpr (GATED) {
+        // SE block tail (reference network/attention.py:58-64): one gate per (n, co) row,
+        // loaded beside the bias; the residual joins before the ReLU
+        const float g = a.aux[(int64_t)n * a.Cout + co];  // aux: the gate
+#pragma unroll
+        for (int nt = 0; nt < NT; ++nt) {
+          const int y = y0 + wn * NT + nt;
+          float v = acc[mt][nt][r] + b;
+          if (y < a.H && x < a.W) {
+            const int64_t o = pbase + (int64_t)y * a.W + x;
+            v = fmaxf(fmaf(g, v, a.res[o]), 0.f);
+            a.out[o] = v;
+          }
+          acc[mt][nt][r] = v;
+        }
+        continue;
+      }
 #pragma unroll
       for (int nt = 0; nt < NT; ++nt) {
         const int y = y0 + wn * NT + nt;
@@ -602,10 +622,28 @@ static void launch_conv(const ConvArgs& a, int BM, hipStream_t st) {
 #undef RPST_LAUNCH
 }
 
-// the tile launch_conv runs; its statistics epilogue exists for >= 4 rows per wave only
-static ConvTiling direct_tiling(ConvArgs& a, int ksize, int in_op) {
+// The gated 1x1 conv on the same tiles. tall: 16 rows for the 32 / 64-channel tiles, so a wave
+// holds 4 rows and the statistics epilogue is compiled (the 8-row tile has 2 rows per wave).
+// Measured at 32 -> 32, 512^2 (profiles/se_attention/stats_tile_ab.log): 0.066 / 0.538 ms at
+// N = 2 / 16, against 0.066 / 0.562 ms for 8 rows on two waves of 4 rows (128 threads).
+static void launch_conv_gated(const ConvArgs& a, int BM, bool tall, hipStream_t st) {
+  const int blocks = a.tiles_x * a.tiles_y * a.N * a.co_tiles;
+#define RPST_LAUNCH(BM_, TH_, WM_, WN_, CK_, DB_)                                           \
+  conv_mfma_kernel<1, BM_, TH_, WM_, WN_, RPST_IN_NONE, 256, CK_, DB_, true><<<blocks, 256, 0, st>>>(a)
+  constexpr int C8 = ConvK<1>::CK, C4 = ConvK<1>::CK / 2;
+  if (BM == 128) RPST_LAUNCH(128, 4, 2, 2, C8, false);
+  else if (BM == 64 && tall) RPST_LAUNCH(64, 16, 1, 4, C4, true);
+  else if (tall) RPST_LAUNCH(32, 16, 1, 4, C4, true);
+  else if (BM == 64) RPST_LAUNCH(64, 8, 1, 4, C4, true);
+  else RPST_LAUNCH(32, 8, 1, 4, C4, true);
+#undef RPST_LAUNCH
+}
+
+// the tile launch_conv runs; its statistics epilogue exists for >= 4 rows per wave only.
+// tall: the 16-row tile of launch_conv_gated
+static ConvTiling direct_tiling(ConvArgs& a, int ksize, int in_op, bool tall = false) {
   const int bm = direct_bm(a.Cout), ck = ck_of(ksize);
-  const int th = bm == 128 && (ksize == 1 || heavy_loader(in_op)) ? 4 : 8;
+  const int th = bm == 128 ? (ksize == 1 || heavy_loader(in_op) ? 4 : 8) : (tall ? 16 : 8);
   const int wn = bm == 128 ? 2 : 4;  // waves along the tile rows
   a.Cout_pad = pad_cout(a.Cout);
   a.nchunks = (a.Cin + ck - 1) / ck;
@@ -716,6 +754,7 @@ static ConvArgs conv_shape(int N, int Cin, int Hs, int Ws, int Cout, int in_op) 
 // or rpst_conv2d_mix's T / offset).
 struct ConvNeeds {
   bool stats, residual, fold;
+  bool gated;  // the SE epilogue (rpst_conv2d_gated): a 1x1 conv, always a direct tile
 };
 
 // Everything decided about one launch, in one place. The launch, the statistics merge and the
@@ -727,6 +766,7 @@ struct ConvPlan {
   int op;        // the loader operator that launches: RPST_IN_NONE once AdaIN folds
   int rpt;       // narrow: rows per thread
   size_t wofs;   // floats from the packed buffer's start to the weight image that launches
+  bool tall;     // gated conv: the 16-row tile, whose statistics epilogue exists
   ConvTiling t;
 };
 
@@ -758,7 +798,8 @@ static ConvPlan conv_plan(ConvArgs& a, int ksize, int in_op, const ConvMode& m, 
     p.wofs = direct_packed_floats(a.Cout, a.Cin, ksize);
     p.t = wino_tiling(a, in_op);
   } else if (p.algo == RPST_CONV_DIRECT) {
-    p.t = direct_tiling(a, ksize, in_op);
+    p.tall = need.gated && need.stats && direct_bm(a.Cout) != 128;
+    p.t = direct_tiling(a, ksize, in_op, p.tall);
   }
   return p;
 }
@@ -883,6 +924,7 @@ struct ConvReq {
   int in2_from;
   const float* mask;  // ConvArgs::mask
   int pool_out;       // ConvArgs::pool_out
+  const float* gate;  // rpst_conv2d_gated: the SE gate, carried in ConvArgs::aux
   // rpst_conv2d_mix: conv(pad(T_n x + offset_n)) with both folded into fold_ws (wino4_mix);
   // the caller has checked that the plan folds
   const double* T;
@@ -924,6 +966,10 @@ static int conv_prepare(const ConvReq& r, const ConvMode& m, ConvArgs& a, ConvPl
   a.skip_from = r.skip_from;
   a.mask = r.mask;
   a.pool_out = r.pool_out;
+  if (r.gate) a.aux = r.gate;  // the gated 1x1 kernel has no loader operand
+  RPST_REQUIRE(!r.gate || (r.ksize == 1 && r.residual && r.in_op == RPST_IN_NONE && !r.mask &&
+                           !r.pool_out && !r.in2),
+               "conv2d_gated: a 1x1 conv with a residual and a plain input only");
   if (r.ksize == 3 && r.pad_mode == RPST_PAD_REFLECT)
     RPST_REQUIRE(a.H >= 2 && a.W >= 2, "conv2d: reflect padding needs H,W >= 2");
   RPST_REQUIRE((int64_t)r.N * (r.Cout > r.Cin ? r.Cout : r.Cin) * a.H * a.W < (1LL << 40),
@@ -933,7 +979,8 @@ static int conv_prepare(const ConvReq& r, const ConvMode& m, ConvArgs& a, ConvPl
   RPST_REQUIRE(((int64_t)r.Cin + 16) * r.Hs * r.Ws * 4 < (1LL << 31),
                "conv2d: one image's input exceeds 2 GiB");
   const bool fold = r.fold_ws && (r.in_op == RPST_IN_ADAIN || r.T);
-  p = conv_plan(a, r.ksize, r.in_op, m, {r.stat_part != nullptr, r.residual != nullptr, fold});
+  p = conv_plan(a, r.ksize, r.in_op, m,
+                {r.stat_part != nullptr, r.residual != nullptr, fold, r.gate != nullptr});
   RPST_REQUIRE(!r.pool_out || p.algo == RPST_CONV_WINOGRAD4,
                "conv2d_pool: the pooled-output epilogue exists on the F(4x4) path only "
                "(rpst_conv2d_algorithm == RPST_CONV_WINOGRAD4)");
@@ -984,6 +1031,10 @@ static int conv_launch(const ConvReq& r, ConvArgs& a, const ConvPlan& p) {
   RPST_REQUIRE(p.t.blocks <= 0x7fffffffLL, "conv2d: grid too large");
   if (r.ksize == 1) {
     RPST_REQUIRE(r.in_op == RPST_IN_NONE, "conv2d: 1x1 conv supports in_op NONE only");
+    if (r.gate) {
+      launch_conv_gated(a, direct_bm(a.Cout), p.tall, st);
+      return launch_status("conv_mfma_kernel (gated)");
+    }
     return launch_direct<1, RPST_IN_NONE>(a, st);
   }
   switch (r.in_op) {
@@ -1182,6 +1233,23 @@ extern "C" size_t rpst_conv2d_stats_workspace_size(int N, int Cin, int Hs, int W
          fold_bytes(N, Cin, Hs, Ws, Cout, ksize, in_op, m);
 }
 
+// the partials a statistics launch left in r.stat_part -> calc_mean_std
+static int stat_merge(const ConvReq& r, const ConvArgs& a, const ConvPlan& p, float* mean,
+                      float* std_out, float eps) {
+  const float2* part = r.stat_part;
+  if (p.t.stat_t) {
+    stat_merge_t_kernel<<<r.N * ((r.Cout + 63) / 64), 256, 0, r.st>>>(
+        part, mean, std_out, r.Cout, a.stat_P, a.tiles_x, p.t.stat_wn, p.t.stat_nt, p.t.stat_tw,
+        a.H, a.W, eps);
+    return launch_status("stat_merge_t_kernel");
+  }
+  const int planes = r.N * r.Cout;
+  stat_merge_kernel<<<(planes + 3) / 4, 256, 0, r.st>>>(part, mean, std_out, planes, a.stat_P,
+                                                        a.tiles_x, p.t.stat_wn, p.t.stat_nt,
+                                                        p.t.stat_tw, a.H, a.W, eps);
+  return launch_status("stat_merge_kernel");
+}
+
 static int conv2d_stats_impl(ConvReq r, float* mean, float* std_out, float eps, void* workspace,
                              size_t workspace_bytes, int store_n) {
   RPST_REQUIRE(mean && std_out, "conv2d_stats: null statistics pointer");
@@ -1211,18 +1279,7 @@ static int conv2d_stats_impl(ConvReq r, float* mean, float* std_out, float eps, 
                               (rpst_stream_t)r.st);
   }
   if (int e = conv_launch(r, a, p)) return e;
-  const float2* part = r.stat_part;
-  if (p.t.stat_t) {
-    stat_merge_t_kernel<<<r.N * ((r.Cout + 63) / 64), 256, 0, r.st>>>(
-        part, mean, std_out, r.Cout, a.stat_P, a.tiles_x, p.t.stat_wn, p.t.stat_nt, p.t.stat_tw,
-        a.H, a.W, eps);
-    return launch_status("stat_merge_t_kernel");
-  }
-  const int planes = r.N * r.Cout;
-  stat_merge_kernel<<<(planes + 3) / 4, 256, 0, r.st>>>(part, mean, std_out, planes, a.stat_P,
-                                                        a.tiles_x, p.t.stat_wn, p.t.stat_nt,
-                                                        p.t.stat_tw, a.H, a.W, eps);
-  return launch_status("stat_merge_kernel");
+  return stat_merge(r, a, p, mean, std_out, eps);
 }
 
 extern "C" int rpst_conv2d_stats_store(const float* input, const float* aux,
@@ -1249,6 +1306,55 @@ extern "C" int rpst_conv2d_stats(const float* input, const float* aux,
   return rpst_conv2d_stats_store(input, aux, packed_weight, bias, residual, out, N, Cin, Hs, Ws,
                                  Cout, ksize, pad_mode, in_op, relu, mean, std_out, eps, N,
                                  workspace, workspace_bytes, stream);
+}
+
+// ---- the conv that ends an SE block (reference network/attention.py:56-64) ------------
+// partials of the gated conv's statistics epilogue: 0 where its tile has none (Cout > 64: the
+// 128-channel 1x1 tile holds 2 rows per wave; the launch then reduces the written output)
+static size_t gated_stat_bytes(int N, int Cin, int H, int W, int Cout, int ksize) {
+  if (bad_shape(N, Cin, H, W, Cout, ksize) || ksize != 1) return 0;
+  ConvArgs a = conv_shape(N, Cin, H, W, Cout, RPST_IN_NONE);
+  const ConvPlan p = conv_plan(a, ksize, RPST_IN_NONE, conv_mode(), {true, true, false, true});
+  if (p.t.stat_nt < 4) return 0;
+  return ((size_t)N * Cout * a.stat_P * sizeof(float2) + 255) / 256 * 256;
+}
+
+extern "C" size_t rpst_conv2d_gated_workspace_size(int N, int Cin, int H, int W, int Cout,
+                                                   int ksize) {
+  return gated_stat_bytes(N, Cin, H, W, Cout, ksize);
+}
+
+extern "C" int rpst_conv2d_gated(const float* input, const float* packed_weight,
+                                 const float* bias, const float* gate, const float* residual,
+                                 float* out, int N, int Cin, int H, int W, int Cout, int ksize,
+                                 float* mean, float* std_out, float eps, void* workspace,
+                                 size_t workspace_bytes, rpst_stream_t stream) {
+  RPST_REQUIRE(ksize == 1, "conv2d_gated: the gated epilogue exists for 1x1 convs only, got "
+               "ksize %d", ksize);
+  RPST_REQUIRE(gate && residual, "conv2d_gated: null gate / residual");
+  RPST_REQUIRE((mean == nullptr) == (std_out == nullptr),
+               "conv2d_gated: mean and std_out are given together or not at all");
+  ConvReq r{.input = input, .packed_weight = packed_weight, .bias = bias, .residual = residual,
+            .out = out, .N = N, .Cin = Cin, .Hs = H, .Ws = W, .Cout = Cout, .ksize = ksize,
+            .pad_mode = RPST_PAD_ZERO, .in_op = RPST_IN_NONE, .relu = RPST_ACT_RELU,
+            .st = as_stream(stream), .gate = gate};
+  const ConvMode m = conv_mode();
+  if (!mean) return conv_common(r, m);
+  const size_t sb = gated_stat_bytes(N, Cin, H, W, Cout, ksize);
+  if (sb && (!workspace || workspace_bytes < sb)) {
+    set_error("conv2d_gated: workspace %zu < %zu bytes", workspace_bytes, sb);
+    return RPST_EWORKSPACE;
+  }
+  if (!sb) {  // no statistics epilogue on this tile: convolve, then reduce the output
+    if (int e = conv_common(r, m)) return e;
+    return rpst_calc_mean_std(out, mean, std_out, N, Cout, (int64_t)H * W, eps, stream);
+  }
+  r.stat_part = static_cast<float2*>(workspace);
+  ConvArgs a;
+  ConvPlan p;
+  if (int e = conv_prepare(r, m, a, p)) return e;
+  if (int e = conv_launch(r, a, p)) return e;
+  return stat_merge(r, a, p, mean, std_out, eps);
 }
 
 // ---- stand-alone max-pool / upsample (used where no conv follows directly) ----------

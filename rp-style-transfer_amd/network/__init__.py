@@ -14,13 +14,14 @@ from .base import (BaseNet, Conv2dBlock, SourceNet, StackType, adaptive_instance
                    build_decrease_depth_rp_blocks, build_increase_depth_rp_blocks, calc_mean_std,
                    decoder, rp_constant_conv_blocks, rp_deeper_conv_blocks,
                    rp_shallower_conv_blocks, vgg)
+from .attention import SEBottleneck, SELayer
 from .adain_rp import AdaIN, AdaINRPNet, MultiScaleAdaINRPNet
 from .sanet import (AdaptiveSAModel, AdaptiveSANet, AdaptiveTransform, AEALReluModule,
                     AEAModule, SAModel, SANet, Transform, cal_affinity_matrix,
                     mean_variance_norm)
 from .wct_rp import WCTRPNet, matrix_inv_sqrt, matrix_sqrt
 
-__all__ = ["BaseNet", "Conv2dBlock", "SourceNet", "StackType", "rp_constant_conv_blocks",
+__all__ = ["BaseNet", "Conv2dBlock", "SEBottleneck", "SELayer", "SourceNet", "StackType", "rp_constant_conv_blocks",
            "rp_deeper_conv_blocks", "rp_shallower_conv_blocks", "MultiScaleAdaINRPNet",
            "adaptive_instance_normalization", "build_decrease_depth_rp_blocks",
            "build_increase_depth_rp_blocks", "calc_mean_std", "decoder", "vgg", "AdaIN",

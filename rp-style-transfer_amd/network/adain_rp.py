@@ -140,12 +140,27 @@ def _block_plan(blk):
     return plan.compile_layers(plan.block_layers(blk))
 
 
+def _encode_se_block(blk, x, x2, n, stats):
+    """One encoder block with SE attention over the [content; style] batch of 2n: the conv
+    plan without statistics, then the SE block, whose gated conv emits calc_mean_std of the
+    block's output when `stats`. blk.attention_map becomes the style half's gates, as after
+    the reference's content-then-style encoding (adain_rp.py:286-290)."""
+    x = plan.run(_block_plan(blk), x, x2=x2)
+    res = ops.se_bottleneck(x, blk.attention_block, stats=stats)
+    gate = res[1][n:]
+    blk.attention_block.attention_map = blk.attention_block.se.attention_map = gate
+    blk.attention_map = gate
+    return (res[0], res[2], res[3]) if stats else res[0]
+
+
 class MultiScaleAdaINRPNet(AdaINRPNet):
     """Multi-scale AdaIN-RP (adain_rp.py:141-345): every encoder
     block's output is kept; decoding starts from AdaIN of the deepest level and, before
     each next decoder block, adds AdaIN of the next shallower level (adain_rp.py:291-302).
     Constant ('constant') and deeper/shallower ('deeper') stacks of Conv2dBlocks
-    (reflect pad, LeakyReLU 0.2). shuffle / sort are not on the kernel path.
+    (reflect pad, LeakyReLU 0.2). shuffle / sort are not on the kernel path. attention 'se'
+    (constant stack: an SEBottleneck after every encoder block, adain_rp.py:160-168) runs in
+    test() / decode() only: BatchNorm's batch statistics have no kernel, so forward() raises.
 
     test() runs the shared encoder once over [content; style]; each encoder block emits
     calc_mean_std of its output from its last conv's epilogue; the decoder's first conv
@@ -195,6 +210,9 @@ class MultiScaleAdaINRPNet(AdaINRPNet):
             raise NotImplementedError(
                 "MultiScaleAdaINRPNet: shuffle / sort have no rpst kernel path")
 
+    def _has_attention(self):
+        return any(blk.attention_block is not None for blk in self.rp_shared_encoder)
+
     def encode_rp_intermediate(self, input):
         results = [input]
         for i in range(len(self.rp_shared_encoder)):
@@ -218,7 +236,10 @@ class MultiScaleAdaINRPNet(AdaINRPNet):
                 x, x2 = content, style
                 feats = []  # feature over 2n per encoder block, no statistics
                 for blk in self.rp_shared_encoder:
-                    x = plan.run(_block_plan(blk), x, x2=x2)
+                    if blk.attention_block is not None:
+                        x = _encode_se_block(blk, x, x2, n, False)
+                    else:
+                        x = plan.run(_block_plan(blk), x, x2=x2)
                     x2 = None
                     feats.append(x)
                 y = self.decode([f[:n] for f in feats], [f[n:] for f in feats], True,
@@ -228,7 +249,10 @@ class MultiScaleAdaINRPNet(AdaINRPNet):
             x, x2 = content, style  # the first block reads both in place (no concat)
             levels = []  # (feature over 2n, mean, std) per encoder block
             for blk in self.rp_shared_encoder:
-                x, mean, std = plan.run(_block_plan(blk), x, stats_last=True, x2=x2)
+                if blk.attention_block is not None:
+                    x, mean, std = _encode_se_block(blk, x, x2, n, True)
+                else:
+                    x, mean, std = plan.run(_block_plan(blk), x, stats_last=True, x2=x2)
                 x2 = None
                 levels.append((x, mean, std))
 
@@ -281,6 +305,10 @@ class MultiScaleAdaINRPNet(AdaINRPNet):
         kernels; total_loss.backward() fills the RP encoder / decoder gradients); under
         no_grad it is evaluated op by op."""
         assert 0 <= alpha <= 1
+        if self._has_attention():
+            raise NotImplementedError(
+                "MultiScaleAdaINRPNet: 'se' attention is inference only (test / decode): "
+                "training-mode BatchNorm and the SE block's backward have no rpst kernel")
         if torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters()):
             self._kernel_path_check()
             from rpst.autograd import multiscale_losses

@@ -10,6 +10,7 @@ Same names, signatures, module structure and state_dict keys as the reference:
   adaptive_instance_normalization_with_segment  network/base.py:421-530 (batched)
   BaseNet                         network/base.py:533-559
   StackType, Conv2dBlock           network/base.py:18-23, 114-198
+  SELayer, SEBottleneck            network/attention.py:5-66 (re-exported from here)
   rp_deeper/shallower/constant_conv_blocks  network/base.py:229-311
   SourceNet (classic AdaIN)        network/base.py:562-649
 The Sequential stacks are rpst.plan.KernelSequential, so calling them runs the fused
@@ -25,6 +26,8 @@ import torch.nn as nn
 
 from rpst import ops, plan
 from rpst.plan import KernelSequential
+
+from .attention import SEBottleneck, SELayer  # noqa: F401 (re-exported, as the reference does)
 
 
 class StackType(object):
@@ -105,8 +108,9 @@ class Conv2dBlock(nn.Module):
     activation -> [attention], with the reference's attribute names (so state_dict keys
     match: conv.*, inception.{k}.0.*). The kernel path covers the configurations the
     reference's RP stacks use: reflect / zero padding 1, stride 1, norm 'none',
-    activation 'lrelu' (LeakyReLU 0.2) / 'relu' / 'none', optional inception, no
-    attention; other options raise NotImplementedError at construction."""
+    activation 'lrelu' (LeakyReLU 0.2) / 'relu' / 'none', optional inception, and 'se'
+    attention (an SEBottleneck after the activation, inference only) for output_dim >= 16;
+    other options raise NotImplementedError at construction."""
 
     def __init__(self, input_dim, output_dim, kernel_size, stride,
                  padding=0, norm='none', activation='lrelu', pad_type='reflect', inception_num=None,
@@ -141,13 +145,26 @@ class Conv2dBlock(nn.Module):
                 for _ in range(inception_num)])
         else:
             self.inception = None
-        if attention in ('se', 'sk'):
-            raise NotImplementedError(f"Conv2dBlock: '{attention}' attention has no rpst kernel")
-        self.attention_block = None
+        if attention == 'sk':
+            raise NotImplementedError("Conv2dBlock: 'sk' attention has no rpst kernel")
+        if attention == 'se' and output_dim < 16:
+            # the reference builds a zero-width squeeze here (output_dim // 16 == 0): every
+            # gate is exactly 0.5 and no config uses it
+            raise NotImplementedError(
+                f"Conv2dBlock: 'se' attention has no rpst kernel for output_dim {output_dim} "
+                "< 16 (the squeeze layer would have output_dim // 16 == 0 units)")
+        if attention == 'se':
+            self.attention_block = SEBottleneck(inplanes=output_dim, planes=output_dim)
+        else:
+            self.attention_block = None
         self.attention_map = None
 
     def forward(self, x):
-        return plan.run(plan.compile_layers(plan.block_layers(self)), x)
+        x = plan.run(plan.compile_layers(plan.block_layers(self)), x)
+        if self.attention_block is not None:
+            x = self.attention_block(x)
+            self.attention_map = self.attention_block.attention_map
+        return x
 
 
 def _blocks(dims, ks, stride, pd, activation, inception_num=None, attention=None):

@@ -532,6 +532,78 @@ def conv2d_stats(x: torch.Tensor, packed: torch.Tensor, bias: Optional[torch.Ten
     return out, mean, std
 
 
+def se_gate(mean_h2: torch.Tensor, w3: torch.Tensor, b3: torch.Tensor, fc_a: torch.Tensor,
+            fc_b: torch.Tensor) -> torch.Tensor:
+    """SE gate (network/attention.py:17-22 on conv3's pooled output): mean_h2 (N, C[, 1, 1]),
+    w3 (C, C) / b3 (C) = conv3 with bn3 folded, fc_a (R, C), fc_b (C, R) ->
+    sigmoid(fc_b relu(fc_a (w3 mean_h2 + b3))) of shape (N, C) (rpst_se_gate)."""
+    _check(mean_h2, w3, b3, fc_a, fc_b)
+    n, c = mean_h2.shape[:2]
+    if mean_h2.numel() != n * c:
+        raise ValueError(f"rpst: mean_h2 must be (N, C) or (N, C, 1, 1), got {tuple(mean_h2.shape)}")
+    r = fc_a.shape[0]
+    if tuple(w3.shape) != (c, c) or tuple(b3.shape) != (c,) or tuple(fc_a.shape) != (r, c) \
+            or tuple(fc_b.shape) != (c, r):
+        raise ValueError("rpst: se_gate needs w3 (C, C), b3 (C), fc_a (R, C), fc_b (C, R)")
+    mean_h2, w3, b3, fc_a, fc_b = (_c(t.detach()) for t in (mean_h2, w3, b3, fc_a, fc_b))
+    gate = torch.empty((n, c), device=mean_h2.device, dtype=torch.float32)
+    with _traced(f"se_gate C{c} R{r} N{n}", 0.0, 0.0):
+        _lib.call("rpst_se_gate", mean_h2.data_ptr(), w3.data_ptr(), b3.data_ptr(),
+                  fc_a.data_ptr(), fc_b.data_ptr(), gate.data_ptr(), n, c, r, _stream(mean_h2))
+    return gate
+
+
+def conv2d_gated(x: torch.Tensor, packed: torch.Tensor, bias: Optional[torch.Tensor],
+                 gate: torch.Tensor, residual: torch.Tensor, cout: int, ksize: int = 1,
+                 stats: bool = False, eps: float = 1e-5):
+    """out = relu(gate[n, co] * (conv_k(x) + bias) + residual) (rpst_conv2d_gated, the tail of
+    an SE block); stats: also calc_mean_std of out -> (out, mean, std)."""
+    assert x.dim() == 4
+    _check(x, packed, bias, gate, residual)
+    x, gate, residual = _c(x), _c(gate), _c(residual)
+    n, cin, h, w = x.shape
+    if gate.numel() != n * cout or gate.shape[0] != n:
+        raise ValueError(f"rpst: gate must be (N, Cout), got {tuple(gate.shape)}")
+    if tuple(residual.shape) != (n, cout, h, w):
+        raise ValueError("rpst: residual must have the output's shape")
+    out = torch.empty((n, cout, h, w), device=x.device, dtype=torch.float32)
+    mean = std = None
+    nbytes = 0
+    if stats:
+        mean = torch.empty((n, cout, 1, 1), device=x.device, dtype=torch.float32)
+        std = torch.empty_like(mean)
+        nbytes = _lib.load().rpst_conv2d_gated_workspace_size(n, cin, h, w, cout, ksize)
+    ws_t = torch.empty(nbytes, device=x.device, dtype=torch.uint8) if nbytes else None
+    with _traced(f"gated{ksize}x{ksize} {cin}->{cout} {h}x{w} N{n}",
+                 2.0 * n * cout * h * w * cin * ksize * ksize,
+                 4.0 * (x.numel() + 2 * out.numel())):
+        _lib.call("rpst_conv2d_gated", x.data_ptr(), packed.data_ptr(),
+                  _ptr(None if bias is None else _c(bias.detach())), gate.data_ptr(),
+                  residual.data_ptr(), out.data_ptr(), n, cin, h, w, cout, ksize, _ptr(mean),
+                  _ptr(std), eps, _ptr(ws_t), nbytes, _stream(x))
+    return (out, mean, std) if stats else out
+
+
+def se_bottleneck(x: torch.Tensor, block, stats: bool = False):
+    """An SEBottleneck (network/attention.py:25-66) in eval mode on x (N, C, H, W): conv1
+    (1x1, ReLU), conv2 (3x3 zero pad, ReLU, with the statistics epilogue for its mean), the
+    gate, the gated conv3 with residual x -> (out, gate (N, C, 1, 1)), or with stats (out,
+    gate, mean, std) where mean / std = calc_mean_std(out). The BatchNorms are folded from
+    their running statistics (rpst.plan.se_folded)."""
+    from . import plan
+    assert x.dim() == 4
+    _check(x)
+    x = _c(x)
+    c = x.shape[1]
+    (p1, b1), (p2, b2), (p3, b3), w3 = plan.se_folded(block)
+    h1 = conv2d(x, p1, b1, c, 1, relu=True)
+    h2, mean_h2, _ = conv2d_stats(h1, p2, b2, c, 3, pad=PAD_ZERO, relu=True)
+    gate = se_gate(mean_h2, w3, b3, block.se.fc[0].weight, block.se.fc[2].weight)
+    res = conv2d_gated(h2, p3, b3, gate, x, c, 1, stats=stats)
+    gate4 = gate.view(gate.shape[0], c, 1, 1)
+    return (res[0], gate4, res[1], res[2]) if stats else (res, gate4)
+
+
 def adain_params(mean_c, std_c, mean_s, std_s) -> torch.Tensor:
     """aux vector of RPST_IN_ADAIN: [mean_c | mean_s | std_c | std_s] (N*C each)."""
     return torch.cat([mean_c.reshape(-1), mean_s.reshape(-1), std_c.reshape(-1),

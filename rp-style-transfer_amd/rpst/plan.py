@@ -37,8 +37,9 @@ def _is_pad1(m: nn.Module) -> bool:
 
 def block_layers(blk: nn.Module) -> List[nn.Module]:
     """The layer sequence of a Conv2dBlock (network/base.py:187-198): pad, conv, the 1x1
-    inception convs, activation. Norm / attention variants are rejected at construction
-    by network.base.Conv2dBlock."""
+    inception convs, activation. Norm variants are rejected at construction by
+    network.base.Conv2dBlock; an 'se' attention block runs after this plan
+    (ops.se_bottleneck)."""
     layers = [blk.pad, blk.conv]
     if blk.inception is not None:
         layers += [seq[0] for seq in blk.inception]
@@ -128,6 +129,47 @@ def packed_weight(conv: nn.Conv2d) -> torch.Tensor:
         packed = ops.pack_conv_weight(w.detach())
     conv._rpst_packed = (key, packed)
     return packed
+
+
+def _tensor_key(t: torch.Tensor):
+    return (t.device, t.data_ptr(), t._version)
+
+
+def fold_batchnorm(conv: nn.Conv2d, bn: nn.BatchNorm2d):
+    """Eval-mode BatchNorm folded into the bias-free conv before it: -> (w', b') fp32 with
+    w' = w * g and b' = beta - running_mean * g per output channel, g = gamma /
+    sqrt(running_var + eps), formed in float64 and rounded once."""
+    g = bn.weight.detach().double() / torch.sqrt(bn.running_var.detach().double() + bn.eps)
+    w = (conv.weight.detach().double() * g.view(-1, 1, 1, 1)).float().contiguous()
+    b = (bn.bias.detach().double() - bn.running_mean.detach().double() * g).float().contiguous()
+    return w, b
+
+
+def se_folded(block: nn.Module):
+    """The kernel operands of an SEBottleneck (network/attention.py:25-66) in eval mode:
+    [(packed w1', b1'), (packed w2', b2'), (packed w3', b3'), w3' as a (C, C) matrix], every
+    BatchNorm folded into its conv. Cached on the module like packed_weight, keyed on the
+    device, data_ptr and _version of each conv weight and of its BatchNorm's weight, bias,
+    running_mean and running_var, so load_state_dict, .to() and in-place updates refresh it."""
+    pairs = ((block.conv1, block.bn1), (block.conv2, block.bn2), (block.conv3, block.bn3))
+    key = tuple(_tensor_key(t) for conv, bn in pairs
+                for t in (conv.weight, bn.weight, bn.bias, bn.running_mean, bn.running_var))
+    key += tuple(bn.eps for _, bn in pairs)
+    cached = getattr(block, "_rpst_se", None)
+    if cached is not None and cached[0] == key:
+        return cached[1]
+    with torch.no_grad():
+        folded = []
+        for conv, bn in pairs:
+            if conv.bias is not None or not bn.affine or not bn.track_running_stats:
+                raise NotImplementedError("rpst plan: SEBottleneck convs are bias-free and its "
+                                          "BatchNorms affine with running statistics")
+            w, b = fold_batchnorm(conv, bn)
+            folded.append((ops.pack_conv_weight(w), b))
+            if conv is block.conv3:
+                folded.append(w.view(w.shape[0], w.shape[1]))
+    block._rpst_se = (key, folded)
+    return folded
 
 
 def run_conv_step(step: ConvStep, x: torch.Tensor, aux=None, residual=None) -> torch.Tensor:

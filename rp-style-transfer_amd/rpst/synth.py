@@ -52,9 +52,33 @@ def conv_param(seed: int, key: str, shape: Tuple[int, ...]) -> np.ndarray:
     return v.astype(np.float32).reshape(shape)
 
 
+def attention_param(seed: int, key: str, shape: Tuple[int, ...]) -> np.ndarray:
+    """A tensor of an SEBottleneck (keys containing '.attention_block.'): conv weights by the
+    He-uniform rule; BatchNorm weight in [0.5, 1.5), bias in [-0.125, 0.125), running_mean in
+    [-0.5, 0.5), running_var in [0.5, 1.5), num_batches_tracked 0; the squeeze / excite Linear
+    weights uniform within +-1/sqrt(fan_in). (conv_param's 1-D rule would give negative
+    running variances and Linear weights so small that every gate sits at 0.5.)"""
+    leaf = key.rsplit(".", 1)[-1]
+    if leaf == "num_batches_tracked":
+        return np.zeros(shape, dtype=np.int64)
+    if len(shape) == 4:
+        return conv_param(seed, key, shape)
+    u = uniform01(seed, key, int(np.prod(shape)))
+    if len(shape) == 2:
+        v = (2.0 * u - 1.0) / np.sqrt(shape[1])
+    elif leaf in ("weight", "running_var"):
+        v = u + 0.5
+    elif leaf == "bias":
+        v = (2.0 * u - 1.0) * 0.125
+    else:  # running_mean
+        v = u - 0.5
+    return v.astype(np.float32).reshape(shape)
+
+
 def synth_state_dict(shapes: Iterable[Tuple[str, Tuple[int, ...]]], seed: int) -> Dict[str, np.ndarray]:
     """Fill every (key, shape) pair of a state_dict template."""
-    return {k: conv_param(seed, k, tuple(s)) for k, s in shapes}
+    return {k: (attention_param if ".attention_block." in k else conv_param)(seed, k, tuple(s))
+            for k, s in shapes}
 
 
 def synth_module_(module, seed: int) -> None:
