@@ -232,6 +232,31 @@ int rpst_conv2d_gated(const float* input, const float* packed_weight, const floa
                       int H, int W, int Cout, int ksize, float* mean, float* std_out, float eps,
                       void* workspace, size_t workspace_bytes, rpst_stream_t stream);
 
+/* ---- f7: 7x7 conv, stride 1, padding 3 (LDMSAdaINRPNet's big-receptive-field branch) ----
+ * Conv2dBlock(C, C, 7, 1, 3): ReflectionPad2d(3) + Conv2d(k=7) + LeakyReLU(0.2)
+ *   adain_rp.py:513-514 (rp_enc{i}_big_revf), base.py:114-198
+ * Weights are repacked once into the K-major image [ceil(Cin/8)][49 taps][8][Cout_pad]
+ * (channel chunk CK = 8; Cout_pad = Cout rounded up to the kernel's output-channel tile: 32
+ * for Cout <= 32, 64 for Cout <= 64, else 128), zero beyond Cin / Cout:
+ *   packed bytes = rpst_conv7_packed_size(Cout, Cin) = 4 * ceil(Cin/8) * 49 * 8 * Cout_pad.
+ * rpst_conv7: out[n, out_channel_offset + co, y, x] = act(bias[co] + sum w[co, ci, kh, kw] *
+ *   pad3(x)[n, ci, y + kh - 3, x + kw - 3]); input (N,Cin,H,W); out is a tensor of
+ *   out_channels_total channels per image of which only channels [out_channel_offset,
+ *   out_channel_offset + Cout) are written (a branch lands in its half of a concatenated
+ *   feature without a copy). pad_mode RPST_PAD_REFLECT = ReflectionPad2d(3), H, W >= 4;
+ *   RPST_PAD_ZERO = zero padding 3, any size. act: RPST_ACT_*. bias may be NULL.
+ *   input2 (may be NULL; otherwise N must be even): images n >= N/2 are read from it, image
+ *   N/2 first, as rpst_conv2d_pair reads its second input. The padding is resolved in the tile loader; no
+ *   padded copy is written. fp32 MFMA, exact products, k-ordered accumulation, no atomics:
+ *   deterministic, and image k's bits do not depend on the batch. */
+size_t rpst_conv7_packed_size(int Cout, int Cin);
+int rpst_conv7_pack(const float* weight, float* packed, int Cout, int Cin,
+                    rpst_stream_t stream);
+int rpst_conv7(const float* input, const float* input2, const float* packed_weight,
+               const float* bias, float* out, int N, int Cin, int H, int W, int Cout,
+               int pad_mode, int act, int out_channel_offset, int out_channels_total,
+               rpst_stream_t stream);
+
 /* MultiScaleAdaINRPNet skip fusion (adain_rp.py:301): out = act(conv(pad(x + AdaIN(c))) +
  * bias), x = `stylized` and c = `content` both (N,Cin,H,W), AdaIN with the calc_mean_std
  * statistics `params` = [mean_c | mean_s | std_c | std_s] (4*N*Cin floats, as

@@ -325,3 +325,182 @@ class MultiScaleAdaINRPNet(AdaINRPNet):
         loss_c = self.calc_content_loss(down_stylized_feats[-1], down_content_feats[-1])
         total_loss = self.config['content_weight'] * loss_c + self.config['style_weight'] * loss_s
         return {'style_loss': loss_s, 'content_loss': loss_c, 'total_loss': total_loss}, total_loss
+
+
+class LDMSAdaINRPNet(MultiScaleAdaINRPNet):
+    """Large-receptive-field multi-scale AdaIN-RP (adain_rp.py:484-567; `network: ld_adain`),
+    inference only. Every encoder level runs two Conv2dBlocks on the previous level and
+    concatenates them: rp_enc{i}_small_revf (3x3) and rp_enc{i}_big_revf (level 0: 3x3, 3 -> h;
+    level i >= 1: 7x7 pad 3, h 2^i -> h 2^i, the rpst_conv7 kernel), so level i has h 2^(i+1)
+    channels. decode() starts from rp_dec0(AdaIN(c[-1], s[-1])) and before every later block
+    adds AdaIN(stylized, s_i), whose content statistics are stylized's own (adain_rp.py:550);
+    use_mask takes the per-label AdaIN of (c_i, s_i) instead, as the parent does.
+
+    test() runs the encoder once over [content; style]; per level the 7x7 branch's kernel
+    writes the upper channel half of the level tensor in place and the 3x3 branch's half is
+    copied in (one strided copy: the 3x3 kernels have no channel-offset output). The decoder's
+    first conv applies AdaIN in its loader (RPST_IN_ADAIN) and every later block's first conv
+    forms stylized + AdaIN(stylized, s_i) in its loader (RPST_IN_ADD_ADAIN with the block
+    input as its own content and the statistics of the previous block's epilogue).
+
+    Deviations from the reference, both where it cannot run: stylized_layers < ld_layer_num
+    raises ValueError at construction (the reference adds a Python list to a tensor in decode),
+    and `resume: True` builds the modules and then loads the checkpoint that save() writes
+    (torch.save(self.state_dict())) strictly, begin taken from the file name (the reference
+    loads into the parent's encoder, which is None for this family). forward() with autograd
+    enabled raises: the 7x7 conv has no backward kernels."""
+
+    def __init__(self, config, vgg_encoder) -> None:
+        super().__init__(dict(config, resume=False), vgg_encoder)
+        self.config = config
+        self.hidden_dim = self.config['hidden_dim']
+        self.inception_num = config['inception_num']
+        self.layer_num = config['ld_layer_num']
+        self.stylized_layers = config['stylized_layers']
+        if self.stylized_layers < self.layer_num:
+            raise ValueError(
+                f"LDMSAdaINRPNet: stylized_layers ({self.stylized_layers}) < ld_layer_num "
+                f"({self.layer_num}) cannot be decoded (adain_rp.py:543-552 adds a list to a "
+                "tensor)")
+        self.build_encoders()
+        self.build_decoders()
+        if self.config['resume']:
+            checkpoint_path = self.config['checkpoint_path']
+            self.begin = int(os.path.splitext(os.path.basename(checkpoint_path))[0])
+            self.load_state_dict(torch.load(checkpoint_path, weights_only=True), strict=True)
+
+    def build_encoders(self):
+        hidden_dim = self.hidden_dim
+        for name in ('small', 'big'):
+            setattr(self, f'rp_enc0_{name}_revf',
+                    Conv2dBlock(3, hidden_dim, 3, 1, 1, inception_num=self.inception_num))
+        for i in range(self.layer_num - 1):
+            hidden_dim *= 2
+            setattr(self, f'rp_enc{i + 1}_small_revf',
+                    Conv2dBlock(hidden_dim, hidden_dim, 3, 1, 1, inception_num=self.inception_num))
+            setattr(self, f'rp_enc{i + 1}_big_revf',
+                    Conv2dBlock(hidden_dim, hidden_dim, 7, 1, 3, inception_num=self.inception_num))
+        self.encoder_out_dim = hidden_dim
+
+    def build_decoders(self):
+        # stylized_layers >= ld_layer_num: every block reads a level-wide (2 x hidden) input
+        hidden_dim = self.encoder_out_dim
+        for i in range(self.layer_num - 1):
+            setattr(self, f'rp_dec{i}',
+                    Conv2dBlock(hidden_dim * 2, hidden_dim, 3, 1, 1,
+                                inception_num=self.inception_num))
+            hidden_dim //= 2
+        setattr(self, f'rp_dec{self.layer_num - 1}',
+                Conv2dBlock(hidden_dim * 2, 3, 3, 1, 1, inception_num=self.inception_num))
+
+    def _has_attention(self):
+        return False
+
+    def _enc(self, i, name):
+        return getattr(self, f'rp_enc{i}_{name}_revf')
+
+    def encode_rp_intermediate(self, input):
+        results = [input]
+        for i in range(self.layer_num):
+            results.append(self._encode_level(i, results[-1], None))
+        return results[1:]
+
+    def _encode_level(self, i, x, x2):
+        """Level i over x (or the batch [x; x2]): cat([small(x), big(x)], dim=1) without the
+        cat. A 7x7 big branch whose block is the conv and its activation alone writes the upper
+        half of the level tensor from its kernel; otherwise (level 0, inception 1x1s) the
+        branch's output is copied in like the small one's."""
+        small = plan.run(_block_plan(self._enc(i, 'small')), x, x2=x2)
+        n, c, h, w = small.shape
+        level = torch.empty((n, 2 * c, h, w), device=small.device, dtype=torch.float32)
+        level[:, :c].copy_(small)
+        steps = _block_plan(self._enc(i, 'big'))
+        if len(steps) == 1 and plan.is_k7(steps[0]):
+            plan.run_conv7_step(steps[0], x, out=level, out_channel_offset=c, x2=x2)
+        else:
+            level[:, c:].copy_(plan.run(steps, x, x2=x2))
+        return level
+
+    def _skip_block(self, i, stylized, stats, style_stats, want_stats=False):
+        """rp_dec{i}(stylized + AdaIN(stylized, style)) with the sum formed in the block's
+        first conv loader; stats = calc_mean_std(stylized), style_stats that of the style
+        level. want_stats: also calc_mean_std of the result (from the last conv's epilogue
+        unless that conv is the skip-AdaIN one, which has none) -> (y, mean, std)."""
+        steps = _block_plan(getattr(self, f'rp_dec{i}'))
+        aux = ops.adain_params(stats[0], stats[1], style_stats[0], style_stats[1])
+        epilogue = want_stats and len(steps) > 1
+        y = plan.run(steps, stylized, first_aux=aux, first_in_op=ops.IN_ADD_ADAIN,
+                     first_content=stylized, stats_last=epilogue)
+        if want_stats and not epilogue:
+            return (y,) + tuple(ops.calc_mean_std(y))
+        return y
+
+    def test(self, content, style, iterations=0, bid=0, c_mask_path=None, s_mask_path=None):
+        self.eval()
+        with torch.no_grad():
+            self._kernel_path_check()
+            use_mask = self.config['use_mask']
+            if not FUSED_ADAIN:
+                y = self.decode(self.encode_rp_intermediate(content),
+                                self.encode_rp_intermediate(style), use_mask=use_mask,
+                                c_mask_path=c_mask_path, s_mask_path=s_mask_path)
+                self.train()
+                return y
+            n = content.shape[0]
+            x, x2 = content, style  # level 0 reads both in place (no concat)
+            feats = []
+            for i in range(self.layer_num):
+                x = self._encode_level(i, x, x2)
+                x2 = None
+                feats.append(x)
+            if use_mask:
+                y = self.decode([f[:n] for f in feats], [f[n:] for f in feats], True,
+                                c_mask_path, s_mask_path)
+                self.train()
+                return y
+            mean, std = ops.calc_mean_std(feats[-1])
+            last = self.layer_num == 1
+            y = plan.run(_block_plan(self.rp_dec0), feats[-1][:n],
+                         first_aux=ops.adain_params(mean[:n], std[:n], mean[n:], std[n:]),
+                         first_in_op=ops.IN_ADAIN, stats_last=not last)
+            for i, f in enumerate(feats[:-1][::-1]):
+                y, ym, ys = y
+                y = self._skip_block(i + 1, y, (ym, ys), ops.calc_mean_std(f[n:]),
+                                     want_stats=i < self.layer_num - 2)
+            self.train()
+            return y
+
+    def decode(self, content_feats, style_feats, use_mask=False, c_mask_path=None, s_mask_path=None):
+        """adain_rp.py:538-553, op by op."""
+        self._kernel_path_check()
+        pairs = list(zip(content_feats[:-1], style_feats[:-1]))[::-1]
+        if use_mask:
+            n, dev = content_feats[-1].shape[0], content_feats[-1].device
+            c_seg = segment_maps(c_mask_path, n, content_feats[-1].shape[2:], dev)
+            s_seg = segment_maps(s_mask_path, n, style_feats[-1].shape[2:], dev)
+            stylized, seg_plan = masked_adain_batch(content_feats[-1], style_feats[-1], c_seg,
+                                                    s_seg)
+            stylized = self.rp_dec0(stylized)
+            for i, (content_feat, style_feat) in enumerate(pairs):
+                fused, _ = masked_adain_batch(content_feat, style_feat, c_seg, s_seg,
+                                              skip=stylized, plan=seg_plan)
+                stylized = getattr(self, f'rp_dec{i + 1}')(fused)
+            return stylized
+        stylized = self.rp_dec0(AdaIN(content_feats[-1], style_feats[-1]))
+        for i, (content_feat, style_feat) in enumerate(pairs):
+            # rp_dec{i+1}(stylized + AdaIN(stylized, style_feat))
+            stylized = self._skip_block(i + 1, stylized, calc_mean_std(stylized),
+                                        calc_mean_std(style_feat))
+        return stylized
+
+    def save(self, save_path, iterations=0):
+        torch.save(self.state_dict(), save_path)
+
+    def forward(self, content, style, alpha=1.0):
+        """The parent's loss dict (adain_rp.py:322-345) under no_grad; with autograd enabled
+        and trainable parameters it raises: ld_adain has no 7x7 backward kernels."""
+        if torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters()):
+            raise NotImplementedError(
+                "LDMSAdaINRPNet (ld_adain) is inference only: the 7x7 conv has no backward "
+                "kernels; call forward() under torch.no_grad()")
+        return super().forward(content, style, alpha)

@@ -107,7 +107,8 @@ class Conv2dBlock(nn.Module):
     """Conv2dBlock (base.py:114-198): pad -> conv -> [1x1 inception convs] -> [norm] ->
     activation -> [attention], with the reference's attribute names (so state_dict keys
     match: conv.*, inception.{k}.0.*). The kernel path covers the configurations the
-    reference's RP stacks use: reflect / zero padding 1, stride 1, norm 'none',
+    reference's RP stacks use: reflect / zero padding 1 with a 3x3 kernel or padding 3 with a
+    7x7 kernel (LDMSAdaINRPNet's big branch), stride 1, norm 'none',
     activation 'lrelu' (LeakyReLU 0.2) / 'relu' / 'none', optional inception, and 'se'
     attention (an SEBottleneck after the activation, inference only) for output_dim >= 16;
     other options raise NotImplementedError at construction."""

@@ -59,6 +59,9 @@ SIGNATURES = {
     "rpst_conv2d_gated_workspace_size": (_SZ, [_I, _I, _I, _I, _I, _I]),
     "rpst_conv2d_gated": (_I, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P, _P, _F, _P,
                                _SZ, _P]),
+    "rpst_conv7_packed_size": (_SZ, [_I, _I]),
+    "rpst_conv7_pack": (_I, [_P, _P, _I, _I, _P]),
+    "rpst_conv7": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P]),
     "rpst_maxpool2x2_ceil": (_I, [_P, _P, _I, _I, _I, _I, _P]),
     "rpst_upsample_nearest2x": (_I, [_P, _P, _I, _I, _I, _I, _P]),
     "rpst_add_upsample_nearest2x": (_I, [_P, _P, _P, _I, _I, _I, _I, _P]),

@@ -275,6 +275,52 @@ def pack_conv_weight(weight: torch.Tensor) -> torch.Tensor:
     return packed
 
 
+def pack_conv7_weight(weight: torch.Tensor) -> torch.Tensor:
+    """Repack (Cout,Cin,7,7) fp32 weights into the 7x7 kernel's K-major layout
+    (rpst_conv7_pack)."""
+    _check(weight)
+    weight = _c(weight.detach())
+    cout, cin, kh, kw = weight.shape
+    assert kh == 7 and kw == 7, "pack_conv7_weight takes 7x7 kernels"
+    nbytes = _lib.load().rpst_conv7_packed_size(cout, cin)
+    packed = torch.empty(nbytes // 4, device=weight.device, dtype=torch.float32)
+    _lib.call("rpst_conv7_pack", weight.data_ptr(), packed.data_ptr(), cout, cin,
+              _stream(weight))
+    return packed
+
+
+def conv2d_k7(x: torch.Tensor, packed: torch.Tensor, bias: Optional[torch.Tensor], cout: int,
+              pad: int = PAD_REFLECT, act=ACT_NONE, out: Optional[torch.Tensor] = None,
+              out_channel_offset: int = 0, x2: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """act(conv7x7(pad3(x)) + bias) (rpst_conv7), written to channels [out_channel_offset,
+    out_channel_offset + cout) of `out` (a contiguous (N, C_total, H, W) tensor whose other
+    channels are left alone; default: a new (N, cout, H, W) tensor). x2: the conv runs over
+    the batch cat([x, x2]) of two equal halves, read in place. Returns `out`."""
+    assert x.dim() == 4
+    _check(x, x2, packed, bias, out)
+    x = _c(x)
+    n, cin, h, w = x.shape
+    if x2 is not None:
+        if x2.shape != x.shape:
+            raise ValueError("rpst: conv2d_k7's second input must have the first one's shape")
+        x2 = _c(x2)
+        n *= 2
+    if out is None:
+        if out_channel_offset:
+            raise ValueError("rpst: conv2d_k7 with a channel offset needs the tensor to write into")
+        out = torch.empty((n, cout, h, w), device=x.device, dtype=torch.float32)
+    elif out.dim() != 4 or not out.is_contiguous() or out.shape[0] != n or \
+            tuple(out.shape[2:]) != (h, w) or out.device != x.device:
+        raise ValueError(f"rpst: out must be a contiguous fp32 ({n}, C, {h}, {w}) tensor on the "
+                         "input's device")
+    with _traced(f"conv7x7 {cin}->{cout} {h}x{w} N{n}", 2.0 * n * cout * h * w * cin * 49,
+                 4.0 * n * (cin + cout) * h * w):
+        _lib.call("rpst_conv7", x.data_ptr(), _ptr(x2), packed.data_ptr(),
+                  _ptr(None if bias is None else _c(bias.detach())), out.data_ptr(), n, cin, h,
+                  w, cout, pad, _act(act), int(out_channel_offset), out.shape[1], _stream(x))
+    return out
+
+
 def conv_out_hw(h: int, w: int, in_op: int) -> Tuple[int, int]:
     if in_op == IN_MAXPOOL2:
         return (h + 1) // 2, (w + 1) // 2

@@ -3,6 +3,8 @@
 The reference builds its stacks from plain layers (network/base.py:25-111,363-396,
 sanet.py:162-192) and Conv2dBlocks (base.py:114-198): [MaxPool2d | Upsample] ->
 [ReflectionPad2d | ZeroPad2d] -> Conv2d -> [ReLU | LeakyReLU(0.2)].
+Convs are 1x1, 3x3 (pad 1) or 7x7 (pad 3: LDMSAdaINRPNet's big-receptive-field blocks,
+adain_rp.py:513-514, one rpst_conv7 launch, no input operator).
 Each such group becomes ONE rpst_conv2d launch: the pool/upsample and the padding are
 applied by the conv kernel's tile loader and ReLU by its epilogue, so no intermediate
 (padded, pooled or upsampled) tensor is ever written to HBM.
@@ -35,6 +37,10 @@ def _is_pad1(m: nn.Module) -> bool:
     return isinstance(m, (nn.ReflectionPad2d, nn.ZeroPad2d)) and tuple(m.padding) == (1, 1, 1, 1)
 
 
+def _is_pad3(m: nn.Module) -> bool:
+    return isinstance(m, (nn.ReflectionPad2d, nn.ZeroPad2d)) and tuple(m.padding) == (3, 3, 3, 3)
+
+
 def block_layers(blk: nn.Module) -> List[nn.Module]:
     """The layer sequence of a Conv2dBlock (network/base.py:187-198): pad, conv, the 1x1
     inception convs, activation. Norm variants are rejected at construction by
@@ -53,6 +59,7 @@ def compile_layers(layers: Iterable[nn.Module]) -> List[object]:
     in_op = ops.IN_NONE
     reflect = False
     zero_pad = False
+    pad3 = False  # the pending pad layer is a pad-3 one: only a 7x7 conv may follow
     last_conv: Optional[ConvStep] = None
     for m in layers:
         if isinstance(m, (nn.ReLU, nn.LeakyReLU)):
@@ -79,8 +86,9 @@ def compile_layers(layers: Iterable[nn.Module]) -> List[object]:
                 raise NotImplementedError("rpst plan: upsample after pad/op")
             in_op = ops.IN_UPSAMPLE2
         elif isinstance(m, (nn.ReflectionPad2d, nn.ZeroPad2d)):
-            if not _is_pad1(m) or reflect or zero_pad:
+            if not (_is_pad1(m) or _is_pad3(m)) or reflect or zero_pad:
                 raise NotImplementedError(f"rpst plan: unsupported {m}")
+            pad3 = _is_pad3(m)
             if isinstance(m, nn.ReflectionPad2d):
                 reflect = True
             else:
@@ -88,10 +96,18 @@ def compile_layers(layers: Iterable[nn.Module]) -> List[object]:
         elif isinstance(m, nn.Conv2d):
             k = tuple(m.kernel_size)
             if (tuple(m.stride) != (1, 1) or tuple(m.dilation) != (1, 1) or m.groups != 1
-                    or k not in ((1, 1), (3, 3))):
+                    or k not in ((1, 1), (3, 3), (7, 7))):
                 raise NotImplementedError(f"rpst plan: unsupported {m}")
             pad_t = tuple(m.padding)
-            if k == (3, 3):
+            if pad3 != (k == (7, 7)):
+                raise NotImplementedError(f"rpst plan: unsupported padding for {m}")
+            if k == (7, 7):
+                # ReflectionPad2d(3) / ZeroPad2d(3) + Conv2d(k=7): rpst_conv7, which has no
+                # loader operator
+                if pad_t != (0, 0) or in_op != ops.IN_NONE:
+                    raise NotImplementedError(f"rpst plan: unsupported 7x7 conv {m}")
+                pad = ops.PAD_REFLECT if reflect else ops.PAD_ZERO
+            elif k == (3, 3):
                 if reflect and pad_t == (0, 0):
                     pad = ops.PAD_REFLECT
                 elif zero_pad and pad_t == (0, 0):
@@ -107,7 +123,7 @@ def compile_layers(layers: Iterable[nn.Module]) -> List[object]:
             step = ConvStep(m, pad, in_op, ops.ACT_NONE)
             steps.append(step)
             last_conv = step
-            in_op, reflect, zero_pad = ops.IN_NONE, False, False
+            in_op, reflect, zero_pad, pad3 = ops.IN_NONE, False, False, False
         else:
             raise NotImplementedError(f"rpst plan: unsupported layer {type(m).__name__}")
     if reflect or zero_pad:
@@ -126,7 +142,8 @@ def packed_weight(conv: nn.Conv2d) -> torch.Tensor:
     if cached is not None and cached[0] == key:
         return cached[1]
     with torch.no_grad():
-        packed = ops.pack_conv_weight(w.detach())
+        pack = ops.pack_conv7_weight if tuple(w.shape[2:]) == (7, 7) else ops.pack_conv_weight
+        packed = pack(w.detach())
     conv._rpst_packed = (key, packed)
     return packed
 
@@ -172,8 +189,24 @@ def se_folded(block: nn.Module):
     return folded
 
 
+def is_k7(step) -> bool:
+    return isinstance(step, ConvStep) and step.conv.kernel_size[0] == 7
+
+
+def run_conv7_step(step: ConvStep, x: torch.Tensor, out=None, out_channel_offset: int = 0,
+                   x2=None) -> torch.Tensor:
+    """A 7x7 ConvStep through rpst_conv7; out / out_channel_offset: ops.conv2d_k7."""
+    c = step.conv
+    return ops.conv2d_k7(x, packed_weight(c), c.bias, c.out_channels, pad=step.pad,
+                         act=step.relu, out=out, out_channel_offset=out_channel_offset, x2=x2)
+
+
 def run_conv_step(step: ConvStep, x: torch.Tensor, aux=None, residual=None) -> torch.Tensor:
     c = step.conv
+    if is_k7(step):
+        if step.in_op != ops.IN_NONE or aux is not None or residual is not None:
+            raise NotImplementedError("rpst plan: a 7x7 conv has no input operator / residual")
+        return run_conv7_step(step, x)
     return ops.conv2d(x, packed_weight(c), c.bias, c.out_channels, c.kernel_size[0],
                       pad=step.pad, in_op=step.in_op, relu=step.relu, aux=aux,
                       residual=residual)
@@ -189,17 +222,24 @@ def run(steps: List[object], x: torch.Tensor, first_aux=None, first_in_op=None,
     stats_last makes the last conv also return calc_mean_std of its output -> (x, mean,
     std); with store_n that conv writes only images < store_n of x (the rest are needed only
     through their statistics; their part of x is unspecified). x2: the plan runs over the
-    batch cat([x, x2]); a plain first conv reads both in place (rpst_conv2d_pair), any
-    other first step gets the concatenation."""
+    batch cat([x, x2]); a plain first conv reads both in place (rpst_conv2d_pair, or
+    rpst_conv7's second input for a 7x7 conv over two equal halves), any other first step
+    gets the concatenation."""
     mean = std = None
+    if steps and is_k7(steps[0]) and (first_in_op is not None or first_mix is not None):
+        raise NotImplementedError("rpst plan: a 7x7 conv has no AdaIN loader / colour mix")
     if x2 is not None:
         s0 = steps[0] if steps else None
         pair = (isinstance(s0, ConvStep) and s0.in_op == ops.IN_NONE and first_mix is None
-                and first_in_op is None and not (stats_last and len(steps) == 1))
+                and first_in_op is None and not (stats_last and len(steps) == 1)
+                and (not is_k7(s0) or x.shape == x2.shape))  # rpst_conv7: two equal halves
         if pair:
             c = s0.conv
-            x = ops.conv2d_pair(x, x2, packed_weight(c), c.bias, c.out_channels,
-                                c.kernel_size[0], pad=s0.pad, relu=s0.relu)
+            if is_k7(s0):
+                x = run_conv7_step(s0, x, x2=x2)
+            else:
+                x = ops.conv2d_pair(x, x2, packed_weight(c), c.bias, c.out_channels,
+                                    c.kernel_size[0], pad=s0.pad, relu=s0.relu)
             steps = steps[1:]
             if not steps:
                 if stats_last:
@@ -221,6 +261,12 @@ def run(steps: List[object], x: torch.Tensor, first_aux=None, first_in_op=None,
             c = s.conv
             x = ops.conv2d_mix(x, first_mix[0], first_mix[1], packed_weight(c), c.bias,
                                c.out_channels, c.kernel_size[0], pad=s.pad, relu=s.relu)
+            continue
+        if is_k7(s):
+            # no statistics epilogue: a last 7x7 conv's statistics come from calc_mean_std of
+            # the written output (below)
+            x = run_conv7_step(s, x)
+            pooled_in = False
             continue
         if isinstance(s, ConvStep):
             in_op, aux = s.in_op, None

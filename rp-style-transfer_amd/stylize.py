@@ -9,12 +9,12 @@ stylises every pair of `test_dir` into `<output>/test/test_output/{cn}-{sn}.png`
 `{cn}-{sn}-cat.png` through rpst.imageio.Pipeline (decode / PNG encode on host threads,
 ToTensor and save_image's pixel path on the GPU). With `use_mask: True` and
 `test_dataset: photoreal` the pipeline also decodes each pair's two segmentation masks and
-`src` / `multi_adain` stylise per label.
+`src` / `multi_adain` / `ld_adain` stylise per label.
 
 Differences from test.py, by design: no TensorBoard writer, no per-step cv2 import, the
 test.py:135 `iterations=i` NameError is not reproduced (iterations=0 is passed), and
 `--synthetic-weights SEED` replaces the checkpoints with rpst.synth weights (offline
-runs, tests). Networks outside the hot path (sel_multi_adain, ld_adain*, mrf, spade) and
+runs, tests). Networks outside the hot path (sel_multi_adain, ld_adain2 and later, mrf, spade) and
 the 'fmt' dataset (single images, which test.py's loop cannot unpack) raise.
 """
 from __future__ import annotations
@@ -34,10 +34,11 @@ logging.basicConfig(level=logging.INFO,
                     format="%(asctime)s - %(name)s - %(levelname)s - %(message)s")
 logger = logging.getLogger("stylize")
 
-OUT_OF_SCOPE = ("sel_multi_adain", "ld_adain", "ld_adain2", "mrf", "spade")
+OUT_OF_SCOPE = ("sel_multi_adain", "ld_adain2", "ld_adain3", "ld_adain4", "ld_adain5", "mrf",
+                "spade")
 
 
-MASKED_NETWORKS = ("src", "multi_adain")  # networks whose test() honours use_mask
+MASKED_NETWORKS = ("src", "multi_adain", "ld_adain")  # networks whose test() honours use_mask
 
 
 def mask_size(kind, img_size):
@@ -67,6 +68,8 @@ def build_network(opt, synthetic_seed=None):
         m = net.AdaINRPNet(opt, vgg_relu4_1)
     elif kind == "multi_adain":
         m = net.MultiScaleAdaINRPNet(opt, vgg_relu4_1)
+    elif kind == "ld_adain":  # test.py:102-103
+        m = net.LDMSAdaINRPNet(opt, vgg_relu4_1)
     elif kind == "wct":
         m = net.WCTRPNet(opt, vgg_relu4_1)
     elif kind == "dynamic_sanet":
@@ -116,7 +119,7 @@ def main(argv=None) -> int:
     network.eval()
     dataset = DATASETS[opt["test_dataset"]](opt["test_dir"])
 
-    # use_mask (test.py:128-136 passes the dataset's mask paths on): the two networks whose
+    # use_mask (test.py:128-136 passes the dataset's mask paths on): the networks whose
     # test() reads them get the label maps decoded ahead by the pipeline
     masks = bool(opt.get("use_mask")) and opt["network"] in MASKED_NETWORKS
     if masks and opt["test_dataset"] != "photoreal":
