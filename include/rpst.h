@@ -434,6 +434,26 @@ int rpst_conv_wgrad(const float* x, const float* dy, float* dw, float* db, int N
 int rpst_conv_wgrad_pad(const float* x, const float* dy, float* dw, float* db, int N, int Cin,
                         int H, int W, int Cout, int pad, void* workspace,
                         size_t workspace_bytes, rpst_stream_t stream);
+/* conv7x7 (stride 1, pad 3: rpst_conv7) weight / bias gradient, LDMSAdaINRPNet's big branch
+ * (adain_rp.py:513-514) in training: x (N,Cin,H,W) the conv input, dy (N,Cout,H,W) the gradient
+ * at its (pre-activation) output -> dw[co][ci][kh][kw] = sum over (n,y,x) of dy[n][co][y][x] *
+ * pad3(x)[n][ci][y+kh-3][x+kw-3] (Cout,Cin,7,7), db[co] = sum dy (db may be NULL). pad_mode
+ * RPST_PAD_REFLECT (ReflectionPad2d(3); H, W >= 4) or RPST_PAD_ZERO (any size), resolved in the
+ * loader (no padded copy). fp32 MFMA, exact products, split over pixels with the partials
+ * summed in a fixed order, no atomics: two calls give the same bits. Any Cin, Cout >= 1.
+ * Workspace: rpst_conv7_wgrad_workspace_size(N, Cin, H, W, Cout).
+ * The data gradient is rpst_conv7 with zero padding on the weights of rpst_conv_weight_flip
+ * (ksize 7) packed by rpst_conv7_pack; for a reflect-padded conv it runs on dy embedded in zeros
+ * over the padded domain (H+6) x (W+6) and rpst_reflect_pad_backward folds the result. */
+size_t rpst_conv7_wgrad_workspace_size(int N, int Cin, int H, int W, int Cout);
+int rpst_conv7_wgrad(const float* x, const float* dy, float* dw, float* db, int N, int Cin,
+                     int H, int W, int Cout, int pad_mode, void* workspace,
+                     size_t workspace_bytes, rpst_stream_t stream);
+/* ReflectionPad2d(pad) backward: gp (planes, H + 2 pad, W + 2 pad) the gradient of the padded
+ * tensor -> dx (planes, H, W), every padded position summed into the pixel it reflects, in a
+ * fixed order (pad < H, W; with H or W <= 2 pad both mirrors reach the same pixels). */
+int rpst_reflect_pad_backward(const float* gp, float* dx, int64_t planes, int H, int W, int pad,
+                              rpst_stream_t stream);
 /* adaptive_instance_normalization backward (base.py:410-418): g the gradient at the AdaIN
  * output, c / s the content / style features (planes x HW), stats = [mean_c | std_c |
  * mean_s | std_s] (planes each) -> dc, ds. Workspace: 2*planes floats. */

@@ -579,7 +579,7 @@ static inline unsigned blocks_for(int64_t n, int per = 256) { return (unsigned)(
 
 extern "C" int rpst_conv_weight_flip(const float* w, float* wt, int Cout, int Cin, int ksize,
                                      rpst_stream_t stream) {
-  RPST_REQUIRE(w && wt && Cout > 0 && Cin > 0 && (ksize == 1 || ksize == 3),
+  RPST_REQUIRE(w && wt && Cout > 0 && Cin > 0 && (ksize == 1 || ksize == 3 || ksize == 7),
                "conv_weight_flip: bad args");
   const int64_t n = (int64_t)Cout * Cin * ksize * ksize;
   conv_flip_kernel<<<blocks_for(n), 256, 0, as_stream(stream)>>>(w, wt, Cout, Cin, ksize);

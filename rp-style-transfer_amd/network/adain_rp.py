@@ -328,8 +328,8 @@ class MultiScaleAdaINRPNet(AdaINRPNet):
 
 
 class LDMSAdaINRPNet(MultiScaleAdaINRPNet):
-    """Large-receptive-field multi-scale AdaIN-RP (adain_rp.py:484-567; `network: ld_adain`),
-    inference only. Every encoder level runs two Conv2dBlocks on the previous level and
+    """Large-receptive-field multi-scale AdaIN-RP (adain_rp.py:484-567; `network: ld_adain`).
+    Every encoder level runs two Conv2dBlocks on the previous level and
     concatenates them: rp_enc{i}_small_revf (3x3) and rp_enc{i}_big_revf (level 0: 3x3, 3 -> h;
     level i >= 1: 7x7 pad 3, h 2^i -> h 2^i, the rpst_conv7 kernel), so level i has h 2^(i+1)
     channels. decode() starts from rp_dec0(AdaIN(c[-1], s[-1])) and before every later block
@@ -348,7 +348,8 @@ class LDMSAdaINRPNet(MultiScaleAdaINRPNet):
     and `resume: True` builds the modules and then loads the checkpoint that save() writes
     (torch.save(self.state_dict())) strictly, begin taken from the file name (the reference
     loads into the parent's encoder, which is None for this family). forward() with autograd
-    enabled raises: the 7x7 conv has no backward kernels."""
+    enabled raises; training goes through rpst.autograd.ld_losses (train.py routes
+    `network: ld_adain` there)."""
 
     def __init__(self, config, vgg_encoder) -> None:
         super().__init__(dict(config, resume=False), vgg_encoder)
@@ -498,7 +499,8 @@ class LDMSAdaINRPNet(MultiScaleAdaINRPNet):
 
     def forward(self, content, style, alpha=1.0):
         """The parent's loss dict (adain_rp.py:322-345) under no_grad; with autograd enabled
-        and trainable parameters it raises: ld_adain has no 7x7 backward kernels."""
+        and trainable parameters it raises. The differentiable loss dict is
+        rpst.autograd.ld_losses(model, content, style), which train.py calls for this network."""
         if torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters()):
             raise NotImplementedError(
                 "LDMSAdaINRPNet (ld_adain) is inference only: the 7x7 conv has no backward "

@@ -79,6 +79,9 @@ SIGNATURES = {
     "rpst_conv_wgrad_workspace_size": (_SZ, [_I, _I, _I, _I, _I]),
     "rpst_conv_wgrad": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _P, _SZ, _P]),
     "rpst_conv_wgrad_pad": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P, _SZ, _P]),
+    "rpst_conv7_wgrad_workspace_size": (_SZ, [_I, _I, _I, _I, _I]),
+    "rpst_conv7_wgrad": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P, _SZ, _P]),
+    "rpst_reflect_pad_backward": (_I, [_P, _P, _I64, _I, _I, _I, _P]),
     "rpst_adain_backward": (_I, [_P, _P, _P, _P, _P, _P, _I, _I64, _P, _SZ, _P]),
     "rpst_style_content_loss_grad": (_I, [_P, _P, _P, _P, _P, _I, _I64, _I, _P]),
     "rpst_sq_diff_workspace_size": (_SZ, []),

@@ -29,7 +29,9 @@ train loop (backward + Adam) trains on the HIP path. The steps are built from sh
 Steps: _AdaINRPStep (RP encoder over [content; style], AdaIN, RP decoder), _WCTRPStep (the
 RP decoder on a constant WCT feature), _SAModelStep (transform + decoder over three
 branches), _SourceNetStep (decoder on AdaIN of frozen VGG features), _MultiScaleStep (block
-encoder / decoder with an AdaIN per level); the *_losses functions are their entry points.
+encoder / decoder with an AdaIN per level), _LDStep (LDMSAdaINRPNet: two-branch levels with
+the 7x7 conv's backward kernels, csrc/rpst_conv7_train.hip); the *_losses functions are their
+entry points.
 """
 from __future__ import annotations
 
@@ -47,8 +49,9 @@ def _ws(nbytes: int, like: torch.Tensor) -> torch.Tensor:
 
 
 def flip_packed_weight(conv: nn.Conv2d) -> torch.Tensor:
-    """Packed flip-transposed weights (Cin, Cout, k, k) of conv for its dgrad, cached on the
-    module like plan.packed_weight (refreshed after optimizer steps)."""
+    """Packed flip-transposed weights (Cin, Cout, k, k) of conv for its dgrad (a 7x7 conv's
+    in rpst_conv7's layout), cached on the module like plan.packed_weight (refreshed after
+    optimizer steps)."""
     w = conv.weight
     key = (w.device, w.data_ptr(), w._version)
     cached = getattr(conv, "_rpst_flip_packed", None)
@@ -60,7 +63,7 @@ def flip_packed_weight(conv: nn.Conv2d) -> torch.Tensor:
         wt = torch.empty((cin, cout, k, k), device=wd.device, dtype=torch.float32)
         _lib.call("rpst_conv_weight_flip", wd.data_ptr(), wt.data_ptr(), cout, cin, k,
                   _stream(wd))
-        packed = ops.pack_conv_weight(wt)
+        packed = ops.pack_conv7_weight(wt) if k == 7 else ops.pack_conv_weight(wt)
     conv._rpst_flip_packed = (key, packed)
     return packed
 
@@ -92,6 +95,8 @@ def conv_dgrad(g: torch.Tensor, step: plan.ConvStep,
     bit (rpst_conv2d_masked, rpst_reflect_pad_border_grad_masked)."""
     c = step.conv
     k = c.kernel_size[0]
+    if k == 7:
+        return _conv7_dgrad(g, step)
     if mask is None:
         dx = ops.conv2d(g, flip_packed_weight(c), None, c.in_channels, k, pad=ops.PAD_ZERO)
     else:
@@ -104,6 +109,27 @@ def conv_dgrad(g: torch.Tensor, step: plan.ConvStep,
         _lib.call("rpst_reflect_pad_border_grad_masked", g.data_ptr(), wd.data_ptr(),
                   None if mask is None else mask.data_ptr(), dx.data_ptr(), n, c.in_channels,
                   c.out_channels, h, w, ws.data_ptr(), nbytes, _stream(g))
+    return dx
+
+
+def _conv7_dgrad(g: torch.Tensor, step: plan.ConvStep) -> torch.Tensor:
+    """7x7 pad-3 dgrad: rpst_conv7 with zero padding on the flip-transposed weights. Behind
+    ReflectionPad2d(3) it runs on g embedded in zeros over the padded domain (H+6) x (W+6),
+    which is the gradient of the padded input, and rpst_reflect_pad_backward sums every padded
+    position into the pixel it mirrors (2.4 % more conv FLOPs at 512 x 512)."""
+    c = step.conv
+    pk = flip_packed_weight(c)
+    if step.pad != ops.PAD_REFLECT:
+        return ops.conv2d_k7(g, pk, None, c.in_channels, pad=ops.PAD_ZERO)
+    n, co, h, w = g.shape
+    ge = torch.zeros((n, co, h + 6, w + 6), device=g.device, dtype=torch.float32)
+    ge[:, :, 3:h + 3, 3:w + 3].copy_(g)
+    gp = ops.conv2d_k7(ge, pk, None, c.in_channels, pad=ops.PAD_ZERO)
+    dx = torch.empty((n, c.in_channels, h, w), device=g.device, dtype=torch.float32)
+    with ops._traced(f"reflect3 fold C{c.in_channels} {h}x{w} N{n}", 0.0,
+                     4.0 * (gp.numel() + dx.numel())):
+        _lib.call("rpst_reflect_pad_backward", gp.data_ptr(), dx.data_ptr(),
+                  n * c.in_channels, h, w, 3, _stream(g))
     return dx
 
 
@@ -148,6 +174,28 @@ def conv_wgrad(x: torch.Tensor, g: torch.Tensor, conv: nn.Conv2d, pad: int = ops
     with ops._traced(f"wgrad3x3 {cin}->{cout} {h}x{w} N{n} op0{' reflect' if pad else ''}",
                      2.0 * n * cout * cin * 9 * h * w, 4.0 * (x.numel() + g.numel())):
         _lib.call("rpst_conv_wgrad_pad", x.data_ptr(), g.data_ptr(), dw.data_ptr(),
+                  None if db is None else db.data_ptr(), n, cin, h, w, cout, int(pad),
+                  ws.data_ptr(), nbytes, _stream(x))
+    return dw, db
+
+
+def conv_wgrad7(x: torch.Tensor, g: torch.Tensor, conv: nn.Conv2d, pad: int = ops.PAD_REFLECT):
+    """7x7 pad-3 conv weight / bias gradient (rpst_conv7_wgrad); pad = ops.PAD_REFLECT for
+    ReflectionPad2d(3) + conv, ops.PAD_ZERO for zero padding, read in the kernel's loader.
+    The traced bytes count x and g once per kernel row (the kernel's blocks split the taps by
+    row and each reads both)."""
+    ops._check(x, g)
+    n, cin, h, w = x.shape
+    cout = conv.out_channels
+    assert conv.kernel_size == (7, 7) and tuple(g.shape) == (n, cout, h, w)
+    x, g = ops._c(x), ops._c(g)
+    dw = torch.empty_like(conv.weight, memory_format=torch.contiguous_format)
+    db = torch.empty_like(conv.bias) if conv.bias is not None else None
+    nbytes = _lib.load().rpst_conv7_wgrad_workspace_size(n, cin, h, w, cout)
+    ws = _ws(nbytes, x)
+    with ops._traced(f"wgrad7x7 {cin}->{cout} {h}x{w} N{n}{' reflect' if pad else ''}",
+                     2.0 * n * cout * cin * 49 * h * w, 4.0 * (7 * x.numel() + 7 * g.numel())):
+        _lib.call("rpst_conv7_wgrad", x.data_ptr(), g.data_ptr(), dw.data_ptr(),
                   None if db is None else db.data_ptr(), n, cin, h, w, cout, int(pad),
                   ws.data_ptr(), nbytes, _stream(x))
     return dw, db
@@ -205,8 +253,9 @@ def _stack_backward(steps, saved, g, grads: Dict[int, torch.Tensor], need_input_
     """Backward through compiled conv steps from g at the last output: 3x3 convs with zero or
     reflect padding (wgrad kernel, the reflection read in its loader; dgrad + reflect border
     fold), optionally behind a nearest x2 upsample (sanet.py:162-192: fused into the conv's
-    loader forward, materialised for the wgrad), and 1x1 convs (Conv2dBlock's inception
-    convs, base.py:166-171: weight gradient as a batched GEMM), each with its ReLU /
+    loader forward, materialised for the wgrad), 7x7 convs with zero or reflect padding 3
+    (LDMSAdaINRPNet's big branch: conv_wgrad7, _conv7_dgrad), and 1x1 convs (Conv2dBlock's
+    inception convs, base.py:166-171: weight gradient as a batched GEMM), each with its ReLU /
     LeakyReLU(0.2) epilogue. Parameter gradients add into grads; returns d input (None when
     not needed)."""
     masked = False  # g already thresholded by step k's ReLU (fused into the dgrad above)
@@ -221,6 +270,8 @@ def _stack_backward(steps, saved, g, grads: Dict[int, torch.Tensor], need_input_
         x = ops.upsample_nearest2x(x_in) if up else x_in
         if s.conv.kernel_size[0] == 3:
             dw, db = conv_wgrad(x, g, s.conv, s.pad)
+        elif s.conv.kernel_size[0] == 7:
+            dw, db = conv_wgrad7(x, g, s.conv, s.pad)
         else:
             dw, db = _lin_grads(g, x)
             db = db if s.conv.bias is not None else None
@@ -789,6 +840,90 @@ class _MultiScaleStep(torch.autograd.Function):
                 ge = _stack_backward(*ctx.enc[i], ge, grads, need_input_grad=i > 0)
         ctx.enc = ctx.dec = ctx.states = None
         return (None, None, None, None, *[grads.get(id(p)) for p in ctx.params])
+
+
+class _LDStep(torch.autograd.Function):
+    """LDMSAdaINRPNet's loss graph (adain_rp.py:484-567 under the parent's forward,
+    adain_rp.py:321-345).
+
+    Forward: per level both branches (3x3 small, 7x7 big; level 0 two 3x3) run over the
+    [content; style] batch with every conv's input / output kept, and their outputs are
+    concatenated into the level; rp_dec0 on AdaIN(c_{L-1}, s_{L-1}), then rp_dec{j} on
+    y + AdaIN(y, s_{L-1-j}), the content statistics being y's own (adain_rp.py:550); VGG
+    losses on the stylized batch.
+    Backward: VGG dgrad -> decoder blocks; at a skip block with input gradient g,
+    (dc, ds) = AdaIN backward of g at (y, s_i): g + dc goes on to the previous block and ds to
+    the style half of level i (the content halves below the top level reach the loss only
+    through the level above). The encoder walks back level by level: the level's gradient is
+    split at the channel midpoint into the small and the big branch, each goes through
+    _stack_backward, and the two input gradients are summed with the level below's."""
+
+    @staticmethod
+    def forward(ctx, content, style, model, cfg, *params):
+        with ops.precise_convs("ld"):
+            n = content.shape[0]
+            x, enc, levels = torch.cat([content, style], dim=0), [], []
+            for i in range(model.layer_num):
+                branches = []
+                for name in ("small", "big"):
+                    st = plan.compile_layers(plan.block_layers(model._enc(i, name)))
+                    branches.append((st,) + _run_steps_saving(st, x))
+                enc.append([(st, sv) for st, _, sv in branches])
+                x = torch.cat([y for _, y, _ in branches], dim=1)
+                levels.append(x)
+            L = len(levels)
+            dec, states = [], []
+            y = None
+            for k in range(L):
+                sf = levels[L - 1 - k][n:]
+                cf = levels[L - 1][:n] if k == 0 else y
+                states.append(_adain_state(cf, sf))
+                z = ops.adaptive_instance_normalization(cf, sf)
+                if k:
+                    z.add_(y)
+                st = plan.compile_layers(plan.block_layers(getattr(model, f"rp_dec{k}")))
+                y, sv = _run_steps_saving(st, z)
+                dec.append((st, sv))
+            loss = _VGGLoss(model, y, content, style, *cfg)
+        ctx.loss, ctx.enc, ctx.dec, ctx.states, ctx.params = loss, enc, dec, states, params
+        return loss.total, loss.ls, loss.lc
+
+    @staticmethod
+    def backward(ctx, g_total, g_ls, g_lc):
+        with ops.precise_convs("ld"):
+            g = ctx.loss.backward(g_total, g_ls, g_lc)
+            grads: Dict[int, torch.Tensor] = {}
+            L = len(ctx.enc)
+            n = g.shape[0]
+            dlev = [None] * L
+            for k in range(L - 1, -1, -1):
+                g = _stack_backward(*ctx.dec[k], g, grads, need_input_grad=True)
+                d = _adain_backward(g, ctx.states[k])  # [d content; d style]
+                if k:
+                    g = g + d[:n]   # the skip and AdaIN's own content, both the block below
+                    d[:n].zero_()
+                dlev[L - 1 - k] = d
+            ge = None
+            for i in range(L - 1, -1, -1):
+                ge = dlev[i] if ge is None else ge.add_(dlev[i])
+                c = ge.shape[1] // 2
+                dx = None
+                for (st, sv), gb in zip(ctx.enc[i], (ge[:, :c], ge[:, c:])):
+                    d = _stack_backward(st, sv, gb.contiguous(), grads, need_input_grad=i > 0)
+                    dx = d if dx is None else dx.add_(d)
+                ge = dx
+        ctx.enc = ctx.dec = ctx.states = None
+        return (None, None, None, None, *[grads.get(id(p)) for p in ctx.params])
+
+
+def ld_losses(model, content: torch.Tensor, style: torch.Tensor):
+    """LDMSAdaINRPNet's training entry: the loss dict of the reference's forward
+    ({'style_loss', 'content_loss', 'total_loss'}) and total_loss, differentiable w.r.t. every
+    rp_enc* / rp_dec* parameter (the VGG is frozen). The model's forward() with autograd
+    enabled keeps raising; train.py calls this instead."""
+    model._kernel_path_check()
+    params = [p for name, p in model.named_parameters() if name.startswith(("rp_enc", "rp_dec"))]
+    return _losses(_LDStep, model, content, style, params)
 
 
 def sourcenet_losses(model, content: torch.Tensor, style: torch.Tensor):

@@ -362,7 +362,12 @@ def _conv_name(ksize, cin, cout, hs, ws, n, in_op):
 # Where a training step runs F(4x4) it runs the 32-channel form (rpst_conv2d_set_precise(2)),
 # not the position-quarter kernel: on the quarter kernel SourceNet's decoder.1.weight gradient
 # reads 7.4e-4 against its 6.0e-4 floor bar (RPST_TRAIN_QUARTER=1 is the A/B switch).
-TRAIN_F4 = {"adain": False, "multiscale": True, "wct": True, "sanet": False, "source": True}
+#   LDMSAdaINRPNet ("ld"): precise. F(4x4) on its 3x3 chains is 3.3 % faster (600.3 -> 580.3 ms
+#     a step at N = 4, 512^2; the step's time is the 7x7 branch's, which has one form) and reads
+#     rp_enc0_small_revf.conv.weight 9.7e-4 against its 1e-4 bar in the CPU-autograd check at
+#     hidden 8, 16x24 (profiles/ld_train/train_forms.log).
+TRAIN_F4 = {"adain": False, "multiscale": True, "wct": True, "sanet": False, "source": True,
+            "ld": False}
 
 
 class precise_convs:
