@@ -3,14 +3,14 @@
 //
 //   wgrad   conv7_wgrad_kernel: implicit GEMM dW[co][ci][kh][kw] = sum over (n,y,x) of
 //           dY[n][co][y][x] pad3(X)[n][ci][y+kh-3][x+kw-3] on fp32 MFMA, split over K (pixels)
-//           with a fixed-order reduction (wgrad7_reduce_kernel); the bias gradient from the
-//           staged dY tiles. The padding (reflect or zero) is resolved in the loader.
+//           with a fixed-order reduction (wgrad_reduce_kernel, rpst_train.h); the bias gradient
+//           from the staged dY tiles. The padding (reflect or zero) is resolved in the loader.
 //   dgrad   = rpst_conv7 on flip-transposed weights with zero padding (rpst_conv_weight_flip,
 //           rpst_conv7_pack). A reflect-padded conv runs it on dY embedded in zeros over the
 //           padded domain, (H+6) x (W+6), which gives the gradient of the padded input, and
 //           reflect_pad_backward_kernel sums every padded position into the pixel it mirrors.
 // All reductions are fixed-order (no float atomics): results are deterministic.
-#include "rpst_common.h"
+#include "rpst_train.h"
 
 namespace rpst {
 
@@ -153,27 +153,6 @@ __global__ __launch_bounds__(256, 2) void conv7_wgrad_kernel(
   }
 }
 
-// dw[i] = sum over splits of part[k][i], in split order: wgrad_reduce_kernel of rpst_train.hip
-// restated (a kernel cannot be launched from another translation unit without relocatable
-// device code, which this library is not built with)
-__global__ __launch_bounds__(256) void wgrad7_reduce_kernel(const float* __restrict__ part,
-                                                            float* __restrict__ dw, int64_t n,
-                                                            int splits) {
-  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  if (i >= n) return;
-  float s = 0.f;
-  int k = 0;
-  for (; k + 8 <= splits; k += 8) {
-    float v[8];
-#pragma unroll
-    for (int u = 0; u < 8; ++u) v[u] = part[(int64_t)(k + u) * n + i];
-#pragma unroll
-    for (int u = 0; u < 8; ++u) s += v[u];
-  }
-  for (; k < splits; ++k) s += part[(int64_t)k * n + i];
-  dw[i] = s;
-}
-
 // ---- ReflectionPad2d(pad) backward -----------------------------------------------------------
 // gp: planes of (H + 2 pad) x (W + 2 pad), the gradient of the padded tensor; dx[i][j] = the sum
 // of gp over every padded position that reads (i, j): its own, and the mirrored ones. Along one
@@ -259,11 +238,11 @@ extern "C" int rpst_conv7_wgrad(const float* x, const float* dy, float* dw, floa
       pad_mode == RPST_PAD_REFLECT);
   if (int e = launch_status("conv7_wgrad_kernel")) return e;
   const int64_t n = (int64_t)Cout * Cin * 49;
-  wgrad7_reduce_kernel<<<(unsigned)((n + 255) / 256), 256, 0, st>>>(part, dw, n, splits);
-  if (int e = launch_status("wgrad7_reduce_kernel")) return e;
+  wgrad_reduce_kernel<<<(unsigned)((n + 255) / 256), 256, 0, st>>>(part, dw, n, splits);
+  if (int e = launch_status("wgrad_reduce_kernel")) return e;
   if (db) {
-    wgrad7_reduce_kernel<<<(unsigned)((Cout + 255) / 256), 256, 0, st>>>(bpart, db, Cout, splits);
-    return launch_status("wgrad7_reduce_kernel(bias)");
+    wgrad_reduce_kernel<<<(unsigned)((Cout + 255) / 256), 256, 0, st>>>(bpart, db, Cout, splits);
+    return launch_status("wgrad_reduce_kernel(bias)");
   }
   return RPST_OK;
 }

@@ -7,7 +7,7 @@
 //                       columns it reflects (reflect_ring_kernel + reflect_fold_kernel)
 //   conv wgrad        conv_wgrad_kernel: implicit GEMM dW[co][ci][tap] = sum over (n,y,x) of
 //                       dY[n][co][y][x] X[n][ci][y+dy][x+dx] on fp32 MFMA, split over K
-//                       (pixels) with a fixed-order reduction (wgrad_reduce_kernel)
+//                       (pixels) with a fixed-order reduction (wgrad_reduce_kernel, rpst_train.h)
 //   bias grad         reduced by the wgrad kernel's first ci-tile blocks from their dY tiles
 //   ReLU / max-pool   relu_backward_kernel, maxpool2_backward_kernel (argmax = first max in
 //                       window order, NaN wins, as ATen's max_pool2d)
@@ -17,7 +17,7 @@
 // All reductions are fixed-order (no float atomics): results are deterministic.
 #include <cstdlib>
 
-#include "rpst_common.h"
+#include "rpst_train.h"
 
 namespace rpst {
 
@@ -447,25 +447,6 @@ __global__ __launch_bounds__(256, 2) void conv_wgrad_kernel(
 #pragma unroll
     for (int t = 0; t < 9; ++t) o[t] = acc[t][r];
   }
-}
-
-__global__ __launch_bounds__(256) void wgrad_reduce_kernel(const float* __restrict__ part,
-                                                           float* __restrict__ dw, int64_t n,
-                                                           int splits) {
-  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  if (i >= n) return;
-  // 8 independent loads in flight, summed in split order
-  float s = 0.f;
-  int k = 0;
-  for (; k + 8 <= splits; k += 8) {
-    float v[8];
-#pragma unroll
-    for (int u = 0; u < 8; ++u) v[u] = part[(int64_t)(k + u) * n + i];
-#pragma unroll
-    for (int u = 0; u < 8; ++u) s += v[u];
-  }
-  for (; k < splits; ++k) s += part[(int64_t)k * n + i];
-  dw[i] = s;
 }
 
 // ---- AdaIN backward ----------------------------------------------------------------------

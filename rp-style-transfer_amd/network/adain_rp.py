@@ -172,7 +172,11 @@ class MultiScaleAdaINRPNet(AdaINRPNet):
     segmentation label (masks resized to the image size, which every level shares, so the
     label counts and validity are planned once); the masked kernels write stylized +
     AdaINSeg(c_i, s_i) once per level and the decoder block reads it as a plain input. The
-    encoder then emits no epilogue statistics."""
+    encoder then emits no epilogue statistics.
+
+    test() (the unfused, masked and fused routes, one exit), decode() with its masked loop and
+    forward() serve the whole family: LDMSAdaINRPNet overrides only the hooks listed below
+    _kernel_path_check."""
 
     def __init__(self, config, vgg_encoder) -> None:
         super().__init__(config, vgg_encoder)
@@ -210,8 +214,22 @@ class MultiScaleAdaINRPNet(AdaINRPNet):
             raise NotImplementedError(
                 "MultiScaleAdaINRPNet: shuffle / sort have no rpst kernel path")
 
+    # What a family of this shape defines (LDMSAdaINRPNet overrides these and nothing else of
+    # test() / decode() / forward()): the rpst.autograd entry point of forward(), the blocks of
+    # encoder level i, decoder block k, a level over the [content; style] pair
+    # (_encode_level), the fused decode (_decode_fused) and the unmasked skip rule of decode()
+    # (_decode_skip).
+    _losses_entry = 'multiscale_losses'
+
+    def _level_blocks(self, i):
+        return [self.rp_shared_encoder[i]]
+
+    def _dec(self, k):
+        return self.rp_decoder[k]
+
     def _has_attention(self):
-        return any(blk.attention_block is not None for blk in self.rp_shared_encoder)
+        return any(blk.attention_block is not None
+                   for i in range(self.layer_num) for blk in self._level_blocks(i))
 
     def encode_rp_intermediate(self, input):
         results = [input]
@@ -219,61 +237,66 @@ class MultiScaleAdaINRPNet(AdaINRPNet):
             results.append(self.rp_shared_encoder[i](results[-1]))
         return results[1:]
 
+    def _encode_level(self, i, x, x2, n, stats):
+        """Encoder level i over the [content; style] batch of 2n, given as x (or as x and x2,
+        read in place: no concat); stats: -> (feature, mean, std), calc_mean_std of the
+        feature from the last conv's epilogue."""
+        blk = self.rp_shared_encoder[i]
+        if blk.attention_block is not None:
+            return _encode_se_block(blk, x, x2, n, stats)
+        return plan.run(_block_plan(blk), x, stats_last=stats, x2=x2)
+
+    def _encode_pair(self, content, style, stats=False):
+        """Every level over [content; style], the encoder run once."""
+        x, x2, levels = content, style, []
+        for i in range(self.layer_num):
+            levels.append(self._encode_level(i, x, x2, content.shape[0], stats))
+            x, x2 = (levels[-1][0] if stats else levels[-1]), None
+        return levels
+
     def test(self, content, style, iterations=0, bid=0, c_mask_path=None, s_mask_path=None):
         self.eval()
         with torch.no_grad():
             self._kernel_path_check()
+            use_mask = self.config['use_mask']
+            n = content.shape[0]
             if not FUSED_ADAIN:
                 content_feats = self.encode_rp_intermediate(content)
                 style_feats = self.encode_rp_intermediate(style)
-                stylized = self.decode(content_feats, style_feats,
-                                       use_mask=self.config['use_mask'],
-                                       c_mask_path=c_mask_path, s_mask_path=s_mask_path)
-                self.train()
-                return stylized
-            n = content.shape[0]
-            if self.config['use_mask']:
-                x, x2 = content, style
-                feats = []  # feature over 2n per encoder block, no statistics
-                for blk in self.rp_shared_encoder:
-                    if blk.attention_block is not None:
-                        x = _encode_se_block(blk, x, x2, n, False)
-                    else:
-                        x = plan.run(_block_plan(blk), x, x2=x2)
-                    x2 = None
-                    feats.append(x)
+                y = self.decode(content_feats, style_feats, use_mask=use_mask,
+                                c_mask_path=c_mask_path, s_mask_path=s_mask_path)
+            elif use_mask:
+                feats = self._encode_pair(content, style)  # no epilogue statistics
                 y = self.decode([f[:n] for f in feats], [f[n:] for f in feats], True,
                                 c_mask_path, s_mask_path)
-                self.train()
-                return y
-            x, x2 = content, style  # the first block reads both in place (no concat)
-            levels = []  # (feature over 2n, mean, std) per encoder block
-            for blk in self.rp_shared_encoder:
-                if blk.attention_block is not None:
-                    x, mean, std = _encode_se_block(blk, x, x2, n, True)
-                else:
-                    x, mean, std = plan.run(_block_plan(blk), x, stats_last=True, x2=x2)
-                x2 = None
-                levels.append((x, mean, std))
+            else:
+                y = self._decode_fused(content, style, n)
+        self.train()
+        return y
 
-            def params(lv):
-                _, m, s = lv
-                return ops.adain_params(m[:n], s[:n], m[n:], s[n:])
+    def _decode_fused(self, content, style, n):
+        """test() without masks: every level's statistics come from its encoder epilogue and
+        every AdaIN (and skip sum) is formed in a decoder block's first conv loader."""
+        levels = self._encode_pair(content, style, stats=True)  # (feature over 2n, mean, std)
 
-            feats = levels[-1][0]
-            y = plan.run(_block_plan(self.rp_decoder[0]), feats[:n],
-                         first_aux=params(levels[-1]), first_in_op=ops.IN_ADAIN)
-            for i, lv in enumerate(levels[:-1][::-1]):
-                y = plan.run(_block_plan(self.rp_decoder[i + 1]), y, first_aux=params(lv),
-                             first_in_op=ops.IN_ADD_ADAIN, first_content=lv[0][:n])
-            self.train()
-            return y
+        def params(lv):
+            _, m, s = lv
+            return ops.adain_params(m[:n], s[:n], m[n:], s[n:])
+
+        y = plan.run(_block_plan(self._dec(0)), levels[-1][0][:n],
+                     first_aux=params(levels[-1]), first_in_op=ops.IN_ADAIN)
+        for i, lv in enumerate(levels[:-1][::-1]):
+            y = plan.run(_block_plan(self._dec(i + 1)), y, first_aux=params(lv),
+                         first_in_op=ops.IN_ADD_ADAIN, first_content=lv[0][:n])
+        return y
 
     def decode(self, content_feats, style_feats, use_mask=False, c_mask_path=None, s_mask_path=None):
-        """adain_rp.py:291-302, op by op: AdaIN kernels, then each block with the skip
-        sum formed in its first conv's loader. use_mask: per-label AdaIN at every level
-        (do_mask_stylized), the skip sum formed by the masked apply kernel."""
+        """adain_rp.py:291-302 (LDMSAdaINRPNet: 538-553), op by op: AdaIN kernels, then each
+        block with the skip sum formed in its first conv's loader (_decode_skip). use_mask:
+        per-label AdaIN of (c_i, s_i) at every level (do_mask_stylized), the skip sum formed by
+        the masked apply kernel."""
         self._kernel_path_check()
+        pairs = list(zip(content_feats[:-1], style_feats[:-1]))[::-1]
         if use_mask:
             # all levels share H x W: decode the masks and plan the labels once
             n, dev = content_feats[-1].shape[0], content_feats[-1].device
@@ -281,29 +304,30 @@ class MultiScaleAdaINRPNet(AdaINRPNet):
             s_seg = segment_maps(s_mask_path, n, style_feats[-1].shape[2:], dev)
             stylized, seg_plan = masked_adain_batch(content_feats[-1], style_feats[-1], c_seg,
                                                     s_seg)
-            stylized = self.rp_decoder[0](stylized)
-            for i, (content_feat, style_feat) in enumerate(
-                    list(zip(content_feats[:-1], style_feats[:-1]))[::-1]):
+            stylized = self._dec(0)(stylized)
+            for i, (content_feat, style_feat) in enumerate(pairs):
                 fused, _ = masked_adain_batch(content_feat, style_feat, c_seg, s_seg,
                                               skip=stylized, plan=seg_plan)
-                stylized = self.rp_decoder[i + 1](fused)
+                stylized = self._dec(i + 1)(fused)
             return stylized
-        stylized = AdaIN(content_feats[-1], style_feats[-1])
-        stylized = self.rp_decoder[0](stylized)
-        for i, (content_feat, style_feat) in enumerate(
-                list(zip(content_feats[:-1], style_feats[:-1]))[::-1]):
-            cm, cs = calc_mean_std(content_feat)
-            sm, ss = calc_mean_std(style_feat)
-            stylized = plan.run(_block_plan(self.rp_decoder[i + 1]), stylized,
-                                first_aux=ops.adain_params(cm, cs, sm, ss),
-                                first_in_op=ops.IN_ADD_ADAIN, first_content=content_feat)
+        stylized = self._dec(0)(AdaIN(content_feats[-1], style_feats[-1]))
+        for i, (content_feat, style_feat) in enumerate(pairs):
+            stylized = self._decode_skip(i + 1, stylized, content_feat, style_feat)
         return stylized
+
+    def _decode_skip(self, k, stylized, content_feat, style_feat):
+        """Decoder block k on stylized + AdaIN(content_feat, style_feat)."""
+        cm, cs = calc_mean_std(content_feat)
+        sm, ss = calc_mean_std(style_feat)
+        return plan.run(_block_plan(self._dec(k)), stylized,
+                        first_aux=ops.adain_params(cm, cs, sm, ss),
+                        first_in_op=ops.IN_ADD_ADAIN, first_content=content_feat)
 
     def forward(self, content, style, alpha=1.0):
         """Loss dict of adain_rp.py:322-345. With autograd enabled and trainable RP
-        parameters the losses come from rpst.autograd._MultiScaleStep (forward and backward
-        kernels; total_loss.backward() fills the RP encoder / decoder gradients); under
-        no_grad it is evaluated op by op."""
+        parameters the losses come from rpst.autograd._MultiScaleStep through the family's
+        entry point (forward and backward kernels; total_loss.backward() fills the RP encoder /
+        decoder gradients); under no_grad it is evaluated op by op."""
         assert 0 <= alpha <= 1
         if self._has_attention():
             raise NotImplementedError(
@@ -311,8 +335,8 @@ class MultiScaleAdaINRPNet(AdaINRPNet):
                 "training-mode BatchNorm and the SE block's backward have no rpst kernel")
         if torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters()):
             self._kernel_path_check()
-            from rpst.autograd import multiscale_losses
-            return multiscale_losses(self, content, style)
+            from rpst import autograd
+            return getattr(autograd, self._losses_entry)(self, content, style)
         content_feats = self.encode_rp_intermediate(content)
         style_feats = self.encode_rp_intermediate(style)
         stylized = self.decode(content_feats, style_feats)
@@ -347,9 +371,13 @@ class LDMSAdaINRPNet(MultiScaleAdaINRPNet):
     raises ValueError at construction (the reference adds a Python list to a tensor in decode),
     and `resume: True` builds the modules and then loads the checkpoint that save() writes
     (torch.save(self.state_dict())) strictly, begin taken from the file name (the reference
-    loads into the parent's encoder, which is None for this family). forward() with autograd
-    enabled raises; training goes through rpst.autograd.ld_losses (train.py routes
-    `network: ld_adain` there)."""
+    loads into the parent's encoder, which is None for this family).
+
+    test(), decode() (its masked loop included) and forward() are the parent's: this class
+    defines the family's hooks only (two blocks per level, rp_dec{k}, _encode_level,
+    _decode_fused, _decode_skip). forward() with autograd enabled returns
+    rpst.autograd.ld_losses(self, content, style), so train.py trains it like every other
+    family."""
 
     def __init__(self, config, vgg_encoder) -> None:
         super().__init__(dict(config, resume=False), vgg_encoder)
@@ -394,26 +422,33 @@ class LDMSAdaINRPNet(MultiScaleAdaINRPNet):
         setattr(self, f'rp_dec{self.layer_num - 1}',
                 Conv2dBlock(hidden_dim * 2, 3, 3, 1, 1, inception_num=self.inception_num))
 
-    def _has_attention(self):
-        return False
+    _losses_entry = 'ld_losses'
 
     def _enc(self, i, name):
         return getattr(self, f'rp_enc{i}_{name}_revf')
 
+    def _level_blocks(self, i):
+        return [self._enc(i, 'small'), self._enc(i, 'big')]
+
+    def _dec(self, k):
+        return getattr(self, f'rp_dec{k}')
+
     def encode_rp_intermediate(self, input):
         results = [input]
         for i in range(self.layer_num):
-            results.append(self._encode_level(i, results[-1], None))
+            results.append(self._encode_level(i, results[-1]))
         return results[1:]
 
-    def _encode_level(self, i, x, x2):
+    def _encode_level(self, i, x, x2=None, n=None, stats=False):
         """Level i over x (or the batch [x; x2]): cat([small(x), big(x)], dim=1) without the
         cat. A 7x7 big branch whose block is the conv and its activation alone writes the upper
         half of the level tensor from its kernel; otherwise (level 0, inception 1x1s) the
-        branch's output is copied in like the small one's."""
+        branch's output is copied in like the small one's. No level has epilogue statistics
+        (a level is two kernels' output): _decode_fused takes them from the level."""
+        assert not stats
         small = plan.run(_block_plan(self._enc(i, 'small')), x, x2=x2)
-        n, c, h, w = small.shape
-        level = torch.empty((n, 2 * c, h, w), device=small.device, dtype=torch.float32)
+        b, c, h, w = small.shape
+        level = torch.empty((b, 2 * c, h, w), device=small.device, dtype=torch.float32)
         level[:, :c].copy_(small)
         steps = _block_plan(self._enc(i, 'big'))
         if len(steps) == 1 and plan.is_k7(steps[0]):
@@ -427,7 +462,7 @@ class LDMSAdaINRPNet(MultiScaleAdaINRPNet):
         first conv loader; stats = calc_mean_std(stylized), style_stats that of the style
         level. want_stats: also calc_mean_std of the result (from the last conv's epilogue
         unless that conv is the skip-AdaIN one, which has none) -> (y, mean, std)."""
-        steps = _block_plan(getattr(self, f'rp_dec{i}'))
+        steps = _block_plan(self._dec(i))
         aux = ops.adain_params(stats[0], stats[1], style_stats[0], style_stats[1])
         epilogue = want_stats and len(steps) > 1
         y = plan.run(steps, stylized, first_aux=aux, first_in_op=ops.IN_ADD_ADAIN,
@@ -436,73 +471,22 @@ class LDMSAdaINRPNet(MultiScaleAdaINRPNet):
             return (y,) + tuple(ops.calc_mean_std(y))
         return y
 
-    def test(self, content, style, iterations=0, bid=0, c_mask_path=None, s_mask_path=None):
-        self.eval()
-        with torch.no_grad():
-            self._kernel_path_check()
-            use_mask = self.config['use_mask']
-            if not FUSED_ADAIN:
-                y = self.decode(self.encode_rp_intermediate(content),
-                                self.encode_rp_intermediate(style), use_mask=use_mask,
-                                c_mask_path=c_mask_path, s_mask_path=s_mask_path)
-                self.train()
-                return y
-            n = content.shape[0]
-            x, x2 = content, style  # level 0 reads both in place (no concat)
-            feats = []
-            for i in range(self.layer_num):
-                x = self._encode_level(i, x, x2)
-                x2 = None
-                feats.append(x)
-            if use_mask:
-                y = self.decode([f[:n] for f in feats], [f[n:] for f in feats], True,
-                                c_mask_path, s_mask_path)
-                self.train()
-                return y
-            mean, std = ops.calc_mean_std(feats[-1])
-            last = self.layer_num == 1
-            y = plan.run(_block_plan(self.rp_dec0), feats[-1][:n],
-                         first_aux=ops.adain_params(mean[:n], std[:n], mean[n:], std[n:]),
-                         first_in_op=ops.IN_ADAIN, stats_last=not last)
-            for i, f in enumerate(feats[:-1][::-1]):
-                y, ym, ys = y
-                y = self._skip_block(i + 1, y, (ym, ys), ops.calc_mean_std(f[n:]),
-                                     want_stats=i < self.layer_num - 2)
-            self.train()
-            return y
+    def _decode_fused(self, content, style, n):
+        feats = self._encode_pair(content, style)
+        mean, std = ops.calc_mean_std(feats[-1])
+        last = self.layer_num == 1
+        y = plan.run(_block_plan(self.rp_dec0), feats[-1][:n],
+                     first_aux=ops.adain_params(mean[:n], std[:n], mean[n:], std[n:]),
+                     first_in_op=ops.IN_ADAIN, stats_last=not last)
+        for i, f in enumerate(feats[:-1][::-1]):
+            y, ym, ys = y
+            y = self._skip_block(i + 1, y, (ym, ys), ops.calc_mean_std(f[n:]),
+                                 want_stats=i < self.layer_num - 2)
+        return y
 
-    def decode(self, content_feats, style_feats, use_mask=False, c_mask_path=None, s_mask_path=None):
-        """adain_rp.py:538-553, op by op."""
-        self._kernel_path_check()
-        pairs = list(zip(content_feats[:-1], style_feats[:-1]))[::-1]
-        if use_mask:
-            n, dev = content_feats[-1].shape[0], content_feats[-1].device
-            c_seg = segment_maps(c_mask_path, n, content_feats[-1].shape[2:], dev)
-            s_seg = segment_maps(s_mask_path, n, style_feats[-1].shape[2:], dev)
-            stylized, seg_plan = masked_adain_batch(content_feats[-1], style_feats[-1], c_seg,
-                                                    s_seg)
-            stylized = self.rp_dec0(stylized)
-            for i, (content_feat, style_feat) in enumerate(pairs):
-                fused, _ = masked_adain_batch(content_feat, style_feat, c_seg, s_seg,
-                                              skip=stylized, plan=seg_plan)
-                stylized = getattr(self, f'rp_dec{i + 1}')(fused)
-            return stylized
-        stylized = self.rp_dec0(AdaIN(content_feats[-1], style_feats[-1]))
-        for i, (content_feat, style_feat) in enumerate(pairs):
-            # rp_dec{i+1}(stylized + AdaIN(stylized, style_feat))
-            stylized = self._skip_block(i + 1, stylized, calc_mean_std(stylized),
-                                        calc_mean_std(style_feat))
-        return stylized
+    def _decode_skip(self, k, stylized, content_feat, style_feat):
+        """rp_dec{k}(stylized + AdaIN(stylized, style_feat)) (adain_rp.py:550)."""
+        return self._skip_block(k, stylized, calc_mean_std(stylized), calc_mean_std(style_feat))
 
     def save(self, save_path, iterations=0):
         torch.save(self.state_dict(), save_path)
-
-    def forward(self, content, style, alpha=1.0):
-        """The parent's loss dict (adain_rp.py:322-345) under no_grad; with autograd enabled
-        and trainable parameters it raises. The differentiable loss dict is
-        rpst.autograd.ld_losses(model, content, style), which train.py calls for this network."""
-        if torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters()):
-            raise NotImplementedError(
-                "LDMSAdaINRPNet (ld_adain) is inference only: the 7x7 conv has no backward "
-                "kernels; call forward() under torch.no_grad()")
-        return super().forward(content, style, alpha)

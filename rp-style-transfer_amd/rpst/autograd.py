@@ -29,13 +29,13 @@ train loop (backward + Adam) trains on the HIP path. The steps are built from sh
 Steps: _AdaINRPStep (RP encoder over [content; style], AdaIN, RP decoder), _WCTRPStep (the
 RP decoder on a constant WCT feature), _SAModelStep (transform + decoder over three
 branches), _SourceNetStep (decoder on AdaIN of frozen VGG features), _MultiScaleStep (block
-encoder / decoder with an AdaIN per level), _LDStep (LDMSAdaINRPNet: two-branch levels with
-the 7x7 conv's backward kernels, csrc/rpst_conv7_train.hip); the *_losses functions are their
-entry points.
+encoder / decoder with an AdaIN per level: MultiScaleAdaINRPNet, and LDMSAdaINRPNet with its
+two-branch levels and the 7x7 conv's backward kernels, csrc/rpst_conv7_train.hip); the
+*_losses functions are their entry points.
 """
 from __future__ import annotations
 
-from typing import Dict, List, Optional, Tuple
+from typing import Dict, List, NamedTuple, Optional, Tuple
 
 import torch
 import torch.nn as nn
@@ -421,19 +421,20 @@ def _adain_backward(g: torch.Tensor, state) -> torch.Tensor:
 
 # ---- the steps ---------------------------------------------------------------------------
 # Every step is Step.apply(content, style, model, cfg, *params): cfg the loss weights
-# (_losses), params the trained parameters, whose gradients its backward returns in order.
+# (_losses), params the trained parameters, whose gradients its backward returns in order
+# (_MultiScaleStep takes its _Family between cfg and params).
 # Forward and backward both enter precise_convs(family): the autograd engine runs the
 # backward on its own thread.
 
 def _losses(step, model, content: torch.Tensor, style: torch.Tensor,
-            params: List[torch.Tensor], extra: Tuple[str, ...] = ()
+            params: List[torch.Tensor], extra: Tuple[str, ...] = (), family=None
             ) -> Tuple[Dict[str, torch.Tensor], torch.Tensor]:
     """Run a step on detached inputs with the float weights of model.config: the loss dict
     ({'style_loss', 'content_loss', f'{extra}_loss'.., 'total_loss'}) and total_loss."""
     ops._check(content, style)
     cfg = tuple(float(model.config[f'{k}_weight']) for k in ('content', 'style') + extra)
     total, ls, lc, *rest = step.apply(content.detach().contiguous(), style.detach().contiguous(),
-                                      model, cfg, *params)
+                                      model, cfg, *(() if family is None else (family,)), *params)
     losses = {'style_loss': ls, 'content_loss': lc}
     losses.update(zip((f'{k}_loss' for k in extra), rest))
     losses['total_loss'] = total
@@ -780,132 +781,93 @@ class _SourceNetStep(torch.autograd.Function):
         return (None, None, None, None, *[grads.get(id(p)) for p in ctx.params])
 
 
-class _MultiScaleStep(torch.autograd.Function):
-    """MultiScaleAdaINRPNet.forward (adain_rp.py:321-345) for the constant / deeper stacks.
+class _Family(NamedTuple):
+    """What _MultiScaleStep needs to know of a multi-scale AdaIN family."""
+    levels: list          # per encoder level its Conv2dBlocks: one, or branches concatenated
+    decoder: list         # decoder blocks, the first on the top level
+    content_is_y: bool    # block k >= 1 adds AdaIN(y, s_level) (LD), not AdaIN(c_level, s_level)
+    f4: str               # the ops.precise_convs (TRAIN_F4) family
+    params: list          # the trained parameters
 
-    Forward: the shared encoder over [content; style] block by block (every block output is
-    a level, every conv's input / output kept); decoder block 0 on AdaIN(level L-1), block k
-    on y_{k-1} + AdaIN(level L-1-k) (adain_rp.py:291-302; the sums and AdaIN outputs are
-    materialised, they are the blocks' wgrad inputs); VGG losses on the stylized batch.
+
+class _MultiScaleStep(torch.autograd.Function):
+    """MultiScaleAdaINRPNet.forward (adain_rp.py:321-345) for the constant / deeper stacks and
+    LDMSAdaINRPNet's loss graph (adain_rp.py:484-567 under the same forward), told apart by
+    fam (_Family).
+
+    Forward: the encoder over [content; style] level by level, every conv's input / output
+    kept; a level is its block's output, or its branches' outputs (LD: 3x3 small, 7x7 big;
+    level 0 two 3x3) concatenated. Decoder block 0 on AdaIN(level L-1), block k on
+    y_{k-1} + AdaIN(c, s_{L-1-k}) with c the level's content half (adain_rp.py:291-302) or,
+    for LD, y_{k-1} itself (adain_rp.py:550); the sums and AdaIN outputs are materialised,
+    they are the blocks' wgrad inputs. VGG losses on the stylized batch.
     Backward: VGG dgrad -> decoder blocks (LeakyReLU, 1x1 / reflect 3x3 wgrad + dgrad); the
-    gradient at each block input passes unchanged to the previous block's output and through
-    AdaIN backward to the level's content and style features; the encoder walks back with
-    each level's [d content; d style] added at its block output."""
+    gradient g at each block input goes through AdaIN backward to [d content; d style] of the
+    level and on to the previous block's output: unchanged, or for LD as g + d content, the
+    level keeping d style alone (its content halves below the top level reach the loss only
+    through the level above). The encoder walks back with each level's gradient added at its
+    output; a two-branch level splits it at the channel midpoint, each branch goes through
+    _stack_backward, and the two input gradients are summed."""
 
     @staticmethod
-    def forward(ctx, content, style, model, cfg, *params):
-        with ops.precise_convs("multiscale"):
+    def forward(ctx, content, style, model, cfg, fam, *params):
+        with ops.precise_convs(fam.f4):
             n = content.shape[0]
             x, enc, levels = torch.cat([content, style], dim=0), [], []
-            for blk in model.rp_shared_encoder:
-                st = plan.compile_layers(plan.block_layers(blk))
-                x, sv = _run_steps_saving(st, x)
-                enc.append((st, sv))
+            for blocks in fam.levels:
+                branches, outs = [], []
+                for blk in blocks:
+                    st = plan.compile_layers(plan.block_layers(blk))
+                    y, sv = _run_steps_saving(st, x)
+                    branches.append((st, sv))
+                    outs.append(y)
+                enc.append(branches)
+                x = outs[0] if len(outs) == 1 else torch.cat(outs, dim=1)
                 levels.append(x)
             L = len(levels)
             dec, states = [], []
             y = None
-            for k, blk in enumerate(model.rp_decoder):
+            for k, blk in enumerate(fam.decoder):
                 lv = levels[L - 1 - k]
-                state = _adain_state(lv[:n], lv[n:])
-                z = ops.adaptive_instance_normalization(lv[:n], lv[n:])
-                if y is not None:
+                cf = y if k and fam.content_is_y else lv[:n]
+                states.append(_adain_state(cf, lv[n:]))
+                z = ops.adaptive_instance_normalization(cf, lv[n:])
+                if k:
                     z.add_(y)
                 st = plan.compile_layers(plan.block_layers(blk))
                 y, sv = _run_steps_saving(st, z)
                 dec.append((st, sv))
-                states.append(state)
                 if k == L - 1:
                     break
             loss = _VGGLoss(model, y, content, style, *cfg)
-        ctx.loss, ctx.enc, ctx.dec, ctx.states, ctx.params = loss, enc, dec, states, params
+        ctx.loss, ctx.enc, ctx.dec, ctx.states, ctx.fam = loss, enc, dec, states, fam
         return loss.total, loss.ls, loss.lc
 
     @staticmethod
     def backward(ctx, g_total, g_ls, g_lc):
-        with ops.precise_convs("multiscale"):
+        fam = ctx.fam
+        with ops.precise_convs(fam.f4):
             g = ctx.loss.backward(g_total, g_ls, g_lc)
             grads: Dict[int, torch.Tensor] = {}
             L = len(ctx.enc)
+            n = g.shape[0]
             dlev = [None] * L
             for k in range(len(ctx.dec) - 1, -1, -1):
                 g = _stack_backward(*ctx.dec[k], g, grads, need_input_grad=True)
-                dlev[L - 1 - k] = _adain_backward(g, ctx.states[k])
+                d = _adain_backward(g, ctx.states[k])  # [d content; d style]
+                if k and fam.content_is_y:
+                    g = g + d[:n]   # the skip and AdaIN's own content, both the block below
+                    d[:n].zero_()
+                dlev[L - 1 - k] = d
             ge = None
             for i in range(L - 1, -1, -1):
                 if dlev[i] is not None:
                     ge = dlev[i] if ge is None else ge.add_(dlev[i])
                 if ge is None:
                     continue
-                ge = _stack_backward(*ctx.enc[i], ge, grads, need_input_grad=i > 0)
-        ctx.enc = ctx.dec = ctx.states = None
-        return (None, None, None, None, *[grads.get(id(p)) for p in ctx.params])
-
-
-class _LDStep(torch.autograd.Function):
-    """LDMSAdaINRPNet's loss graph (adain_rp.py:484-567 under the parent's forward,
-    adain_rp.py:321-345).
-
-    Forward: per level both branches (3x3 small, 7x7 big; level 0 two 3x3) run over the
-    [content; style] batch with every conv's input / output kept, and their outputs are
-    concatenated into the level; rp_dec0 on AdaIN(c_{L-1}, s_{L-1}), then rp_dec{j} on
-    y + AdaIN(y, s_{L-1-j}), the content statistics being y's own (adain_rp.py:550); VGG
-    losses on the stylized batch.
-    Backward: VGG dgrad -> decoder blocks; at a skip block with input gradient g,
-    (dc, ds) = AdaIN backward of g at (y, s_i): g + dc goes on to the previous block and ds to
-    the style half of level i (the content halves below the top level reach the loss only
-    through the level above). The encoder walks back level by level: the level's gradient is
-    split at the channel midpoint into the small and the big branch, each goes through
-    _stack_backward, and the two input gradients are summed with the level below's."""
-
-    @staticmethod
-    def forward(ctx, content, style, model, cfg, *params):
-        with ops.precise_convs("ld"):
-            n = content.shape[0]
-            x, enc, levels = torch.cat([content, style], dim=0), [], []
-            for i in range(model.layer_num):
-                branches = []
-                for name in ("small", "big"):
-                    st = plan.compile_layers(plan.block_layers(model._enc(i, name)))
-                    branches.append((st,) + _run_steps_saving(st, x))
-                enc.append([(st, sv) for st, _, sv in branches])
-                x = torch.cat([y for _, y, _ in branches], dim=1)
-                levels.append(x)
-            L = len(levels)
-            dec, states = [], []
-            y = None
-            for k in range(L):
-                sf = levels[L - 1 - k][n:]
-                cf = levels[L - 1][:n] if k == 0 else y
-                states.append(_adain_state(cf, sf))
-                z = ops.adaptive_instance_normalization(cf, sf)
-                if k:
-                    z.add_(y)
-                st = plan.compile_layers(plan.block_layers(getattr(model, f"rp_dec{k}")))
-                y, sv = _run_steps_saving(st, z)
-                dec.append((st, sv))
-            loss = _VGGLoss(model, y, content, style, *cfg)
-        ctx.loss, ctx.enc, ctx.dec, ctx.states, ctx.params = loss, enc, dec, states, params
-        return loss.total, loss.ls, loss.lc
-
-    @staticmethod
-    def backward(ctx, g_total, g_ls, g_lc):
-        with ops.precise_convs("ld"):
-            g = ctx.loss.backward(g_total, g_ls, g_lc)
-            grads: Dict[int, torch.Tensor] = {}
-            L = len(ctx.enc)
-            n = g.shape[0]
-            dlev = [None] * L
-            for k in range(L - 1, -1, -1):
-                g = _stack_backward(*ctx.dec[k], g, grads, need_input_grad=True)
-                d = _adain_backward(g, ctx.states[k])  # [d content; d style]
-                if k:
-                    g = g + d[:n]   # the skip and AdaIN's own content, both the block below
-                    d[:n].zero_()
-                dlev[L - 1 - k] = d
-            ge = None
-            for i in range(L - 1, -1, -1):
-                ge = dlev[i] if ge is None else ge.add_(dlev[i])
+                if len(ctx.enc[i]) == 1:
+                    ge = _stack_backward(*ctx.enc[i][0], ge, grads, need_input_grad=i > 0)
+                    continue
                 c = ge.shape[1] // 2
                 dx = None
                 for (st, sv), gb in zip(ctx.enc[i], (ge[:, :c], ge[:, c:])):
@@ -913,17 +875,19 @@ class _LDStep(torch.autograd.Function):
                     dx = d if dx is None else dx.add_(d)
                 ge = dx
         ctx.enc = ctx.dec = ctx.states = None
-        return (None, None, None, None, *[grads.get(id(p)) for p in ctx.params])
+        return (None, None, None, None, None, *[grads.get(id(p)) for p in fam.params])
 
 
 def ld_losses(model, content: torch.Tensor, style: torch.Tensor):
-    """LDMSAdaINRPNet's training entry: the loss dict of the reference's forward
-    ({'style_loss', 'content_loss', 'total_loss'}) and total_loss, differentiable w.r.t. every
-    rp_enc* / rp_dec* parameter (the VGG is frozen). The model's forward() with autograd
-    enabled keeps raising; train.py calls this instead."""
+    """LDMSAdaINRPNet's training entry (its forward() with autograd enabled): the loss dict of
+    the reference's forward ({'style_loss', 'content_loss', 'total_loss'}) and total_loss,
+    differentiable w.r.t. every rp_enc* / rp_dec* parameter (the VGG is frozen)."""
     model._kernel_path_check()
     params = [p for name, p in model.named_parameters() if name.startswith(("rp_enc", "rp_dec"))]
-    return _losses(_LDStep, model, content, style, params)
+    L = model.layer_num
+    fam = _Family([model._level_blocks(i) for i in range(L)], [model._dec(k) for k in range(L)],
+                  True, "ld", params)
+    return _losses(_MultiScaleStep, model, content, style, params, family=fam)
 
 
 def sourcenet_losses(model, content: torch.Tensor, style: torch.Tensor):
@@ -935,5 +899,7 @@ def sourcenet_losses(model, content: torch.Tensor, style: torch.Tensor):
 def multiscale_losses(model, content: torch.Tensor, style: torch.Tensor):
     """MultiScaleAdaINRPNet.forward with autograd: the loss dict and total_loss,
     differentiable w.r.t. the RP encoder / decoder parameters."""
-    return _losses(_MultiScaleStep, model, content, style,
-                   list(model.rp_shared_encoder.parameters()) + list(model.rp_decoder.parameters()))
+    params = list(model.rp_shared_encoder.parameters()) + list(model.rp_decoder.parameters())
+    fam = _Family([[blk] for blk in model.rp_shared_encoder], list(model.rp_decoder), False,
+                  "multiscale", params)
+    return _losses(_MultiScaleStep, model, content, style, params, family=fam)

@@ -22,8 +22,7 @@ Networks with backward kernels: 'adain' (AdaINRPNet: RP encoder + decoder), 'wct
 (WCTRPNet: RP decoder; its fuse() detaches the encoder features, wct_rp.py:161-162) and
 'sanet' (SAModel: transform + decoder, sanet.py:248-275; checkpoints {'decoder',
 'transform'}), 'dynamic_sanet', 'multi_adain', 'src' and 'ld_adain' (LDMSAdaINRPNet: every
-rp_enc* / rp_dec* block through rpst.autograd.ld_losses, its forward() being left to raise
-with autograd enabled; checkpoints the whole state_dict); the others raise.
+rp_enc* / rp_dec* block; checkpoints the whole state_dict); the others raise.
 """
 from __future__ import annotations
 
@@ -171,14 +170,6 @@ def main(argv=None) -> int:
             d.mkdir(exist_ok=True, parents=True)
     network = stylize.build_network(opt, args.synthetic_weights).to(device)
     network.train()
-    step_losses = network
-    if opt["network"] == "ld_adain":
-        # LDMSAdaINRPNet.forward() with autograd enabled raises (its tests pin that); the
-        # training step is rpst.autograd.ld_losses
-        from rpst.autograd import ld_losses
-
-        def step_losses(content, style):
-            return ld_losses(network, content, style)
     params = [p for p in network.parameters() if p.requires_grad]
     optimizer = torch.optim.Adam(params, lr=opt["lr"])
     reduce_grads = GradientAllReduce(params) if world > 1 else None
@@ -197,7 +188,7 @@ def main(argv=None) -> int:
         optimizer.zero_grad()
         adjust_learning_rate(opt, optimizer, iteration_count=i)
         content_images, style_images = next(loader)
-        loss_dict, total_loss = step_losses(content_images, style_images)
+        loss_dict, total_loss = network(content_images, style_images)
         total_loss.backward()
         st = getattr(network, "_wct_status", None)
         if st is not None:

@@ -323,8 +323,16 @@ def test_ld_forward_losses(cuda, golden):
     assert all(bool(torch.isfinite(v).all()) for v in losses.values())
     assert torch.equal(total, losses["total_loss"])
     assert torch.is_grad_enabled()
-    with pytest.raises(NotImplementedError, match="ld_adain"):
-        m(c, s)
+    # with autograd enabled forward() is rpst.autograd.ld_losses, bit for bit
+    from rpst import autograd as A
+    train_losses, train_total = m(c, s)
+    assert set(train_losses) == {"style_loss", "content_loss", "total_loss"}
+    assert all(bool(torch.isfinite(v).all()) for v in train_losses.values())
+    assert train_total.requires_grad and train_losses["total_loss"].requires_grad
+    ref_losses, ref_total = A.ld_losses(m, c, s)
+    assert torch.equal(train_total, ref_total)
+    for k, v in ref_losses.items():
+        assert torch.equal(train_losses[k], v), k
 
 
 # ---- pipeline -----------------------------------------------------------------------------

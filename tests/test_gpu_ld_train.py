@@ -335,10 +335,22 @@ def test_ld_train_driver_end_to_end(cuda, tmp_path):
 
 # ---- unchanged surface --------------------------------------------------------------------
 def test_forward_still_raises_and_no_cpu_fallback(cuda):
+    """(Name kept.) forward() with autograd enabled trains: m(c, s)[1].backward() leaves on every
+    rp_enc* / rp_dec* parameter the gradient of ld_losses(...)[1].backward() on a copy of the
+    model, bit for bit; ld_losses still refuses CPU tensors."""
     from rpst import autograd as A
-    m, _ = _net(LT.config(4, 3), 99, cuda)
-    c = torch.zeros((1, 3, 16, 16), device=cuda)
-    with pytest.raises(NotImplementedError, match="ld_adain"):
-        m(c, c)
+    from rpst import synth
+    m, _ = _net(LT.config(4, 3, 0), 99, cuda)
+    m2 = copy.deepcopy(m)
+    c = torch.from_numpy(synth.image(9305, (1, 3, 16, 24))).to(cuda)
+    s = torch.from_numpy(synth.image(9306, (1, 3, 16, 24))).to(cuda)
+    m(c, s)[1].backward()
+    A.ld_losses(m2, c, s)[1].backward()
+    named, named2 = dict(m.named_parameters()), dict(m2.named_parameters())
+    names = [k for k in named if k.startswith(("rp_enc", "rp_dec"))]
+    assert sorted(names) == _rp_names(m) and len(names) == 2 * (2 * 3 + 3)
+    for k in names:
+        assert named[k].grad is not None and bool(torch.isfinite(named[k].grad).all()), k
+        assert torch.equal(named[k].grad, named2[k].grad), k
     with pytest.raises(RuntimeError, match="ROCm GPU"):
         A.ld_losses(m, c.cpu(), c.cpu())

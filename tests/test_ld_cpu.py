@@ -87,10 +87,18 @@ def test_stylized_layers_below_layer_num_raises():
 
 def test_forward_with_grad_raises_before_any_kernel():
     import network as net
+    """forward() with autograd enabled is the parent's dispatch to rpst.autograd.ld_losses:
+    CPU tensors are refused before any kernel (no CPU fallback), sort / shuffle before that."""
     m = net.LDMSAdaINRPNet(L.config(4, 3), copy.deepcopy(net.vgg))
     x = torch.zeros(1, 3, 8, 8)
-    with pytest.raises(NotImplementedError, match="ld_adain"):
+    assert torch.is_grad_enabled() and any(p.requires_grad for p in m.parameters())
+    with pytest.raises(RuntimeError, match="ROCm GPU"):
         m(x, x)
+    for key in ("sort", "shuffle"):
+        cfg = L.config(4, 3)
+        cfg[key] = True
+        with pytest.raises(NotImplementedError, match="shuffle / sort"):
+            net.LDMSAdaINRPNet(cfg, copy.deepcopy(net.vgg))(x, x)
 
 
 def test_stylize_builds_ld_adain_and_refuses_the_later_ones():
