@@ -39,11 +39,10 @@ def adain_rp_fused(encoder, decoder, content, style):
     (store_n = n; adain_rp.py:94-101 reads style_feat only via calc_mean_std)."""
     n = content.shape[0]
     assert content.size() == style.size()
-    feats, mean, std = plan.run(plan.compile_layers(encoder.children()), content,
-                                x2=style, stats_last=True, store_n=None if STORE_ALL else n)
+    feats, mean, std = plan.run(plan.of(encoder), content, x2=style, stats_last=True,
+                                store_n=None if STORE_ALL else n)
     aux = ops.adain_params(mean[:n], std[:n], mean[n:], std[n:])
-    return plan.run(plan.compile_layers(decoder.children()), feats[:n],
-                    first_aux=aux, first_in_op=ops.IN_ADAIN)
+    return plan.run(plan.of(decoder), feats[:n], first_aux=aux, first_in_op=ops.IN_ADAIN)
 
 
 def encode_both(encoder, content, style):
@@ -136,16 +135,12 @@ class AdaINRPNet(BaseNet):
         return {'style_loss': loss_s, 'content_loss': loss_c, 'total_loss': total_loss}, total_loss
 
 
-def _block_plan(blk):
-    return plan.compile_layers(plan.block_layers(blk))
-
-
 def _encode_se_block(blk, x, x2, n, stats):
     """One encoder block with SE attention over the [content; style] batch of 2n: the conv
     plan without statistics, then the SE block, whose gated conv emits calc_mean_std of the
     block's output when `stats`. blk.attention_map becomes the style half's gates, as after
     the reference's content-then-style encoding (adain_rp.py:286-290)."""
-    x = plan.run(_block_plan(blk), x, x2=x2)
+    x = plan.run(plan.of(blk), x, x2=x2)
     res = ops.se_bottleneck(x, blk.attention_block, stats=stats)
     gate = res[1][n:]
     blk.attention_block.attention_map = blk.attention_block.se.attention_map = gate
@@ -244,7 +239,7 @@ class MultiScaleAdaINRPNet(AdaINRPNet):
         blk = self.rp_shared_encoder[i]
         if blk.attention_block is not None:
             return _encode_se_block(blk, x, x2, n, stats)
-        return plan.run(_block_plan(blk), x, stats_last=stats, x2=x2)
+        return plan.run(plan.of(blk), x, stats_last=stats, x2=x2)
 
     def _encode_pair(self, content, style, stats=False):
         """Every level over [content; style], the encoder run once."""
@@ -283,10 +278,10 @@ class MultiScaleAdaINRPNet(AdaINRPNet):
             _, m, s = lv
             return ops.adain_params(m[:n], s[:n], m[n:], s[n:])
 
-        y = plan.run(_block_plan(self._dec(0)), levels[-1][0][:n],
+        y = plan.run(plan.of(self._dec(0)), levels[-1][0][:n],
                      first_aux=params(levels[-1]), first_in_op=ops.IN_ADAIN)
         for i, lv in enumerate(levels[:-1][::-1]):
-            y = plan.run(_block_plan(self._dec(i + 1)), y, first_aux=params(lv),
+            y = plan.run(plan.of(self._dec(i + 1)), y, first_aux=params(lv),
                          first_in_op=ops.IN_ADD_ADAIN, first_content=lv[0][:n])
         return y
 
@@ -319,7 +314,7 @@ class MultiScaleAdaINRPNet(AdaINRPNet):
         """Decoder block k on stylized + AdaIN(content_feat, style_feat)."""
         cm, cs = calc_mean_std(content_feat)
         sm, ss = calc_mean_std(style_feat)
-        return plan.run(_block_plan(self._dec(k)), stylized,
+        return plan.run(plan.of(self._dec(k)), stylized,
                         first_aux=ops.adain_params(cm, cs, sm, ss),
                         first_in_op=ops.IN_ADD_ADAIN, first_content=content_feat)
 
@@ -446,13 +441,13 @@ class LDMSAdaINRPNet(MultiScaleAdaINRPNet):
         branch's output is copied in like the small one's. No level has epilogue statistics
         (a level is two kernels' output): _decode_fused takes them from the level."""
         assert not stats
-        small = plan.run(_block_plan(self._enc(i, 'small')), x, x2=x2)
+        small = plan.run(plan.of(self._enc(i, 'small')), x, x2=x2)
         b, c, h, w = small.shape
         level = torch.empty((b, 2 * c, h, w), device=small.device, dtype=torch.float32)
         level[:, :c].copy_(small)
-        steps = _block_plan(self._enc(i, 'big'))
+        steps = plan.of(self._enc(i, 'big'))
         if len(steps) == 1 and plan.is_k7(steps[0]):
-            plan.run_conv7_step(steps[0], x, out=level, out_channel_offset=c, x2=x2)
+            plan.conv(steps[0], x, out=level, out_channel_offset=c, x2=x2)
         else:
             level[:, c:].copy_(plan.run(steps, x, x2=x2))
         return level
@@ -462,7 +457,7 @@ class LDMSAdaINRPNet(MultiScaleAdaINRPNet):
         first conv loader; stats = calc_mean_std(stylized), style_stats that of the style
         level. want_stats: also calc_mean_std of the result (from the last conv's epilogue
         unless that conv is the skip-AdaIN one, which has none) -> (y, mean, std)."""
-        steps = _block_plan(self._dec(i))
+        steps = plan.of(self._dec(i))
         aux = ops.adain_params(stats[0], stats[1], style_stats[0], style_stats[1])
         epilogue = want_stats and len(steps) > 1
         y = plan.run(steps, stylized, first_aux=aux, first_in_op=ops.IN_ADD_ADAIN,
@@ -475,7 +470,7 @@ class LDMSAdaINRPNet(MultiScaleAdaINRPNet):
         feats = self._encode_pair(content, style)
         mean, std = ops.calc_mean_std(feats[-1])
         last = self.layer_num == 1
-        y = plan.run(_block_plan(self.rp_dec0), feats[-1][:n],
+        y = plan.run(plan.of(self.rp_dec0), feats[-1][:n],
                      first_aux=ops.adain_params(mean[:n], std[:n], mean[n:], std[n:]),
                      first_in_op=ops.IN_ADAIN, stats_last=not last)
         for i, f in enumerate(feats[:-1][::-1]):

@@ -161,7 +161,7 @@ class Conv2dBlock(nn.Module):
         self.attention_map = None
 
     def forward(self, x):
-        x = plan.run(plan.compile_layers(plan.block_layers(self)), x)
+        x = plan.run(plan.of(self), x)
         if self.attention_block is not None:
             x = self.attention_block(x)
             self.attention_map = self.attention_block.attention_map
@@ -249,7 +249,7 @@ def encode_both(encoder, content, style, stats=False):
     x, x2 = content, style  # the first conv reads both in place (rpst_conv2d_pair)
     mean = std = None
     for k, st in enumerate(stages):
-        steps = plan.compile_layers(st.children())
+        steps = plan.of(st)
         if stats and k == len(stages) - 1:
             x, mean, std = plan.run(steps, x, stats_last=True, x2=x2)
         else:
@@ -262,8 +262,7 @@ def decode_adain(decoder_seq, feats, mean, std, n):
     """decoder(AdaIN(content, style)) with AdaIN applied in the decoder's first conv
     loader; feats/mean/std over the [content; style] batch of 2n (base.py:588-594)."""
     aux = ops.adain_params(mean[:n], std[:n], mean[n:], std[n:])
-    return plan.run(plan.compile_layers(decoder_seq.children()), feats[:n],
-                    first_aux=aux, first_in_op=ops.IN_ADAIN)
+    return plan.run(plan.of(decoder_seq), feats[:n], first_aux=aux, first_in_op=ops.IN_ADAIN)
 
 
 def adaptive_instance_normalization_with_segment(content_feat, style_feat, content_seg_path,

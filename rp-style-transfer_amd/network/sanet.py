@@ -19,7 +19,7 @@ import torch
 import torch.nn as nn
 
 from rpst import ops, plan
-from rpst.plan import KernelSequential, packed_weight
+from rpst.plan import KernelSequential
 
 from .base import BaseNet, _make_decoder, calc_mean_std, mse
 
@@ -75,11 +75,6 @@ class AEALReluModule(AEAModule):
         return nn.Tanh()
 
 
-def _conv1x1(conv: nn.Conv2d, x, residual=None):
-    return ops.conv2d(x, packed_weight(conv), conv.bias, conv.out_channels, 1,
-                      residual=residual)
-
-
 class SANet(nn.Module):
     def __init__(self, in_planes):
         super().__init__()
@@ -90,11 +85,11 @@ class SANet(nn.Module):
         self.out_conv = nn.Conv2d(in_planes, in_planes, (1, 1))
 
     def forward(self, content, style):
-        F = _conv1x1(self.f, mean_variance_norm(content))
-        G = _conv1x1(self.g, mean_variance_norm(style))
-        H = _conv1x1(self.h, style)
+        F = plan.conv(self.f, mean_variance_norm(content))
+        G = plan.conv(self.g, mean_variance_norm(style))
+        H = plan.conv(self.h, style)
         O = ops.sanet_attention(F, G, H)
-        return _conv1x1(self.out_conv, O, residual=content)
+        return plan.conv(self.out_conv, O, residual=content)
 
 
 class Transform(nn.Module):
@@ -116,11 +111,9 @@ class Transform(nn.Module):
             # F(4x4) has no two-operand loader: a + upsample2(b) is materialised (one
             # elementwise pass) and the conv runs on F(4x4) (512->512 at 64^2, N = 32:
             # ~1.8 vs 2.7 ms on the fused F(2x2) loader)
-            return ops.conv2d(ops.add_upsample_nearest2x(a, b), packed_weight(c), c.bias,
-                              c.out_channels, 3, pad=ops.PAD_REFLECT)
+            return plan.conv(c, ops.add_upsample_nearest2x(a, b), pad=ops.PAD_REFLECT)
         # merge_conv(reflect_pad(a + upsample2(b))) as ONE conv launch
-        return ops.conv2d(a, packed_weight(c), c.bias, c.out_channels, 3, pad=ops.PAD_REFLECT,
-                          in_op=ops.IN_ADD_UPSAMPLE2, aux=b)
+        return plan.conv(c, a, pad=ops.PAD_REFLECT, in_op=ops.IN_ADD_UPSAMPLE2, aux=b)
 
 
 class AdaptiveSANet(nn.Module):
@@ -144,9 +137,9 @@ class AdaptiveSANet(nn.Module):
         self.keep_claims = False
 
     def forward(self, content, style):
-        F = _conv1x1(self.f, mean_variance_norm(content))
-        G = _conv1x1(self.g, mean_variance_norm(style))
-        H = _conv1x1(self.h, style)
+        F = plan.conv(self.f, mean_variance_norm(content))
+        G = plan.conv(self.g, mean_variance_norm(style))
+        H = plan.conv(self.h, style)
         al = self.attention_layer
         O, claim, before, after = ops.adaptive_attention(
             F, G, H, content, style, al.f_psi, al.mode, float(al.scale_value),
@@ -154,7 +147,7 @@ class AdaptiveSANet(nn.Module):
         if self.keep_claims:
             self.claim_before, self.claim_after = before, after
         self.claim_value = claim
-        return _conv1x1(self.out_conv, O, residual=content)
+        return plan.conv(self.out_conv, O, residual=content)
 
 
 class AdaptiveTransform(nn.Module):
@@ -180,7 +173,7 @@ def _encode_pair_intermediate(model, a, b):
     """model.encode_with_intermediate(torch.cat([a, b])) (sanet.py:219-224 over the
     [style; content] batch of test(), :240-242) with enc_1's first conv reading a and b in
     place (rpst_conv2d_pair) instead of a concatenated copy."""
-    results = [plan.run(plan.compile_layers(model.enc_1.children()), a, x2=b)]
+    results = [plan.run(plan.of(model.enc_1), a, x2=b)]
     for i in range(1, 5):
         results.append(getattr(model, 'enc_{:d}'.format(i + 1))(results[-1]))
     return results

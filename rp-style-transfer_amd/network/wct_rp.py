@@ -52,11 +52,10 @@ def wct_rp_fused(encoder, decoder, content, style, model=None):
     (rpst_conv2d_mix), so the fused feature T (cF - mu_c) + mu_s is never written."""
     n = content.shape[0]
     assert content.size() == style.size()
-    feats, mean, _ = plan.run(plan.compile_layers(encoder.children()), content, x2=style,
-                              stats_last=True)
+    feats, mean, _ = plan.run(plan.of(encoder), content, x2=style, stats_last=True)
     T, c, res, st = ops.wct_params(feats[:n], feats[n:], means=mean.reshape(2 * n, -1),
                                    status=True)
-    out = plan.run(plan.compile_layers(decoder.children()), feats[:n], first_mix=(T, c))
+    out = plan.run(plan.of(decoder), feats[:n], first_mix=(T, c))
     # st: per-image status on the device: an image whose iteration did not converge
     # (non-finite features), or whose persistent launch timed out, has NaN T and c, so its
     # output is NaN; checked after this call's launches are queued (_status)

@@ -13,7 +13,7 @@ train loop (backward + Adam) trains on the HIP path. The steps are built from sh
                LeakyReLU; a ReLU feeding a 3x3 conv directly is fused into that conv's dgrad
                as a mask), weight / bias gradient (3x3 with zero or reflect padding, 1x1 as
                a batched GEMM, the nearest x2 upsample of the conv's loader materialised for
-               it) added into grads, dgrad conv (flip-transposed weights, zero pad) + reflect
+               it) added into grads, dgrad conv (plan.conv(.., flip=True), zero pad) + reflect
                border fold, upsample backward.
   VGG losses   _vgg_saving runs the frozen VGG slices over a stylized batch keeping every
                conv input / output; _vgg_backward walks them from loss seeds at the taps
@@ -48,26 +48,6 @@ def _ws(nbytes: int, like: torch.Tensor) -> torch.Tensor:
     return torch.empty(max(nbytes, 16), device=like.device, dtype=torch.uint8)
 
 
-def flip_packed_weight(conv: nn.Conv2d) -> torch.Tensor:
-    """Packed flip-transposed weights (Cin, Cout, k, k) of conv for its dgrad (a 7x7 conv's
-    in rpst_conv7's layout), cached on the module like plan.packed_weight (refreshed after
-    optimizer steps)."""
-    w = conv.weight
-    key = (w.device, w.data_ptr(), w._version)
-    cached = getattr(conv, "_rpst_flip_packed", None)
-    if cached is not None and cached[0] == key:
-        return cached[1]
-    with torch.no_grad():
-        wd = w.detach().contiguous()
-        cout, cin, k, _ = wd.shape
-        wt = torch.empty((cin, cout, k, k), device=wd.device, dtype=torch.float32)
-        _lib.call("rpst_conv_weight_flip", wd.data_ptr(), wt.data_ptr(), cout, cin, k,
-                  _stream(wd))
-        packed = ops.pack_conv7_weight(wt) if k == 7 else ops.pack_conv_weight(wt)
-    conv._rpst_flip_packed = (key, packed)
-    return packed
-
-
 def relu_backward(g: torch.Tensor, y: torch.Tensor) -> torch.Tensor:
     out = torch.empty_like(g)
     _lib.call("rpst_relu_backward", g.data_ptr(), y.data_ptr(), out.data_ptr(), g.numel(),
@@ -98,9 +78,9 @@ def conv_dgrad(g: torch.Tensor, step: plan.ConvStep,
     if k == 7:
         return _conv7_dgrad(g, step)
     if mask is None:
-        dx = ops.conv2d(g, flip_packed_weight(c), None, c.in_channels, k, pad=ops.PAD_ZERO)
+        dx = plan.conv(c, g, flip=True)
     else:
-        dx = ops.conv2d_masked(g, flip_packed_weight(c), c.in_channels, k, mask)
+        dx = ops.conv2d_masked(g, plan.packed_weight(c, flip=True), c.in_channels, k, mask)
     if k == 3 and step.pad == ops.PAD_REFLECT:
         n, _, h, w = g.shape
         wd = c.weight.detach().contiguous()
@@ -118,13 +98,12 @@ def _conv7_dgrad(g: torch.Tensor, step: plan.ConvStep) -> torch.Tensor:
     which is the gradient of the padded input, and rpst_reflect_pad_backward sums every padded
     position into the pixel it mirrors (2.4 % more conv FLOPs at 512 x 512)."""
     c = step.conv
-    pk = flip_packed_weight(c)
     if step.pad != ops.PAD_REFLECT:
-        return ops.conv2d_k7(g, pk, None, c.in_channels, pad=ops.PAD_ZERO)
+        return plan.conv(c, g, flip=True)
     n, co, h, w = g.shape
     ge = torch.zeros((n, co, h + 6, w + 6), device=g.device, dtype=torch.float32)
     ge[:, :, 3:h + 3, 3:w + 3].copy_(g)
-    gp = ops.conv2d_k7(ge, pk, None, c.in_channels, pad=ops.PAD_ZERO)
+    gp = plan.conv(c, ge, flip=True)
     dx = torch.empty((n, c.in_channels, h, w), device=g.device, dtype=torch.float32)
     with ops._traced(f"reflect3 fold C{c.in_channels} {h}x{w} N{n}", 0.0,
                      4.0 * (gp.numel() + dx.numel())):
@@ -217,6 +196,10 @@ def _lin_grads(dY, X):
     return dw, db
 
 
+# kernel size -> (x, g, conv, pad) -> (dw, db): the weight-gradient kernel of a conv step
+_WGRAD = {1: lambda x, g, conv, pad: _lin_grads(g, x), 3: conv_wgrad, 7: conv_wgrad7}
+
+
 def _acc(grads: Dict[int, torch.Tensor], p: torch.Tensor, g: torch.Tensor) -> None:
     if g is None:
         return
@@ -243,7 +226,7 @@ def _run_steps_saving(steps, x):
     saved = []
     for s in steps:
         assert isinstance(s, plan.ConvStep)
-        y = plan.run_conv_step(s, x)
+        y = plan.conv(s, x)
         saved.append((x, y))
         x = y
     return x, saved
@@ -268,15 +251,9 @@ def _stack_backward(steps, saved, g, grads: Dict[int, torch.Tensor], need_input_
         if not up and s.in_op != ops.IN_NONE:
             raise NotImplementedError("rpst autograd: conv stack input operator")
         x = ops.upsample_nearest2x(x_in) if up else x_in
-        if s.conv.kernel_size[0] == 3:
-            dw, db = conv_wgrad(x, g, s.conv, s.pad)
-        elif s.conv.kernel_size[0] == 7:
-            dw, db = conv_wgrad7(x, g, s.conv, s.pad)
-        else:
-            dw, db = _lin_grads(g, x)
-            db = db if s.conv.bias is not None else None
+        dw, db = _WGRAD[s.conv.kernel_size[0]](x, g, s.conv, s.pad)
         _acc(grads, s.conv.weight, dw)
-        _acc(grads, s.conv.bias, db)
+        _acc(grads, s.conv.bias, db if s.conv.bias is not None else None)
         if k == 0 and not need_input_grad:
             return None
         mask = _relu_mask(steps, saved, k)
@@ -318,7 +295,7 @@ def _seed(F, target, stats, wts, out, acc: bool):
 def _vgg_saving(model, x, levels=5):
     steps, saved, taps = [], [], []
     for i in range(levels):
-        st = plan.compile_layers(getattr(model, f"enc_{i + 1}").children())
+        st = plan.of(getattr(model, f"enc_{i + 1}"))
         x, sv = _run_steps_saving(st, x)
         steps += st
         saved += sv
@@ -450,8 +427,8 @@ class _AdaINRPStep(torch.autograd.Function):
     def forward(ctx, content, style, model, cfg, *params):
         with ops.precise_convs("adain"):
             n = content.shape[0]
-            enc_steps = plan.compile_layers(model.rp_shared_encoder.children())
-            dec_steps = plan.compile_layers(model.rp_decoder.children())
+            enc_steps = plan.of(model.rp_shared_encoder)
+            dec_steps = plan.of(model.rp_decoder)
             feats, enc_saved = _run_steps_saving(enc_steps, torch.cat([content, style], dim=0))
             ctx.adain = _adain_state(feats[:n], feats[n:])
             t = ops.adaptive_instance_normalization(feats[:n], feats[n:])
@@ -486,11 +463,10 @@ class _WCTRPStep(torch.autograd.Function):
         with ops.precise_convs("wct"):
             n = content.shape[0]
             with ops.precise_convs(on=False):  # fuse() detaches: a constant of the step
-                feats = plan.run(plan.compile_layers(model.rp_shared_encoder.children()),
-                                 torch.cat([content, style], dim=0))
+                feats = plan.run(plan.of(model.rp_shared_encoder), torch.cat([content, style]))
             # per-image WCT status (device): train.py checks it after the step's loss sync
             t, model._wct_status = ops.wct_fuse(feats[:n], feats[n:], status=True)
-            dec_steps = plan.compile_layers(model.rp_decoder.children())
+            dec_steps = plan.of(model.rp_decoder)
             stylized, dec_saved = _run_steps_saving(dec_steps, t)
             loss = _VGGLoss(model, stylized, content, style, *cfg)
         ctx.loss, ctx.dec, ctx.params = loss, (dec_steps, dec_saved), params
@@ -536,11 +512,6 @@ def _pad1(x: torch.Tensor, reflect: bool) -> torch.Tensor:
     return out
 
 
-def _conv1x1(conv, x, residual=None):
-    return ops.conv2d(x, plan.packed_weight(conv), conv.bias, conv.out_channels, 1,
-                      residual=residual)
-
-
 def _is_adaptive(m) -> bool:
     return hasattr(m, "attention_layer")
 
@@ -550,9 +521,9 @@ def _sanet_forward(m, c, s):
     what the backward needs."""
     Fn = ops.mean_variance_norm(c)
     Gn = ops.mean_variance_norm(s)
-    F = _conv1x1(m.f, Fn)
-    G = _conv1x1(m.g, Gn)
-    H = _conv1x1(m.h, s)
+    F = plan.conv(m.f, Fn)
+    G = plan.conv(m.g, Gn)
+    H = plan.conv(m.h, s)
     if _is_adaptive(m):
         al = m.attention_layer
         O, m.claim_value, _, _ = ops.adaptive_attention(
@@ -560,7 +531,7 @@ def _sanet_forward(m, c, s):
             float(al.value_interval))
     else:
         O = ops.sanet_attention(F, G, H)
-    return _conv1x1(m.out_conv, O, residual=c), (Fn, Gn, s, F, G, H, O, c)
+    return plan.conv(m.out_conv, O, residual=c), (Fn, Gn, s, F, G, H, O, c)
 
 
 def _sanet_backward(m, saved, d_out, grads):
@@ -573,7 +544,7 @@ def _sanet_backward(m, saved, d_out, grads):
     dw, db = _lin_grads(d_out, O)
     _acc(grads, m.out_conv.weight, dw)
     _acc(grads, m.out_conv.bias, db)
-    dO = ops.conv2d(d_out, flip_packed_weight(m.out_conv), None, ch, 1).contiguous()
+    dO = plan.conv(m.out_conv, d_out, flip=True).contiguous()
     dF, dG, dH = torch.empty_like(F), torch.empty_like(G), torch.empty_like(H)
     if _is_adaptive(m):
         # rpst_adaptive_attention_backward forms P and the clamped attention Q from the
@@ -611,9 +582,7 @@ def _sanet_backward(m, saved, d_out, grads):
 def _transform_forward(tr, c4, s4, c5, s5):
     a, sa = _sanet_forward(tr.sanet4_1, c4, s4)
     b, sb = _sanet_forward(tr.sanet5_1, c5, s5)
-    c = tr.merge_conv
-    out = ops.conv2d(a, plan.packed_weight(c), c.bias, c.out_channels, 3, pad=ops.PAD_REFLECT,
-                     in_op=ops.IN_ADD_UPSAMPLE2, aux=b)
+    out = plan.conv(tr.merge_conv, a, pad=ops.PAD_REFLECT, in_op=ops.IN_ADD_UPSAMPLE2, aux=b)
     z = a + ops.upsample_nearest2x(b)  # merge conv input, for its weight gradient
     return out, (sa, sb, z)
 
@@ -648,7 +617,7 @@ class _SAModelStep(torch.autograd.Function):
                 feats.append(x)
             sf = [f[:n].contiguous() for f in feats]
             cf = [f[n:].contiguous() for f in feats]
-            dec_steps = plan.compile_layers(model.decoder.children())
+            dec_steps = plan.of(model.decoder)
             tr = model.transform
             br = {}
             for name, (a4, b4, a5, b5) in (("gt", (cf[3], sf[3], cf[4], sf[4])),
@@ -764,7 +733,7 @@ class _SourceNetStep(torch.autograd.Function):
                     ref = getattr(model, f"enc_{i + 1}")(ref)
                     targets.append(ref)
             t = ops.adaptive_instance_normalization(targets[3][n:], targets[3][:n])
-            dec_steps = plan.compile_layers(model.decoder.children())
+            dec_steps = plan.of(model.decoder)
             stylized, dec_saved = _run_steps_saving(dec_steps, t)
             loss = _VGGLoss(model, stylized, content, style, *cfg, targets=targets,
                             content_target=t)
@@ -817,7 +786,7 @@ class _MultiScaleStep(torch.autograd.Function):
             for blocks in fam.levels:
                 branches, outs = [], []
                 for blk in blocks:
-                    st = plan.compile_layers(plan.block_layers(blk))
+                    st = plan.of(blk)
                     y, sv = _run_steps_saving(st, x)
                     branches.append((st, sv))
                     outs.append(y)
@@ -834,7 +803,7 @@ class _MultiScaleStep(torch.autograd.Function):
                 z = ops.adaptive_instance_normalization(cf, lv[n:])
                 if k:
                     z.add_(y)
-                st = plan.compile_layers(plan.block_layers(blk))
+                st = plan.of(blk)
                 y, sv = _run_steps_saving(st, z)
                 dec.append((st, sv))
                 if k == L - 1:

@@ -109,6 +109,45 @@ def _ptr(t: Optional[torch.Tensor]) -> Optional[int]:
     return None if t is None else t.data_ptr()
 
 
+def _shape(x) -> tuple:  # x: a tensor or its shape
+    return tuple(x.shape) if isinstance(x, torch.Tensor) else tuple(x)
+
+
+# ---- the frame of the conv wrappers: checked input, output, bias pointer, trace ----------
+def _conv_in(x: torch.Tensor, *others):
+    """x (N, Cin, H, W) and `others` (None entries skipped) pass _check -> x contiguous, shape."""
+    assert x.dim() == 4
+    _check(x, *others)
+    x = _c(x)
+    return x, tuple(x.shape)
+
+
+def _conv_out(x: torch.Tensor, shape, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """A conv's output on x's device: a new fp32 tensor of `shape`, or the caller's `out`
+    validated against it (a channel count of None: any)."""
+    if out is None:
+        return torch.empty(shape, device=x.device, dtype=torch.float32)
+    n, c, h, w = shape
+    if out.dim() != 4 or not out.is_contiguous() or out.dtype != torch.float32 or \
+            out.device != x.device or (out.shape[0], out.shape[2], out.shape[3]) != (n, h, w) \
+            or (c is not None and out.shape[1] != c):
+        raise ValueError(f"rpst: out must be a contiguous fp32 ({n}, {'C' if c is None else c}, "
+                         f"{h}, {w}) tensor on the input's device")
+    return out
+
+
+def _bias_ptr(bias: Optional[torch.Tensor]) -> Optional[int]:
+    return _ptr(None if bias is None else _c(bias.detach()))
+
+
+def _conv_traced(shape, cout: int, ksize: int, in_op: int, moved: int, name=None):
+    """Trace entry of a k x k conv over a (n, cin, hs, ws) source: `moved` fp32 elements."""
+    n, cin, hs, ws = shape
+    h, w = conv_out_hw(hs, ws, in_op)
+    return _traced(name or _conv_name(ksize, cin, cout, hs, ws, n, in_op),
+                   2.0 * n * cout * h * w * cin * ksize * ksize, 4.0 * moved)
+
+
 def calc_mean_std(feat: torch.Tensor, eps: float = 1e-5) -> Tuple[torch.Tensor, torch.Tensor]:
     """network/base.py:399-407 on the GPU: (N,C,H,W) -> mean, std of shape (N,C,1,1)."""
     assert feat.dim() == 4
@@ -289,6 +328,16 @@ def pack_conv7_weight(weight: torch.Tensor) -> torch.Tensor:
     return packed
 
 
+def conv_weight_flip(weight: torch.Tensor) -> torch.Tensor:
+    """(Cout, Cin, k, k) -> the flip-transposed (Cin, Cout, k, k) weights of the conv's dgrad
+    (rpst_conv_weight_flip)."""
+    wd = weight.detach().contiguous()
+    cout, cin, k, _ = wd.shape
+    wt = torch.empty((cin, cout, k, k), device=wd.device, dtype=torch.float32)
+    _lib.call("rpst_conv_weight_flip", wd.data_ptr(), wt.data_ptr(), cout, cin, k, _stream(wd))
+    return wt
+
+
 def conv2d_k7(x: torch.Tensor, packed: torch.Tensor, bias: Optional[torch.Tensor], cout: int,
               pad: int = PAD_REFLECT, act=ACT_NONE, out: Optional[torch.Tensor] = None,
               out_channel_offset: int = 0, x2: Optional[torch.Tensor] = None) -> torch.Tensor:
@@ -296,28 +345,20 @@ def conv2d_k7(x: torch.Tensor, packed: torch.Tensor, bias: Optional[torch.Tensor
     out_channel_offset + cout) of `out` (a contiguous (N, C_total, H, W) tensor whose other
     channels are left alone; default: a new (N, cout, H, W) tensor). x2: the conv runs over
     the batch cat([x, x2]) of two equal halves, read in place. Returns `out`."""
-    assert x.dim() == 4
-    _check(x, x2, packed, bias, out)
-    x = _c(x)
-    n, cin, h, w = x.shape
+    x, (n, cin, h, w) = _conv_in(x, x2, packed, bias, out)
     if x2 is not None:
         if x2.shape != x.shape:
             raise ValueError("rpst: conv2d_k7's second input must have the first one's shape")
         x2 = _c(x2)
         n *= 2
-    if out is None:
-        if out_channel_offset:
-            raise ValueError("rpst: conv2d_k7 with a channel offset needs the tensor to write into")
-        out = torch.empty((n, cout, h, w), device=x.device, dtype=torch.float32)
-    elif out.dim() != 4 or not out.is_contiguous() or out.shape[0] != n or \
-            tuple(out.shape[2:]) != (h, w) or out.device != x.device:
-        raise ValueError(f"rpst: out must be a contiguous fp32 ({n}, C, {h}, {w}) tensor on the "
-                         "input's device")
-    with _traced(f"conv7x7 {cin}->{cout} {h}x{w} N{n}", 2.0 * n * cout * h * w * cin * 49,
-                 4.0 * n * (cin + cout) * h * w):
-        _lib.call("rpst_conv7", x.data_ptr(), _ptr(x2), packed.data_ptr(),
-                  _ptr(None if bias is None else _c(bias.detach())), out.data_ptr(), n, cin, h,
-                  w, cout, pad, _act(act), int(out_channel_offset), out.shape[1], _stream(x))
+    if out is None and out_channel_offset:
+        raise ValueError("rpst: conv2d_k7 with a channel offset needs the tensor to write into")
+    out = _conv_out(x, (n, cout if out is None else None, h, w), out)
+    with _conv_traced((n, cin, h, w), cout, 7, IN_NONE, n * (cin + cout) * h * w,
+                      f"conv7x7 {cin}->{cout} {h}x{w} N{n}"):
+        _lib.call("rpst_conv7", x.data_ptr(), _ptr(x2), packed.data_ptr(), _bias_ptr(bias),
+                  out.data_ptr(), n, cin, h, w, cout, pad, _act(act), int(out_channel_offset),
+                  out.shape[1], _stream(x))
     return out
 
 
@@ -408,7 +449,7 @@ def pool_pass_pays(x, cout: int, ksize: int) -> bool:
     shape): True when the library would run the pooled map's conv as F(4x4,3x3) (measured:
     pool pass + F(4x4) is faster than the F(2x2) conv with the pool fused into its loader,
     profiles/r01_bench_sanet_w4*)."""
-    n, cin, h, w = tuple(x.shape) if isinstance(x, torch.Tensor) else tuple(x)
+    n, cin, h, w = _shape(x)
     return ksize == 3 and _lib.load().rpst_conv2d_algorithm(
         cout, cin, (h + 1) // 2, (w + 1) // 2, ksize, IN_NONE) == 2
 
@@ -418,19 +459,16 @@ def conv2d_pair(x: torch.Tensor, x2: torch.Tensor, packed: torch.Tensor,
                 relu: bool = False) -> torch.Tensor:
     """conv2d over the batch cat([x, x2]) without materialising the concatenation
     (rpst_conv2d_pair: the kernel reads images >= len(x) from x2 in place)."""
-    assert x.dim() == 4 and x2.dim() == 4 and tuple(x.shape[1:]) == tuple(x2.shape[1:])
-    _check(x, packed, bias, None, None)
-    _check(x2, packed, bias, None, None)
-    x, x2 = _c(x), _c(x2)
-    n1, cin, hs, ws = x.shape
+    assert x2.dim() == 4 and tuple(x.shape[1:]) == tuple(x2.shape[1:])
+    x, (n1, cin, hs, ws) = _conv_in(x, x2, packed, bias)
+    x2 = _c(x2)
     n = n1 + x2.shape[0]
-    out = torch.empty((n, cout, hs, ws), device=x.device, dtype=torch.float32)
-    with _traced(_conv_name(ksize, cin, cout, hs, ws, n, IN_NONE),
-                 2.0 * n * cout * hs * ws * cin * ksize * ksize,
-                 4.0 * (x.numel() + x2.numel() + out.numel())):
+    out = _conv_out(x, (n, cout, hs, ws))
+    with _conv_traced((n, cin, hs, ws), cout, ksize, IN_NONE,
+                      x.numel() + x2.numel() + out.numel()):
         _lib.call("rpst_conv2d_pair", x.data_ptr(), x2.data_ptr(), n1, packed.data_ptr(),
-                  _ptr(None if bias is None else _c(bias.detach())), out.data_ptr(), n, cin,
-                  hs, ws, cout, ksize, pad, _act(relu), _stream(x))
+                  _bias_ptr(bias), out.data_ptr(), n, cin, hs, ws, cout, ksize, pad, _act(relu),
+                  _stream(x))
     return out
 
 
@@ -441,15 +479,11 @@ def conv2d(x: torch.Tensor, packed: torch.Tensor, bias: Optional[torch.Tensor], 
     """out = act(conv_k(in_op(x)) + bias) [+ residual]; see include/rpst.h. fold: let the
     library fold an ADAIN loader into per-image weights when it has a workspace for it
     (rpst_conv2d_ws); False keeps the affine in the tile loader (rpst_conv2d)."""
-    assert x.dim() == 4
     if in_op == IN_ADD_ADAIN:
         raise ValueError("rpst: the skip-AdaIN operator takes two inputs: use conv2d_skip_adain")
-    _check(x, packed, bias, aux, residual)
-    x = _c(x)
-    n, cin, hs, ws = x.shape
+    x, (n, cin, hs, ws) = _conv_in(x, packed, bias, aux, residual)
     h, w = conv_out_hw(hs, ws, in_op)
-    if out is None:
-        out = torch.empty((n, cout, h, w), device=x.device, dtype=torch.float32)
+    out = _conv_out(x, (n, cout, h, w), out)
     if residual is not None:
         residual = _c(residual)
         assert tuple(residual.shape) == (n, cout, h, w)
@@ -459,22 +493,16 @@ def conv2d(x: torch.Tensor, packed: torch.Tensor, bias: Optional[torch.Tensor], 
             assert aux.numel() == 4 * n * cin, "ADAIN aux = [mean_c|mean_s|std_c|std_s]"
         else:
             assert tuple(aux.shape) == (n, cin, h // 2, w // 2)
-    with _traced(_conv_name(ksize, cin, cout, hs, ws, n, in_op),
-                 2.0 * n * cout * h * w * cin * ksize * ksize,
-                 4.0 * (x.numel() + n * cout * h * w)):
+    with _conv_traced(x.shape, cout, ksize, in_op, x.numel() + out.numel()):
         nbytes = _lib.load().rpst_conv2d_workspace_size(n, cin, hs, ws, cout, ksize,
                                                         in_op) if fold else 0
+        args = (x.data_ptr(), _ptr(aux), packed.data_ptr(), _bias_ptr(bias), _ptr(residual),
+                out.data_ptr(), n, cin, hs, ws, cout, ksize, pad, in_op, _act(relu))
         if nbytes:
             ws_t = torch.empty(nbytes, device=x.device, dtype=torch.uint8)
-            _lib.call("rpst_conv2d_ws", x.data_ptr(), _ptr(aux), packed.data_ptr(),
-                      _ptr(None if bias is None else _c(bias.detach())), _ptr(residual),
-                      out.data_ptr(), n, cin, hs, ws, cout, ksize, pad, in_op, _act(relu),
-                      ws_t.data_ptr(), nbytes, _stream(x))
+            _lib.call("rpst_conv2d_ws", *args, ws_t.data_ptr(), nbytes, _stream(x))
         else:
-            _lib.call("rpst_conv2d", x.data_ptr(), _ptr(aux), packed.data_ptr(),
-                      _ptr(None if bias is None else _c(bias.detach())), _ptr(residual),
-                      out.data_ptr(), n, cin, hs, ws, cout, ksize, pad, in_op, _act(relu),
-                      _stream(x))
+            _lib.call("rpst_conv2d", *args, _stream(x))
     return out
 
 
@@ -483,7 +511,7 @@ def conv2d_pool_fuses(x: torch.Tensor, cout: int, ksize: int, in_op: int = IN_NO
     max-pooled (rpst_conv2d_pool)."""
     if os.environ.get("RPST_POOL_EPILOGUE", "") == "0":  # A/B switch: the separate pool pass
         return False
-    n, cin, hs, ws = x.shape
+    n, cin, hs, ws = _shape(x)
     return in_op in (IN_NONE, IN_ADAIN, IN_UPSAMPLE2) and _lib.load().rpst_conv2d_algorithm(
         cout, cin, hs, ws, ksize, in_op) == 2
 
@@ -494,19 +522,14 @@ def conv2d_pool(x: torch.Tensor, packed: torch.Tensor, bias: Optional[torch.Tens
     """max_pool2d(conv2d(x), 2, 2, ceil_mode=True) with the pool in the F(4x4) epilogue
     (rpst_conv2d_pool; the full-resolution output is never written). Needs
     conv2d_pool_fuses(x, cout, ksize, in_op)."""
-    assert x.dim() == 4 and in_op in (IN_NONE, IN_UPSAMPLE2)
-    _check(x, packed, bias, None, None)
-    x = _c(x)
-    n, cin, hs, ws = x.shape
+    assert in_op in (IN_NONE, IN_UPSAMPLE2)
+    x, (n, cin, hs, ws) = _conv_in(x, packed, bias)
     h, w = conv_out_hw(hs, ws, in_op)
-    out = torch.empty((n, cout, (h + 1) // 2, (w + 1) // 2), device=x.device,
-                      dtype=torch.float32)
-    with _traced(_conv_name(ksize, cin, cout, hs, ws, n, in_op),
-                 2.0 * n * cout * h * w * cin * ksize * ksize,
-                 4.0 * (x.numel() + out.numel())):
-        _lib.call("rpst_conv2d_pool", x.data_ptr(), None, packed.data_ptr(),
-                  _ptr(None if bias is None else _c(bias.detach())), out.data_ptr(), n, cin,
-                  hs, ws, cout, ksize, pad, in_op, _act(relu), _stream(x))
+    out = _conv_out(x, (n, cout, (h + 1) // 2, (w + 1) // 2))
+    with _conv_traced(x.shape, cout, ksize, in_op, x.numel() + out.numel()):
+        _lib.call("rpst_conv2d_pool", x.data_ptr(), None, packed.data_ptr(), _bias_ptr(bias),
+                  out.data_ptr(), n, cin, hs, ws, cout, ksize, pad, in_op, _act(relu),
+                  _stream(x))
     return out
 
 
@@ -514,14 +537,11 @@ def conv2d_masked(x: torch.Tensor, packed: torch.Tensor, cout: int, ksize: int,
                   mask: torch.Tensor, pad: int = PAD_ZERO) -> torch.Tensor:
     """out = conv_k(x), zeroed where mask <= 0 (rpst_conv2d_masked): a conv dgrad fused with
     the ReLU backward of the layer before it (mask = that ReLU's output)."""
-    _check(x, packed, mask)
-    x, mask = _c(x), _c(mask)
-    n, cin, h, w = x.shape
+    x, (n, cin, h, w) = _conv_in(x, packed, mask)
+    mask = _c(mask)
     assert tuple(mask.shape) == (n, cout, h, w)
-    out = torch.empty((n, cout, h, w), device=x.device, dtype=torch.float32)
-    with _traced(_conv_name(ksize, cin, cout, h, w, n, IN_NONE),
-                 2.0 * n * cout * h * w * cin * ksize * ksize,
-                 4.0 * (x.numel() + 2 * n * cout * h * w)):
+    out = _conv_out(x, (n, cout, h, w))
+    with _conv_traced(x.shape, cout, ksize, IN_NONE, x.numel() + 2 * out.numel()):
         _lib.call("rpst_conv2d_masked", x.data_ptr(), packed.data_ptr(), None, mask.data_ptr(),
                   out.data_ptr(), n, cin, h, w, cout, ksize, pad, _stream(x))
     return out
@@ -534,19 +554,15 @@ def conv2d_skip_adain(x: torch.Tensor, content: torch.Tensor, params: torch.Tens
     """out = act(conv(pad(x + AdaIN(content))) + bias): the skip fusion of
     MultiScaleAdaINRPNet.decode (adain_rp.py:301); params = adain_params(...) of
     (content, style) — the sum is formed in the conv's tile loader."""
-    assert x.dim() == 4 and x.shape == content.shape
-    _check(x, content, params, packed, bias)
-    x, content, params = _c(x), _c(content), _c(params)
-    n, cin, h, w = x.shape
+    assert x.shape == content.shape
+    x, (n, cin, h, w) = _conv_in(x, content, params, packed, bias)
+    content, params = _c(content), _c(params)
     assert params.numel() == 4 * n * cin, "params = [mean_c|mean_s|std_c|std_s]"
-    if out is None:
-        out = torch.empty((n, cout, h, w), device=x.device, dtype=torch.float32)
-    with _traced(_conv_name(ksize, cin, cout, h, w, n, IN_ADD_ADAIN),
-                 2.0 * n * cout * h * w * cin * ksize * ksize,
-                 4.0 * (2 * x.numel() + n * cout * h * w)):
+    out = _conv_out(x, (n, cout, h, w), out)
+    with _conv_traced(x.shape, cout, ksize, IN_ADD_ADAIN, 2 * x.numel() + out.numel()):
         _lib.call("rpst_conv2d_skip_adain", x.data_ptr(), content.data_ptr(), params.data_ptr(),
-                  packed.data_ptr(), _ptr(None if bias is None else _c(bias.detach())),
-                  out.data_ptr(), n, cin, h, w, cout, ksize, pad, _act(relu), _stream(x))
+                  packed.data_ptr(), _bias_ptr(bias), out.data_ptr(), n, cin, h, w, cout, ksize,
+                  pad, _act(relu), _stream(x))
     return out
 
 
@@ -557,29 +573,20 @@ def conv2d_stats(x: torch.Tensor, packed: torch.Tensor, bias: Optional[torch.Ten
     """conv2d plus calc_mean_std of its output, reduced in the conv epilogue:
     returns (out, mean (N,Cout,1,1), std (N,Cout,1,1)). store_n: write out[:store_n] only
     (rpst_conv2d_stats_store; out[store_n:] unspecified, the statistics cover every image)."""
-    assert x.dim() == 4
-    _check(x, packed, bias, aux)
-    x = _c(x)
-    n, cin, hs, ws = x.shape
-    h, w = conv_out_hw(hs, ws, in_op)
-    out = torch.empty((n, cout, h, w), device=x.device, dtype=torch.float32)
+    x, (n, cin, hs, ws) = _conv_in(x, packed, bias, aux)
+    out = _conv_out(x, (n, cout, *conv_out_hw(hs, ws, in_op)))
     mean = torch.empty((n, cout, 1, 1), device=x.device, dtype=torch.float32)
     std = torch.empty_like(mean)
-    lib = _lib.load()
-    nbytes = lib.rpst_conv2d_stats_workspace_size(n, cin, hs, ws, cout, ksize, in_op)
+    nbytes = _lib.load().rpst_conv2d_stats_workspace_size(n, cin, hs, ws, cout, ksize, in_op)
     ws_t = torch.empty(nbytes, device=x.device, dtype=torch.uint8)
-    with _traced(_conv_name(ksize, cin, cout, hs, ws, n, in_op), 2.0 * n * cout * h * w * cin * ksize * ksize,
-                 4.0 * (x.numel() + n * cout * h * w)):
+    args = (x.data_ptr(), _ptr(aux), packed.data_ptr(), _bias_ptr(bias), None, out.data_ptr(), n,
+            cin, hs, ws, cout, ksize, pad, in_op, _act(relu), mean.data_ptr(), std.data_ptr(), eps)
+    with _conv_traced(x.shape, cout, ksize, in_op, x.numel() + out.numel()):
         if store_n is None or store_n >= n:
-            _lib.call("rpst_conv2d_stats", x.data_ptr(), _ptr(aux), packed.data_ptr(),
-                      _ptr(None if bias is None else _c(bias.detach())), None, out.data_ptr(), n,
-                      cin, hs, ws, cout, ksize, pad, in_op, _act(relu), mean.data_ptr(),
-                      std.data_ptr(), eps, ws_t.data_ptr(), nbytes, _stream(x))
+            _lib.call("rpst_conv2d_stats", *args, ws_t.data_ptr(), nbytes, _stream(x))
         else:
-            _lib.call("rpst_conv2d_stats_store", x.data_ptr(), _ptr(aux), packed.data_ptr(),
-                      _ptr(None if bias is None else _c(bias.detach())), None, out.data_ptr(), n,
-                      cin, hs, ws, cout, ksize, pad, in_op, _act(relu), mean.data_ptr(),
-                      std.data_ptr(), eps, int(store_n), ws_t.data_ptr(), nbytes, _stream(x))
+            _lib.call("rpst_conv2d_stats_store", *args, int(store_n), ws_t.data_ptr(), nbytes,
+                      _stream(x))
     return out, mean, std
 
 
@@ -609,15 +616,13 @@ def conv2d_gated(x: torch.Tensor, packed: torch.Tensor, bias: Optional[torch.Ten
                  stats: bool = False, eps: float = 1e-5):
     """out = relu(gate[n, co] * (conv_k(x) + bias) + residual) (rpst_conv2d_gated, the tail of
     an SE block); stats: also calc_mean_std of out -> (out, mean, std)."""
-    assert x.dim() == 4
-    _check(x, packed, bias, gate, residual)
-    x, gate, residual = _c(x), _c(gate), _c(residual)
-    n, cin, h, w = x.shape
+    x, (n, cin, h, w) = _conv_in(x, packed, bias, gate, residual)
+    gate, residual = _c(gate), _c(residual)
     if gate.numel() != n * cout or gate.shape[0] != n:
         raise ValueError(f"rpst: gate must be (N, Cout), got {tuple(gate.shape)}")
     if tuple(residual.shape) != (n, cout, h, w):
         raise ValueError("rpst: residual must have the output's shape")
-    out = torch.empty((n, cout, h, w), device=x.device, dtype=torch.float32)
+    out = _conv_out(x, (n, cout, h, w))
     mean = std = None
     nbytes = 0
     if stats:
@@ -625,13 +630,11 @@ def conv2d_gated(x: torch.Tensor, packed: torch.Tensor, bias: Optional[torch.Ten
         std = torch.empty_like(mean)
         nbytes = _lib.load().rpst_conv2d_gated_workspace_size(n, cin, h, w, cout, ksize)
     ws_t = torch.empty(nbytes, device=x.device, dtype=torch.uint8) if nbytes else None
-    with _traced(f"gated{ksize}x{ksize} {cin}->{cout} {h}x{w} N{n}",
-                 2.0 * n * cout * h * w * cin * ksize * ksize,
-                 4.0 * (x.numel() + 2 * out.numel())):
-        _lib.call("rpst_conv2d_gated", x.data_ptr(), packed.data_ptr(),
-                  _ptr(None if bias is None else _c(bias.detach())), gate.data_ptr(),
-                  residual.data_ptr(), out.data_ptr(), n, cin, h, w, cout, ksize, _ptr(mean),
-                  _ptr(std), eps, _ptr(ws_t), nbytes, _stream(x))
+    with _conv_traced(x.shape, cout, ksize, IN_NONE, x.numel() + 2 * out.numel(),
+                      f"gated{ksize}x{ksize} {cin}->{cout} {h}x{w} N{n}"):
+        _lib.call("rpst_conv2d_gated", x.data_ptr(), packed.data_ptr(), _bias_ptr(bias),
+                  gate.data_ptr(), residual.data_ptr(), out.data_ptr(), n, cin, h, w, cout,
+                  ksize, _ptr(mean), _ptr(std), eps, _ptr(ws_t), nbytes, _stream(x))
     return (out, mean, std) if stats else out
 
 
@@ -974,20 +977,16 @@ def conv2d_mix(x: torch.Tensor, T: torch.Tensor, offset: torch.Tensor, packed: t
                relu=False) -> torch.Tensor:
     """out = act(conv(pad(T_n x + c_n)) + bias) per image (include/rpst.h rpst_conv2d_mix):
     the WCT colour transform (wct_rp.py:109-113) applied inside the consumer conv."""
-    assert x.dim() == 4
-    _check(x, packed, bias)
+    x, (n, cin, h, w) = _conv_in(x, packed, bias)
     _check(T, offset, dtype=torch.float64)
-    x, T, offset = _c(x), _c(T), _c(offset)
-    n, cin, h, w = x.shape
+    T, offset = _c(T), _c(offset)
     assert tuple(T.shape) == (n, cin, cin) and tuple(offset.shape) == (n, cin)
-    out = torch.empty((n, cout, h, w), device=x.device, dtype=torch.float32)
+    out = _conv_out(x, (n, cout, h, w))
     nbytes = _lib.load().rpst_conv2d_mix_workspace_size(n, cin, h, w, cout, ksize)
     ws = torch.empty(nbytes, device=x.device, dtype=torch.uint8)
-    with _traced(_conv_name(ksize, cin, cout, h, w, n, IN_NONE).replace(" op0", " mix"),
-                 2.0 * n * cout * h * w * cin * ksize * ksize,
-                 4.0 * (x.numel() + n * cout * h * w)):
+    with _conv_traced(x.shape, cout, ksize, IN_NONE, x.numel() + out.numel(),
+                      _conv_name(ksize, cin, cout, h, w, n, IN_NONE).replace(" op0", " mix")):
         _lib.call("rpst_conv2d_mix", x.data_ptr(), T.data_ptr(), offset.data_ptr(),
-                  packed.data_ptr(), _ptr(None if bias is None else _c(bias.detach())),
-                  out.data_ptr(), n, cin, h, w, cout, ksize, pad, _act(relu), ws.data_ptr(),
-                  nbytes, _stream(x))
+                  packed.data_ptr(), _bias_ptr(bias), out.data_ptr(), n, cin, h, w, cout, ksize,
+                  pad, _act(relu), ws.data_ptr(), nbytes, _stream(x))
     return out

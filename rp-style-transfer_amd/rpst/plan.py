@@ -8,6 +8,11 @@ adain_rp.py:513-514, one rpst_conv7 launch, no input operator).
 Each such group becomes ONE rpst_conv2d launch: the pool/upsample and the padding are
 applied by the conv kernel's tile loader and ReLU by its epilogue, so no intermediate
 (padded, pooled or upsampled) tensor is ever written to HBM.
+
+compile_layers / of group the layers into steps; lower() decides on the host which launch each
+step becomes (Launch records; no tensor touched, every refusal raised there); run() performs
+that list; conv() is the one mapping from a conv module to an ops call, for run() and for
+single convs (SANet, rpst.autograd); packed_weight() caches the kernel-layout weights.
 """
 from __future__ import annotations
 
@@ -133,23 +138,35 @@ def compile_layers(layers: Iterable[nn.Module]) -> List[object]:
     return steps
 
 
-def packed_weight(conv: nn.Conv2d) -> torch.Tensor:
-    """K-major packed copy of conv.weight, cached on the module and refreshed whenever
-    the parameter is replaced or modified in place (load_state_dict, optimizer step)."""
-    w = conv.weight
-    key = (w.device, w.data_ptr(), w._version)
-    cached = getattr(conv, "_rpst_packed", None)
-    if cached is not None and cached[0] == key:
-        return cached[1]
-    with torch.no_grad():
-        pack = ops.pack_conv7_weight if tuple(w.shape[2:]) == (7, 7) else ops.pack_conv_weight
-        packed = pack(w.detach())
-    conv._rpst_packed = (key, packed)
-    return packed
-
-
 def _tensor_key(t: torch.Tensor):
     return (t.device, t.data_ptr(), t._version)
+
+
+def cached(module: nn.Module, attr: str, key, make):
+    """make() (run without grad), kept on the module as `attr` while `key` compares equal. Keys
+    hold _tensor_key (device, data_ptr, _version) of every tensor the value derives from, so
+    load_state_dict, .to() and in-place updates (optimizer step) refresh the value."""
+    hit = getattr(module, attr, None)
+    if hit is not None and hit[0] == key:
+        return hit[1]
+    with torch.no_grad():
+        value = make()
+    setattr(module, attr, (key, value))
+    return value
+
+
+def packed_weight(conv: nn.Conv2d, flip: bool = False) -> torch.Tensor:
+    """conv.weight in its kernel's K-major layout (rpst_conv7's for a 7x7 conv, else the conv /
+    Winograd kernels'), cached on the module. flip: of the flip-transposed weights (Cin, Cout,
+    k, k) instead, which are the weights of the conv's dgrad."""
+    def make():
+        w = conv.weight.detach()
+        if flip:
+            w = ops.conv_weight_flip(w)
+        return (ops.pack_conv7_weight if w.shape[2] == 7 else ops.pack_conv_weight)(w)
+
+    return cached(conv, "_rpst_flip_packed" if flip else "_rpst_packed",
+                  _tensor_key(conv.weight), make)
 
 
 def fold_batchnorm(conv: nn.Conv2d, bn: nn.BatchNorm2d):
@@ -172,10 +189,8 @@ def se_folded(block: nn.Module):
     key = tuple(_tensor_key(t) for conv, bn in pairs
                 for t in (conv.weight, bn.weight, bn.bias, bn.running_mean, bn.running_var))
     key += tuple(bn.eps for _, bn in pairs)
-    cached = getattr(block, "_rpst_se", None)
-    if cached is not None and cached[0] == key:
-        return cached[1]
-    with torch.no_grad():
+
+    def fold():
         folded = []
         for conv, bn in pairs:
             if conv.bias is not None or not bn.affine or not bn.track_running_stats:
@@ -185,140 +200,167 @@ def se_folded(block: nn.Module):
             folded.append((ops.pack_conv_weight(w), b))
             if conv is block.conv3:
                 folded.append(w.view(w.shape[0], w.shape[1]))
-    block._rpst_se = (key, folded)
-    return folded
+        return folded
+
+    return cached(block, "_rpst_se", key, fold)
+
+
+def of(module: nn.Module) -> List[object]:
+    """The compiled steps of a KernelSequential / nn.Sequential (its children) or of a
+    Conv2dBlock (block_layers); compiled per call, so a replaced child needs no invalidation."""
+    return compile_layers(module.children() if isinstance(module, nn.Sequential)
+                          else block_layers(module))
 
 
 def is_k7(step) -> bool:
     return isinstance(step, ConvStep) and step.conv.kernel_size[0] == 7
 
 
-def run_conv7_step(step: ConvStep, x: torch.Tensor, out=None, out_channel_offset: int = 0,
-                   x2=None) -> torch.Tensor:
-    """A 7x7 ConvStep through rpst_conv7; out / out_channel_offset: ops.conv2d_k7."""
-    c = step.conv
-    return ops.conv2d_k7(x, packed_weight(c), c.bias, c.out_channels, pad=step.pad,
-                         act=step.relu, out=out, out_channel_offset=out_channel_offset, x2=x2)
-
-
-def run_conv_step(step: ConvStep, x: torch.Tensor, aux=None, residual=None) -> torch.Tensor:
-    c = step.conv
-    if is_k7(step):
-        if step.in_op != ops.IN_NONE or aux is not None or residual is not None:
+def conv(step_or_conv, x: torch.Tensor, *, op: Optional[str] = None, pad=None, in_op=None,
+         relu=None, flip: bool = False, **operands) -> torch.Tensor:
+    """One conv launch: the only place a conv module is expanded into kernel-call arguments.
+    step_or_conv: a ConvStep, or a bare nn.Conv2d (zero pad, no input operator, no activation);
+    pad / in_op / relu override the step's. op: the ops wrapper that runs (default conv2d, or
+    conv2d_k7 for a 7x7 conv); operands are that wrapper's own (aux, residual, out,
+    out_channel_offset, x2, store_n, fold; content for conv2d_skip_adain, mix = (T, c) for
+    conv2d_mix). flip: the conv's dgrad instead: flip-transposed weights, no bias."""
+    s = step_or_conv if isinstance(step_or_conv, ConvStep) else ConvStep(
+        step_or_conv, ops.PAD_ZERO, ops.IN_NONE, ops.ACT_NONE)
+    c = s.conv
+    pad = s.pad if pad is None else pad
+    in_op = s.in_op if in_op is None else in_op
+    relu = s.relu if relu is None else relu
+    w = (packed_weight(c, flip),) + ((None, c.in_channels) if flip else (c.bias, c.out_channels))
+    if c.kernel_size[0] == 7:
+        if in_op != ops.IN_NONE or any(operands.get(k) is not None for k in ("aux", "residual")):
             raise NotImplementedError("rpst plan: a 7x7 conv has no input operator / residual")
-        return run_conv7_step(step, x)
-    return ops.conv2d(x, packed_weight(c), c.bias, c.out_channels, c.kernel_size[0],
-                      pad=step.pad, in_op=step.in_op, relu=step.relu, aux=aux,
-                      residual=residual)
+        return ops.conv2d_k7(x, *w, pad=pad, act=relu, **operands)
+    w += (c.kernel_size[0],)
+    if op == "conv2d_pair":
+        return ops.conv2d_pair(x, operands["x2"], *w, pad=pad, relu=relu)
+    if op == "conv2d_mix":
+        return ops.conv2d_mix(x, *operands["mix"], *w, pad=pad, relu=relu)
+    if op == "conv2d_skip_adain":
+        return ops.conv2d_skip_adain(x, operands["content"], operands["aux"], *w, pad=pad,
+                                     relu=relu)
+    return getattr(ops, op or "conv2d")(x, *w, pad=pad, in_op=in_op, relu=relu, **operands)
+
+
+@dataclass
+class Launch:
+    """One record of lower()'s launch list."""
+    op: str                          # the ops entry that runs; "cat": torch.cat([x, x2])
+    step: Optional[ConvStep] = None  # the conv launches' step
+    in_op: int = ops.IN_NONE         # the conv's effective input operator
+    pooled: bool = False             # the conv's output comes out max-pooled (conv2d_pool)
+    takes: tuple = ()                # run()'s operands it reads: aux content mix store_n x2
+
+
+def lower(steps: List[object], shape, x2_shape=None, *, first_in_op=None,
+          first_mix: bool = False, stats_last: bool = False) -> List[Launch]:
+    """The launches run() performs for a compiled plan on an input of `shape` (over the batch
+    [x; x2] with x2_shape), in order. Host only: no tensor, no device, the library's algorithm
+    queries alone. Every refusal of run() is raised here, before any launch."""
+    n, cin, h, w = shape
+    s0 = steps[0] if steps else None
+    if is_k7(s0) and (first_in_op is not None or first_mix):
+        raise NotImplementedError("rpst plan: a 7x7 conv has no AdaIN loader / colour mix")
+    out: List[Launch] = []
+    pair = False
+    if x2_shape is not None:
+        # a plain first conv reads x and x2 in place (rpst_conv7: two equal halves)
+        pair = (isinstance(s0, ConvStep) and s0.in_op == ops.IN_NONE and not first_mix
+                and first_in_op is None and not (stats_last and len(steps) == 1)
+                and (not is_k7(s0) or tuple(shape) == tuple(x2_shape)))
+        n += x2_shape[0]
+        if not pair:
+            out.append(Launch("cat"))
+    if first_mix and not isinstance(s0, ConvStep):
+        # the colour transform only fuses into a conv: skipping it would decode raw features
+        raise NotImplementedError("rpst plan: first_mix needs a conv as the plan's first step")
+    if first_in_op is not None and not isinstance(s0, ConvStep):
+        raise NotImplementedError("rpst plan: first_in_op needs a conv as the plan's first step")
+    for i, s in enumerate(steps):
+        if not isinstance(s, ConvStep):
+            pool = s.in_op == ops.IN_MAXPOOL2
+            out.append(Launch("maxpool2x2_ceil" if pool else "upsample_nearest2x"))
+            h, w = ops.conv_out_hw(h, w, s.in_op)
+            continue
+        cout, k = s.conv.out_channels, s.conv.kernel_size[0]
+        last = stats_last and i == len(steps) - 1
+        nxt = steps[i + 1] if i + 1 < len(steps) else None
+        pooled_in = bool(out) and out[-1].pooled  # the conv before wrote its output pooled
+        rec = Launch("conv2d_k7" if k == 7 else "conv2d", s, s.in_op)
+        if i == 0 and pair:
+            rec.op, rec.takes = rec.op if k == 7 else "conv2d_pair", ("x2",)
+        elif i == 0 and first_mix:
+            if s.in_op != ops.IN_NONE or last:
+                raise NotImplementedError("rpst plan: mixed first conv with an input op / stats")
+            rec.op, rec.takes = "conv2d_mix", ("mix",)
+        elif k != 7:  # (a 7x7 conv has no statistics epilogue: calc_mean_std below)
+            if i == 0 and first_in_op is not None:
+                if s.in_op != ops.IN_NONE:
+                    raise NotImplementedError("rpst plan: first conv already has an input op")
+                rec.in_op, rec.takes = first_in_op, ("aux",)
+            if rec.in_op == ops.IN_MAXPOOL2 and pooled_in:
+                rec.in_op = ops.IN_NONE
+            elif rec.in_op == ops.IN_MAXPOOL2 and ops.pool_pass_pays((n, cin, h, w), cout, k):
+                # F(4x4,3x3) has no max-pool loader: a separate pool pass (one read of the
+                # source, one write of the pooled map) + F(4x4) beats the fused F(2x2)
+                out.append(Launch("maxpool2x2_ceil"))
+                (h, w), rec.in_op = ops.conv_out_hw(h, w, ops.IN_MAXPOOL2), ops.IN_NONE
+            if (isinstance(nxt, ConvStep) and nxt.in_op == ops.IN_MAXPOOL2 and not last
+                    and rec.in_op in (ops.IN_NONE, ops.IN_UPSAMPLE2)
+                    and ops.conv2d_pool_fuses((n, cin, h, w), cout, k, rec.in_op)
+                    and ops.pool_pass_pays((n, cout, *ops.conv_out_hw(h, w, rec.in_op)),
+                                           nxt.conv.out_channels, nxt.conv.kernel_size[0])):
+                # this conv's output only feeds the next conv's pool pass: write it pooled
+                # from the F(4x4) epilogue (never the full-resolution map)
+                rec.op, rec.pooled, rec.takes = "conv2d_pool", True, ()
+            elif rec.in_op == ops.IN_ADD_ADAIN:
+                if last:
+                    raise NotImplementedError("rpst plan: skip-AdaIN conv with statistics")
+                rec.op, rec.takes = "conv2d_skip_adain", ("content", "aux")
+            elif last:
+                rec.op, rec.takes = "conv2d_stats", rec.takes + ("store_n",)
+        out.append(rec)
+        cin, (h, w) = cout, ops.conv_out_hw(h, w, rec.in_op)
+        if rec.pooled:
+            h, w = ops.conv_out_hw(h, w, ops.IN_MAXPOOL2)
+    if stats_last and not (out and out[-1].op == "conv2d_stats"):
+        out.append(Launch("calc_mean_std"))
+    return out
 
 
 def run(steps: List[object], x: torch.Tensor, first_aux=None, first_in_op=None,
         stats_last: bool = False, first_content=None, first_mix=None, store_n=None,
         x2: Optional[torch.Tensor] = None):
-    """Run a compiled plan. first_in_op/first_aux override the first conv's input operator
-    (e.g. RPST_IN_ADAIN to fuse AdaIN into the decoder's first conv; RPST_IN_ADD_ADAIN
-    with first_content = the skip feature, for x + AdaIN(content)); first_mix = (T, c)
-    makes the first conv read T_n x + c_n (the WCT colour transform, rpst_conv2d_mix);
-    stats_last makes the last conv also return calc_mean_std of its output -> (x, mean,
-    std); with store_n that conv writes only images < store_n of x (the rest are needed only
-    through their statistics; their part of x is unspecified). x2: the plan runs over the
-    batch cat([x, x2]); a plain first conv reads both in place (rpst_conv2d_pair, or
+    """Run a compiled plan: perform lower()'s launch list. first_in_op/first_aux override the
+    first conv's input operator (e.g. RPST_IN_ADAIN to fuse AdaIN into the decoder's first
+    conv; RPST_IN_ADD_ADAIN with first_content = the skip feature, for x + AdaIN(content));
+    first_mix = (T, c) makes the first conv read T_n x + c_n (the WCT colour transform,
+    rpst_conv2d_mix); stats_last makes the last conv also return calc_mean_std of its output
+    -> (x, mean, std); with store_n that conv writes only images < store_n of x (the rest are
+    needed only through their statistics; their part of x is unspecified). x2: the plan runs
+    over the batch cat([x, x2]); a plain first conv reads both in place (rpst_conv2d_pair, or
     rpst_conv7's second input for a 7x7 conv over two equal halves), any other first step
     gets the concatenation."""
+    given = dict(aux=first_aux, content=first_content, mix=first_mix, store_n=store_n, x2=x2)
     mean = std = None
-    if steps and is_k7(steps[0]) and (first_in_op is not None or first_mix is not None):
-        raise NotImplementedError("rpst plan: a 7x7 conv has no AdaIN loader / colour mix")
-    if x2 is not None:
-        s0 = steps[0] if steps else None
-        pair = (isinstance(s0, ConvStep) and s0.in_op == ops.IN_NONE and first_mix is None
-                and first_in_op is None and not (stats_last and len(steps) == 1)
-                and (not is_k7(s0) or x.shape == x2.shape))  # rpst_conv7: two equal halves
-        if pair:
-            c = s0.conv
-            if is_k7(s0):
-                x = run_conv7_step(s0, x, x2=x2)
-            else:
-                x = ops.conv2d_pair(x, x2, packed_weight(c), c.bias, c.out_channels,
-                                    c.kernel_size[0], pad=s0.pad, relu=s0.relu)
-            steps = steps[1:]
-            if not steps:
-                if stats_last:
-                    mean, std = ops.calc_mean_std(x)
-                    return x, mean, std
-                return x
-        else:
+    for rec in lower(steps, x.shape, None if x2 is None else x2.shape, first_in_op=first_in_op,
+                     first_mix=first_mix is not None, stats_last=stats_last):
+        if rec.op == "cat":
             x = torch.cat([x, x2], dim=0)
-    if first_mix is not None and (not steps or not isinstance(steps[0], ConvStep)):
-        # the colour transform only fuses into a conv: skipping it would decode raw features
-        raise NotImplementedError("rpst plan: first_mix needs a conv as the plan's first step")
-    if first_in_op is not None and (not steps or not isinstance(steps[0], ConvStep)):
-        raise NotImplementedError("rpst plan: first_in_op needs a conv as the plan's first step")
-    pooled_in = False  # step i's input was max-pooled by step i - 1's epilogue
-    for i, s in enumerate(steps):
-        if isinstance(s, ConvStep) and i == 0 and first_mix is not None:
-            if s.in_op != ops.IN_NONE or (stats_last and len(steps) == 1):
-                raise NotImplementedError("rpst plan: mixed first conv with an input op / stats")
-            c = s.conv
-            x = ops.conv2d_mix(x, first_mix[0], first_mix[1], packed_weight(c), c.bias,
-                               c.out_channels, c.kernel_size[0], pad=s.pad, relu=s.relu)
-            continue
-        if is_k7(s):
-            # no statistics epilogue: a last 7x7 conv's statistics come from calc_mean_std of
-            # the written output (below)
-            x = run_conv7_step(s, x)
-            pooled_in = False
-            continue
-        if isinstance(s, ConvStep):
-            in_op, aux = s.in_op, None
-            if i == 0 and first_in_op is not None:
-                if s.in_op != ops.IN_NONE:
-                    raise NotImplementedError("rpst plan: first conv already has an input op")
-                in_op, aux = first_in_op, first_aux
-            c = s.conv
-            if in_op == ops.IN_MAXPOOL2 and pooled_in:
-                in_op = ops.IN_NONE
-            elif in_op == ops.IN_MAXPOOL2 and ops.pool_pass_pays(x, c.out_channels,
-                                                                 c.kernel_size[0]):
-                # F(4x4,3x3) has no max-pool loader: a separate pool pass (one read of the
-                # source, one write of the pooled map) + F(4x4) beats the fused F(2x2)
-                x, in_op = ops.maxpool2x2_ceil(x), ops.IN_NONE
-            pooled_in = False
-            nxt = steps[i + 1] if i + 1 < len(steps) else None
-            if (isinstance(nxt, ConvStep) and nxt.in_op == ops.IN_MAXPOOL2
-                    and in_op in (ops.IN_NONE, ops.IN_UPSAMPLE2)
-                    and not (stats_last and i == len(steps) - 1)
-                    and ops.conv2d_pool_fuses(x, c.out_channels, c.kernel_size[0], in_op)):
-                h, w = ops.conv_out_hw(x.shape[2], x.shape[3], in_op)
-                y_shape = (x.shape[0], c.out_channels, h, w)
-                if ops.pool_pass_pays(y_shape, nxt.conv.out_channels, nxt.conv.kernel_size[0]):
-                    # this conv's output only feeds the next conv's pool pass: write it
-                    # pooled from the F(4x4) epilogue (never the full-resolution map)
-                    x = ops.conv2d_pool(x, packed_weight(c), c.bias, c.out_channels,
-                                        c.kernel_size[0], pad=s.pad, in_op=in_op, relu=s.relu)
-                    pooled_in = True
-                    continue
-            if in_op == ops.IN_ADD_ADAIN:
-                if stats_last and i == len(steps) - 1:
-                    raise NotImplementedError("rpst plan: skip-AdaIN conv with statistics")
-                x = ops.conv2d_skip_adain(x, first_content, aux, packed_weight(c), c.bias,
-                                          c.out_channels, c.kernel_size[0], pad=s.pad,
-                                          relu=s.relu)
-            elif stats_last and i == len(steps) - 1:
-                x, mean, std = ops.conv2d_stats(x, packed_weight(c), c.bias, c.out_channels,
-                                                c.kernel_size[0], pad=s.pad, in_op=in_op,
-                                                relu=s.relu, aux=aux, store_n=store_n)
-            else:
-                x = ops.conv2d(x, packed_weight(c), c.bias, c.out_channels, c.kernel_size[0],
-                               pad=s.pad, in_op=in_op, relu=s.relu, aux=aux)
-        elif s.in_op == ops.IN_MAXPOOL2:
-            x = ops.maxpool2x2_ceil(x)
-        else:
-            x = ops.upsample_nearest2x(x)
-    if stats_last:
-        if mean is None:
+        elif rec.op == "calc_mean_std":
             mean, std = ops.calc_mean_std(x)
-        return x, mean, std
-    return x
+        elif rec.step is None:
+            x = getattr(ops, rec.op)(x)
+        else:
+            x = conv(rec.step, x, op=rec.op, in_op=rec.in_op,
+                     **{k: given[k] for k in rec.takes})
+            if rec.op == "conv2d_stats":
+                x, mean, std = x
+    return (x, mean, std) if stats_last else x
 
 
 class KernelSequential(nn.Sequential):

@@ -166,7 +166,7 @@ def test_conv2d_block_7x7_with_inception(cuda, pad_type):
 
 
 def test_plan_runs_7x7_steps(cuda):
-    """plan.run / run_conv_step route a pad-3 + 7x7 group to conv2d_k7 (one launch, cached
+    """plan.run / plan.conv route a pad-3 + 7x7 group to conv2d_k7 (one launch, cached
     packed weights); stats_last on a last 7x7 conv reduces the written output."""
     import torch.nn as nn
 
@@ -179,7 +179,7 @@ def test_plan_runs_7x7_steps(cuda):
         direct = ops.conv2d_k7(x, ops.pack_conv7_weight(conv.weight), conv.bias, 24,
                                pad=ops.PAD_ZERO, act=ops.ACT_RELU)
         assert torch.equal(plan.run(steps, x), direct)
-        assert torch.equal(plan.run_conv_step(steps[0], x), direct)
+        assert torch.equal(plan.conv(steps[0], x), direct)
         assert plan.packed_weight(conv) is plan.packed_weight(conv)
         y, mean, std = plan.run(steps, x, stats_last=True)
         m2, s2 = ops.calc_mean_std(direct)
@@ -189,7 +189,7 @@ def test_plan_runs_7x7_steps(cuda):
         x3 = torch.cat([x, x[:1]])
         assert torch.equal(plan.run(steps, x3[:1], x2=x3[1:])[:2], direct)
         with pytest.raises(NotImplementedError, match="7x7"):
-            plan.run_conv_step(steps[0], x, residual=direct)
+            plan.conv(steps[0], x, residual=direct)
 
 
 # ---- the network --------------------------------------------------------------------------

@@ -93,7 +93,7 @@ def bench_kernels(args):
         gp = torch.rand((n, c, hw + 6, hw + 6), device=dev, generator=g) - 0.5
 
         def conv7():
-            plan.run_conv7_step(step, x, out=out)
+            plan.conv(step, x, out=out)
 
         def wgrad7():
             A.conv_wgrad7(x, dy, conv, ops.PAD_REFLECT)

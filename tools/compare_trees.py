@@ -1,0 +1,208 @@
+"""Bit-for-bit comparison of two trees of this repository on the GPU.
+
+    python tools/compare_trees.py PARENT_ROOT NEW_ROOT [--cases a,b,..] [--work DIR] [--log FILE]
+
+PARENT_ROOT is a checkout of the parent commit (`git archive <commit> | tar -x -C DIR`) with its
+own built librpst.so, NEW_ROOT this tree. Every case (CASES) runs once per tree, the parent
+first, in a fresh child process started with subprocess under its own timeout, one GPU process
+at a time; the first non-zero exit stops the run. The child wraps rpst._lib.call to log each
+entry point's name and its non-pointer arguments (a pointer is logged as null / non-null),
+runs the case under ops.TRACE on seeded inputs and saves, with torch.save, the output tensors
+(test() outputs, or losses and every parameter gradient), the call log and TRACE.summary().
+A case passes when the tensors are torch.equal, the call logs are identical and the trace
+summaries have the same keys, launches, FLOPs and bytes. COVERAGE lists the entry points the
+parent's logs must reach over all cases. Reads nothing outside the two trees; exit status 0
+only if every case passes and the coverage is complete.
+"""
+from __future__ import annotations
+
+import argparse
+import copy
+import os
+import subprocess
+import sys
+
+COVERAGE = """rpst_conv2d rpst_conv2d_ws rpst_conv2d_pair rpst_conv2d_pool rpst_conv2d_masked
+rpst_conv2d_skip_adain rpst_conv2d_stats rpst_conv2d_stats_store rpst_conv2d_mix rpst_conv2d_gated
+rpst_conv7 rpst_maxpool2x2_ceil rpst_upsample_nearest2x rpst_conv_wgrad_pad rpst_conv7_wgrad
+rpst_conv1x1_wgrad rpst_reflect_pad_border_grad_masked rpst_reflect_pad_backward""".split()
+
+RP = {"rp_blocks": 5, "hidden_dim": 16, "content_weight": 1.0, "style_weight": 10.0,
+      "resume": False, "use_mask": False}
+MS = dict(RP, shuffle=False, shuffle_layers=1, sort=False, stylized_layers=5,
+          enc_stack_way="constant", inception_num=0, attention="none")
+LD = dict(MS, rp_blocks=3, stylized_layers=3, ld_layer_num=3, enc_stack_way="NONE")
+SA = {"content_weight": 1.0, "style_weight": 3.0, "l_identity1_weight": 50.0,
+      "l_identity2_weight": 1.0}
+SOURCE = {"use_mask": False, "content_weight": 1.0, "style_weight": 10.0}
+
+# case -> (model class, (config, arguments after the VGG..), what runs, environment);
+# what: "test", "test_mask" (label maps at feat x feat), "forward_nograd" or an rpst.autograd entry
+CASES = {
+    "adain.test": ("AdaINRPNet", (RP,), "test", {}),
+    "adain.test.unfused": ("AdaINRPNet", (RP,), "test", {"RPST_FUSE_ADAIN": "0"}),
+    "adain.forward_nograd": ("AdaINRPNet", (RP,), "forward_nograd", {}),
+    "wct.test": ("WCTRPNet", (RP,), "test", {"RPST_FUSE_WCT": "1"}),
+    "wct.test.unfused": ("WCTRPNet", (RP,), "test", {"RPST_FUSE_WCT": "0"}),
+    "samodel.test": ("SAModel", (SA, 0, 64), "test", {}),
+    "adaptive.test": ("AdaptiveSAModel", (dict(SA, ada_module="relu"), 0, 64), "test", {}),
+    "source.test": ("SourceNet", (SOURCE,), "test", {}),
+    # the one case added for COVERAGE: at these shapes only the separate pool pass (the
+    # RPST_POOL_EPILOGUE=0 route of plan.lower) reaches rpst_maxpool2x2_ceil
+    "source.test.pool_pass": ("SourceNet", (SOURCE,), "test", {"RPST_POOL_EPILOGUE": "0"}),
+    "source.test.mask": ("SourceNet", (dict(SOURCE, use_mask=True),), "test_mask:8", {}),
+    "multiscale.test": ("MultiScaleAdaINRPNet", (MS,), "test", {}),
+    "multiscale.test.deeper": ("MultiScaleAdaINRPNet",
+                               (dict(MS, enc_stack_way="deeper", inception_num=3),), "test", {}),
+    "multiscale.test.se": ("MultiScaleAdaINRPNet", (dict(MS, attention="se"),), "test", {}),
+    "multiscale.test.mask": ("MultiScaleAdaINRPNet", (dict(MS, use_mask=True),), "test_mask:64",
+                             {}),
+    "ld.test": ("LDMSAdaINRPNet", (LD,), "test", {}),
+    "ld.test.inception1": ("LDMSAdaINRPNet", (dict(LD, inception_num=1),), "test", {}),
+    "adain.losses": ("AdaINRPNet", (RP,), "adain_rp_losses", {}),
+    "wct.losses": ("WCTRPNet", (RP,), "wct_rp_losses", {}),
+    "samodel.losses": ("SAModel", (SA, 0, 64), "samodel_losses", {}),
+    "adaptive.losses": ("AdaptiveSAModel", (dict(SA, ada_module="relu"), 0, 64),
+                        "samodel_losses", {}),
+    "source.losses": ("SourceNet", (SOURCE,), "sourcenet_losses", {}),
+    "multiscale.losses": ("MultiScaleAdaINRPNet", (MS,), "multiscale_losses", {}),
+    "ld.losses": ("LDMSAdaINRPNet", (LD,), "ld_losses", {}),
+}
+SHAPE = (2, 3, 64, 64)
+
+
+def child(root: str, case: str, out_path: str) -> None:
+    """Run one case on the tree at `root` and save what the parent process compares."""
+    sys.path[:0] = [root, os.path.join(root, "rp-style-transfer_amd")]
+    import torch
+
+    import network as net
+    from rpst import _lib, autograd, ops, synth
+
+    assert os.path.realpath(_lib.LIB_PATH).startswith(os.path.realpath(root)), _lib.LIB_PATH
+    cls, args, what, _ = CASES[case]
+    dev = torch.device("cuda:0")
+    model = getattr(net, cls)(*copy.deepcopy(args[:1]), copy.deepcopy(net.vgg), *args[1:])
+    synth.synth_module_(model, 7)
+    model = model.to(dev)
+    c = torch.from_numpy(synth.image(1, SHAPE)).to(dev)
+    s = torch.from_numpy(synth.image(2, SHAPE)).to(dev)
+
+    calls, real_call = [], _lib.call
+
+    def logged_call(name, *a):
+        types = _lib.SIGNATURES[name][1]
+        calls.append((name, tuple(("null" if v is None else "ptr") if t is _lib._P else v
+                                  for v, t in zip(a, types))))
+        return real_call(name, *a)
+
+    _lib.call = logged_call
+    ops.TRACE = ops.Trace()
+    tensors = {}
+    if what == "test":
+        tensors["out"] = model.test(c, s)
+    elif what.startswith("test_mask"):
+        side = int(what.split(":")[1])
+        gen = torch.Generator().manual_seed(3)
+        segs = [torch.randint(0, 4, (SHAPE[0], side, side), generator=gen).to(torch.uint8).to(dev)
+                for _ in range(2)]
+        tensors["out"] = model.test(c, s, c_mask_path=segs[0], s_mask_path=segs[1])
+    elif what == "forward_nograd":
+        with torch.no_grad():
+            losses, _ = model(c, s)
+        tensors.update(losses)
+    else:
+        losses, total = getattr(autograd, what)(model, c, s)
+        total.backward()
+        tensors.update(losses)
+        tensors.update({"grad " + k: p.grad for k, p in model.named_parameters()
+                        if p.grad is not None})
+    torch.cuda.synchronize()
+    trace = {k: (v["launches"], v["flops"], v["bytes"]) for k, v in ops.TRACE.summary().items()}
+    torch.save({"tensors": {k: v.detach().cpu() for k, v in tensors.items()}, "calls": calls,
+                "trace": trace}, out_path)
+
+
+def compare(case: str, a: dict, b: dict, say) -> bool:
+    import torch
+    ta, tb = a["tensors"], b["tensors"]
+    equal = [k for k in ta if k in tb and ta[k].shape == tb[k].shape and torch.equal(ta[k], tb[k])]
+    grads = sum(k.startswith("grad ") for k in ta)
+    ok_t = list(ta) == list(tb) and len(equal) == len(ta)
+    say(f"{case}: {len(equal) - grads}/{len(ta) - grads} output / loss tensors, {grads} gradient "
+        f"tensors torch.equal: {'ALL EQUAL' if ok_t else 'DIFFERENT'}")
+    for k in ta:
+        if k not in equal:
+            say(f"   differs: {k}")
+    ok_c = a["calls"] == b["calls"]
+    say(f"   calls parent {len(a['calls'])}, new {len(b['calls'])}: "
+        f"{'SAME SEQUENCE AND ARGUMENTS' if ok_c else 'DIFFERENT'}")
+    if not ok_c:
+        for i, (x, y) in enumerate(zip(a["calls"], b["calls"])):
+            if x != y:
+                say(f"   first difference at call {i}: parent {x} | new {y}")
+                break
+    ok_s = a["trace"] == b["trace"]
+    say(f"   trace keys parent {len(a['trace'])}, new {len(b['trace'])}: "
+        f"{'SAME KEYS, LAUNCHES, FLOPS, BYTES' if ok_s else 'DIFFERENT'}")
+    if not ok_s:
+        for k in sorted(set(a["trace"]) | set(b["trace"])):
+            if a["trace"].get(k) != b["trace"].get(k):
+                say(f"   {k}: parent {a['trace'].get(k)} | new {b['trace'].get(k)}")
+    return ok_t and ok_c and ok_s
+
+
+def main() -> int:
+    ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
+    ap.add_argument("parent")
+    ap.add_argument("new")
+    ap.add_argument("--cases", default=",".join(CASES))
+    ap.add_argument("--work", default="compare_trees_out", help="directory of the saved runs")
+    ap.add_argument("--log", default=None, help="also append the report to this file")
+    ap.add_argument("--timeout", type=int, default=240, help="seconds per child process")
+    ap.add_argument("--child", nargs=2, metavar=("CASE", "OUT"), help=argparse.SUPPRESS)
+    a = ap.parse_args()
+    if a.child:
+        child(os.path.abspath(a.new), *a.child)
+        return 0
+    import torch
+    os.makedirs(a.work, exist_ok=True)
+    log = open(a.log, "a") if a.log else None
+
+    def say(line):
+        print(line, flush=True)
+        if log:
+            log.write(line + "\n")
+            log.flush()
+
+    say("# parent tree (git archive of the parent commit, its own librpst.so) vs this tree; one "
+        "fresh process per case per tree, parent first;")
+    say(f"# seeded inputs {SHAPE}; rpst_* calls logged with their non-pointer arguments by "
+        "wrapping rpst._lib.call; tensors compared with torch.equal")
+    say("# source.test.pool_pass (RPST_POOL_EPILOGUE=0) is the case added for coverage: no other "
+        "case reaches rpst_maxpool2x2_ceil at these shapes")
+    reached, ok = set(), True
+    for case in a.cases.split(","):
+        runs = []
+        for tag, root in (("parent", os.path.abspath(a.parent)), ("new", os.path.abspath(a.new))):
+            out = os.path.abspath(os.path.join(a.work, f"{case}.{tag}.pt"))
+            env = dict(os.environ, **CASES[case][3])
+            env.pop("RPST_LIB", None)  # each tree loads its own library
+            cmd = ["timeout", "-k", "10", str(a.timeout), sys.executable, os.path.abspath(__file__),
+                   root, root, "--child", case, out]
+            rc = subprocess.run(cmd, env=env, cwd=root).returncode
+            if rc != 0:
+                say(f"{case}: the {tag} tree's process exited with status {rc}: STOPPED")
+                return 1
+            runs.append(torch.load(out, weights_only=False))
+        reached |= {name for name, _ in runs[0]["calls"]}
+        ok &= compare(case, runs[0], runs[1], say)
+    missing = [e for e in COVERAGE if e not in reached]
+    say(f"# coverage of the parent's logs: {len(COVERAGE) - len(missing)}/{len(COVERAGE)} entry "
+        f"points reached{': MISSING ' + ' '.join(missing) if missing else ''}")
+    say(f"RESULT: {'PASS' if ok and not missing else 'FAIL'}")
+    return 0 if ok and not missing else 1
+
+
+if __name__ == "__main__":
+    sys.exit(main())
