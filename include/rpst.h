@@ -257,6 +257,36 @@ int rpst_conv7(const float* input, const float* input2, const float* packed_weig
                int pad_mode, int act, int out_channel_offset, int out_channels_total,
                rpst_stream_t stream);
 
+/* ---- LDMSAdaINRPNet4 (`network: ld_adain4`, adain_rp.py:711-819): coarse pyramid + concat ----
+ * Nearest rule of F.interpolate(x, size) in its default mode, per axis:
+ *   src = min((int)floorf(dst * ((float)in / (float)out)), in - 1), the product in fp32.
+ * rpst_nearest_index_table (host only): index[dst] for dst in [0, out), by the statement of the
+ *   rule the kernels share.
+ * rpst_resize_nearest: src (N,C,h,w) -> channels [channel_offset, channel_offset + C) of dst
+ *   (N,channels_total,H,W), h <= H, w <= W (the identity included); a pure gather, the other
+ *   channels are left alone.
+ * rpst_resized_mean_std: calc_mean_std (unbiased variance + eps, sqrt) of that resize without
+ *   writing it: each source pixel weighted by the number of destination pixels that read it;
+ *   mean / std_out (N,C). fp64 shifted sums in a fixed order: two calls give the same bits.
+ *   H*W = 1 as rpst_calc_mean_std. Workspace: rpst_resized_mean_std_workspace_size(h, w).
+ * rpst_ld4_fuse: a decoder block's input in one pass, out (N, Ca + 2*hidden, H, W):
+ *   channels [0, Ca): y (N,Ca,H,W) copied (Ca = 0 with y NULL: the first block);
+ *   [Ca, Ca + hidden): (v - mean_c) / std_c * std_s + mean_s of fine (N,hidden,H,W);
+ *   [Ca + hidden, Ca + 2*hidden): the same of coarse (N,hidden,h,w) gathered by the rule.
+ *   params_fine / params_coarse = [mean_c | mean_s | std_c | std_s], N*hidden floats each (as
+ *   RPST_IN_ADAIN). fine / coarse may point at a [content; style] batch of 2N images: the
+ *   first N are read. No atomics; plane bases need 4-byte alignment only. */
+int rpst_nearest_index_table(int in, int out, int* index);
+int rpst_resize_nearest(const float* src, float* dst, int N, int C, int h, int w, int H, int W,
+                        int channel_offset, int channels_total, rpst_stream_t stream);
+size_t rpst_resized_mean_std_workspace_size(int h, int w);
+int rpst_resized_mean_std(const float* src, float* mean, float* std_out, int N, int C, int h,
+                          int w, int H, int W, float eps, void* workspace,
+                          size_t workspace_bytes, rpst_stream_t stream);
+int rpst_ld4_fuse(const float* y, const float* fine, const float* coarse,
+                  const float* params_fine, const float* params_coarse, float* out, int N,
+                  int Ca, int hidden, int H, int W, int h, int w, rpst_stream_t stream);
+
 /* MultiScaleAdaINRPNet skip fusion (adain_rp.py:301): out = act(conv(pad(x + AdaIN(c))) +
  * bias), x = `stylized` and c = `content` both (N,Cin,H,W), AdaIN with the calc_mean_std
  * statistics `params` = [mean_c | mean_s | std_c | std_s] (4*N*Cin floats, as

@@ -381,17 +381,20 @@ class LDMSAdaINRPNet(MultiScaleAdaINRPNet):
         self.inception_num = config['inception_num']
         self.layer_num = config['ld_layer_num']
         self.stylized_layers = config['stylized_layers']
-        if self.stylized_layers < self.layer_num:
-            raise ValueError(
-                f"LDMSAdaINRPNet: stylized_layers ({self.stylized_layers}) < ld_layer_num "
-                f"({self.layer_num}) cannot be decoded (adain_rp.py:543-552 adds a list to a "
-                "tensor)")
+        self._check_stylized_layers()
         self.build_encoders()
         self.build_decoders()
         if self.config['resume']:
             checkpoint_path = self.config['checkpoint_path']
             self.begin = int(os.path.splitext(os.path.basename(checkpoint_path))[0])
             self.load_state_dict(torch.load(checkpoint_path, weights_only=True), strict=True)
+
+    def _check_stylized_layers(self):
+        if self.stylized_layers < self.layer_num:
+            raise ValueError(
+                f"LDMSAdaINRPNet: stylized_layers ({self.stylized_layers}) < ld_layer_num "
+                f"({self.layer_num}) cannot be decoded (adain_rp.py:543-552 adds a list to a "
+                "tensor)")
 
     def build_encoders(self):
         hidden_dim = self.hidden_dim
@@ -485,3 +488,137 @@ class LDMSAdaINRPNet(MultiScaleAdaINRPNet):
 
     def save(self, save_path, iterations=0):
         torch.save(self.state_dict(), save_path)
+
+
+class LDMSAdaINRPNet4(LDMSAdaINRPNet):
+    """Two-encoder multi-scale AdaIN-RP with a concat decoder (adain_rp.py:711-819; `network:
+    ld_adain4`). A fine chain of Conv2dBlocks (rp_enc{i}_small_revf, 3 -> h -> h ...) keeps the
+    image size; a coarse chain of Sequentials (rp_enc{i}_big_revf: conv1x1, two reflect 3x3 +
+    ReLU, ceil-mode 2x2 max-pool) halves it per level; the chains never mix. Level i is
+    cat([fine_i, nearest(coarse_i -> H x W)]), 2h channels. decode() starts from
+    rp_dec0(F(c[-1], s[-1])) and feeds every later block cat([stylized, F(c_i, s_i)]), F being
+    AdaIN or, with use_mask, the per-label AdaIN. stylized_layers sets the decoder widths only
+    (build_decoders); every 1 <= stylized_layers <= ld_layer_num decodes.
+
+    test() without masks runs both chains once over [content; style]; the fine blocks emit
+    their statistics from the last conv's epilogue, every coarse level's come from
+    ops.resized_mean_std (the small map weighted by its replication counts), and ops.ld4_fuse
+    writes each decoder block's whole input in one pass: no level tensor, no resized coarse
+    map, no AdaIN output and no concatenation is written on the way. encode_rp_intermediate(),
+    decode() and the masked route build the levels (fine half copied, coarse half written by
+    ops.resize_nearest) and concatenate in front of each block.
+
+    Deviations from the reference, where it cannot run: stylized_layers outside
+    [1, ld_layer_num] raises ValueError at construction (it builds decoder widths that decode()
+    cannot feed), `resume` as in LDMSAdaINRPNet. Inference only: forward() with autograd
+    enabled raises."""
+
+    def _check_stylized_layers(self):
+        if not 1 <= self.stylized_layers <= self.layer_num:
+            raise ValueError(
+                f"LDMSAdaINRPNet4: stylized_layers ({self.stylized_layers}) outside "
+                f"[1, ld_layer_num = {self.layer_num}] builds decoder widths that decode() cannot "
+                "feed (adain_rp.py:751-798)")
+
+    def build_encoders(self):
+        hidden_dim = self.hidden_dim
+        for i in range(self.layer_num):
+            in_dim = 3 if i == 0 else hidden_dim
+            setattr(self, f'rp_enc{i}_small_revf',
+                    Conv2dBlock(in_dim, hidden_dim, 3, 1, 1, inception_num=self.inception_num))
+            setattr(self, f'rp_enc{i}_big_revf', nn.Sequential(
+                nn.Conv2d(in_dim, hidden_dim, (1, 1)),
+                nn.ReflectionPad2d((1, 1, 1, 1)), nn.Conv2d(hidden_dim, hidden_dim, (3, 3)),
+                nn.ReLU(),
+                nn.ReflectionPad2d((1, 1, 1, 1)), nn.Conv2d(hidden_dim, hidden_dim, (3, 3)),
+                nn.ReLU(),
+                nn.MaxPool2d((2, 2), (2, 2), (0, 0), ceil_mode=True)))
+        self.encoder_out_dim = hidden_dim
+
+    def build_decoders(self):
+        # block k reads what block k - 1 writes plus a level (2h); blocks before
+        # stylized_layers - 1 write 2h channels, the later ones h, the last one the image
+        h, prev = self.encoder_out_dim, 0
+        for k in range(self.layer_num):
+            out = 3 if k == self.layer_num - 1 else (2 * h if k < self.stylized_layers - 1 else h)
+            setattr(self, f'rp_dec{k}',
+                    Conv2dBlock(prev + 2 * h, out, 3, 1, 1, inception_num=self.inception_num))
+            prev = out
+
+    def _has_attention(self):
+        return False
+
+    def _chains(self, x, x2=None, stats=False):
+        """Both encoder chains over x (or the batch [x; x2], read in place) -> per level
+        (fine, coarse), or with stats (fine, mean, std, coarse): calc_mean_std of fine from its
+        last conv's epilogue."""
+        fine, coarse, f2, c2, out = x, x, x2, x2, []
+        for i in range(self.layer_num):
+            fine = plan.run(plan.of(self._enc(i, 'small')), fine, x2=f2, stats_last=stats)
+            coarse = plan.run(plan.of(self._enc(i, 'big')), coarse, x2=c2)
+            out.append((*fine, coarse) if stats else (fine, coarse))
+            if stats:
+                fine = fine[0]
+            f2 = c2 = None
+        return out
+
+    def _levels(self, x, x2=None):
+        """cat([fine_i, interpolate(coarse_i, size)], dim=1) per level without the cat: the fine
+        half is one strided copy, the coarse half is written by the resize kernel."""
+        levels = []
+        for fine, coarse in self._chains(x, x2):
+            b, c, h, w = fine.shape
+            level = torch.empty((b, 2 * c, h, w), device=fine.device, dtype=torch.float32)
+            level[:, :c].copy_(fine)
+            levels.append(ops.resize_nearest(coarse, (h, w), out=level, out_channel_offset=c))
+        return levels
+
+    def encode_rp_intermediate(self, input):
+        return self._levels(input)
+
+    def _encode_pair(self, content, style, stats=False):
+        assert not stats
+        return self._levels(content, style)
+
+    def _decode_fused(self, content, style, n):
+        size = content.shape[2:]
+        y = None
+        for k, (fine, fm, fs, coarse) in enumerate(self._chains(content, style, stats=True)[::-1]):
+            cm, cs = ops.resized_mean_std(coarse, size)
+            y = ops.ld4_fuse(y, fine, coarse, ops.adain_params(fm[:n], fs[:n], fm[n:], fs[n:]),
+                             ops.adain_params(cm[:n], cs[:n], cm[n:], cs[n:]), n=n)
+            y = plan.run(plan.of(self._dec(k)), y)
+        return y
+
+    def decode(self, content_feats, style_feats, use_mask=False, c_mask_path=None, s_mask_path=None):
+        """adain_rp.py:780-799, op by op: AdaIN (or the per-label AdaIN) of every level, then
+        each block on cat([stylized, that])."""
+        self._kernel_path_check()
+        if use_mask:
+            # all levels share H x W: decode the masks and plan the labels once
+            n, dev = content_feats[-1].shape[0], content_feats[-1].device
+            c_seg = segment_maps(c_mask_path, n, content_feats[-1].shape[2:], dev)
+            s_seg = segment_maps(s_mask_path, n, style_feats[-1].shape[2:], dev)
+            seg_plan = ops.segment_plan(c_seg, s_seg)
+
+            def fuse(c, s):
+                return masked_adain_batch(c, s, c_seg, s_seg, plan=seg_plan)[0]
+        else:
+            fuse = AdaIN
+        stylized = self._dec(0)(fuse(content_feats[-1], style_feats[-1]))
+        pairs = list(zip(content_feats[:-1], style_feats[:-1]))[::-1]
+        for i, (content_feat, style_feat) in enumerate(pairs):
+            stylized = self._dec(i + 1)(torch.cat([stylized, fuse(content_feat, style_feat)],
+                                                  dim=1))
+        return stylized
+
+    def forward(self, content, style, alpha=1.0):
+        """The loss dict of adain_rp.py:322-345 under no_grad, op by op through
+        encode_rp_intermediate / decode; with autograd enabled and trainable parameters it
+        raises: ld_adain4 training is not built."""
+        self._kernel_path_check()
+        if torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters()):
+            raise NotImplementedError(
+                "LDMSAdaINRPNet4: ld_adain4 training is not built (inference only: test / "
+                "decode / forward under torch.no_grad())")
+        return super().forward(content, style, alpha)

@@ -62,6 +62,11 @@ SIGNATURES = {
     "rpst_conv7_packed_size": (_SZ, [_I, _I]),
     "rpst_conv7_pack": (_I, [_P, _P, _I, _I, _P]),
     "rpst_conv7": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P]),
+    "rpst_nearest_index_table": (_I, [_I, _I, _P]),
+    "rpst_resize_nearest": (_I, [_P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _P]),
+    "rpst_resized_mean_std_workspace_size": (_SZ, [_I, _I]),
+    "rpst_resized_mean_std": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _I, _F, _P, _SZ, _P]),
+    "rpst_ld4_fuse": (_I, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P]),
     "rpst_maxpool2x2_ceil": (_I, [_P, _P, _I, _I, _I, _I, _P]),
     "rpst_upsample_nearest2x": (_I, [_P, _P, _I, _I, _I, _I, _P]),
     "rpst_add_upsample_nearest2x": (_I, [_P, _P, _P, _I, _I, _I, _I, _P]),

@@ -664,6 +664,110 @@ def adain_params(mean_c, std_c, mean_s, std_s) -> torch.Tensor:
                       std_s.reshape(-1)])
 
 
+# ---- LDMSAdaINRPNet4: nearest resize of the coarse pyramid, its statistics, the concat ----
+def nearest_index_table(size_in: int, size_out: int) -> torch.Tensor:
+    """F.interpolate's default-mode source index of every destination index along one axis:
+    int32 (size_out,) on the host, min(floor(dst * (float32(in) / float32(out))), in - 1) as
+    the kernels compute it (rpst_nearest_index_table: the same statement of the rule)."""
+    import ctypes
+    size_in, size_out = int(size_in), int(size_out)
+    buf = (ctypes.c_int * max(size_out, 1))()
+    _lib.call("rpst_nearest_index_table", size_in, size_out, ctypes.addressof(buf))
+    return torch.tensor(list(buf[:size_out]), dtype=torch.int32)
+
+
+def nearest_counts(size_in: int, size_out: int) -> torch.Tensor:
+    """Replication count of every source index under nearest_index_table: int64 (size_in,)."""
+    return torch.bincount(nearest_index_table(size_in, size_out).long(), minlength=int(size_in))
+
+
+def _resize_args(src: torch.Tensor, size):
+    assert src.dim() == 4
+    H, W = (int(v) for v in size)
+    n, c, h, w = src.shape
+    if h > H or w > W:
+        raise ValueError(f"rpst: nearest resize enlarges only ({h}x{w} -> {H}x{W})")
+    return n, c, h, w, H, W
+
+
+def resize_nearest(src: torch.Tensor, size, out: Optional[torch.Tensor] = None,
+                   out_channel_offset: int = 0) -> torch.Tensor:
+    """F.interpolate(src, size) (default mode 'nearest', adain_rp.py:813-815) written to channels
+    [out_channel_offset, out_channel_offset + C) of `out` (a contiguous (N, C_total, H, W)
+    tensor whose other channels are left alone; default: a new (N, C, H, W) tensor). A pure
+    gather: bit-identical to torch's. Returns `out`."""
+    _check(src, out)
+    n, c, h, w, H, W = _resize_args(src, size)
+    src = _c(src)
+    if out is None and out_channel_offset:
+        raise ValueError("rpst: resize_nearest with a channel offset needs the tensor to write "
+                         "into")
+    out = _conv_out(src, (n, c if out is None else None, H, W), out)
+    with _traced(f"resize_nearest C{c} {h}x{w}->{H}x{W} N{n}", 0.0,
+                 4.0 * n * c * (h * w + H * W)):
+        _lib.call("rpst_resize_nearest", src.data_ptr(), out.data_ptr(), n, c, h, w, H, W,
+                  int(out_channel_offset), out.shape[1], _stream(src))
+    return out
+
+
+def resized_mean_std(src: torch.Tensor, size,
+                     eps: float = 1e-5) -> Tuple[torch.Tensor, torch.Tensor]:
+    """calc_mean_std(F.interpolate(src, size)) from src alone (the resize is not written): every
+    source pixel weighted by its replication count -> mean, std of shape (N, C, 1, 1)."""
+    _check(src)
+    n, c, h, w, H, W = _resize_args(src, size)
+    src = _c(src)
+    mean = torch.empty((n, c, 1, 1), device=src.device, dtype=torch.float32)
+    std = torch.empty_like(mean)
+    nbytes = _lib.load().rpst_resized_mean_std_workspace_size(h, w)
+    ws = torch.empty(nbytes, device=src.device, dtype=torch.uint8)
+    with _traced(f"resized_mean_std C{c} {h}x{w}->{H}x{W} N{n}", 0.0, 4.0 * n * c * h * w):
+        _lib.call("rpst_resized_mean_std", src.data_ptr(), mean.data_ptr(), std.data_ptr(), n, c,
+                  h, w, H, W, eps, ws.data_ptr(), nbytes, _stream(src))
+    return mean, std
+
+
+def ld4_fuse(y: Optional[torch.Tensor], fine: torch.Tensor, coarse: torch.Tensor,
+             params_fine: torch.Tensor, params_coarse: torch.Tensor, n: Optional[int] = None,
+             out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """A decoder block's input of LDMSAdaINRPNet4.decode (adain_rp.py:786-798) in one pass:
+    cat([y, AdaIN(cat([fine, F.interpolate(coarse, (H, W))]), style)], dim=1) of shape
+    (n, Ca + 2h, H, W). y (n, Ca, H, W) or None (the first block); fine (>= n, h, H, W) and
+    coarse (>= n, h, hc, wc) are read at their first n images, so a [content; style] batch is
+    passed whole (n defaults to y's batch, else fine's); params_fine / params_coarse =
+    adain_params(mean_c, std_c, mean_s, std_s) of the two halves, n * h each."""
+    assert fine.dim() == 4 and coarse.dim() == 4
+    _check(y, fine, coarse, params_fine, params_coarse, out)
+    fine, coarse = _c(fine), _c(coarse)
+    params_fine, params_coarse = _c(params_fine), _c(params_coarse)
+    if n is None:
+        n = fine.shape[0] if y is None else y.shape[0]
+    n = int(n)
+    hd, H, W = fine.shape[1:]
+    hc, wc = coarse.shape[2:]
+    ca = 0
+    if y is not None:
+        y = _c(y)
+        ca = y.shape[1]
+        if y.dim() != 4 or (y.shape[0], y.shape[2], y.shape[3]) != (n, H, W) or ca == 0:
+            raise ValueError(f"rpst: ld4_fuse's y must be ({n}, Ca > 0, {H}, {W}), got "
+                             f"{tuple(y.shape)}")
+    if n < 1 or fine.shape[0] < n or coarse.shape[0] < n or coarse.shape[1] != hd:
+        raise ValueError("rpst: ld4_fuse needs fine (>= n, h, H, W) and coarse (>= n, h, hc, wc), "
+                         f"got {tuple(fine.shape)} and {tuple(coarse.shape)} for n = {n}")
+    if hc > H or wc > W:
+        raise ValueError(f"rpst: nearest resize enlarges only ({hc}x{wc} -> {H}x{W})")
+    if params_fine.numel() != 4 * n * hd or params_coarse.numel() != 4 * n * hd:
+        raise ValueError("rpst: ld4_fuse params = [mean_c | mean_s | std_c | std_s], n * h each")
+    out = _conv_out(fine, (n, ca + 2 * hd, H, W), out)
+    with _traced(f"ld4_fuse {ca}+2x{hd} {hc}x{wc}->{H}x{W} N{n}", 0.0,
+                 4.0 * n * ((2 * ca + 3 * hd) * H * W + hd * hc * wc)):
+        _lib.call("rpst_ld4_fuse", _ptr(y), fine.data_ptr(), coarse.data_ptr(),
+                  params_fine.data_ptr(), params_coarse.data_ptr(), out.data_ptr(), n, ca, hd, H,
+                  W, hc, wc, _stream(fine))
+    return out
+
+
 def maxpool2x2_ceil(x: torch.Tensor) -> torch.Tensor:
     _check(x)
     x = _c(x)

@@ -9,13 +9,13 @@ stylises every pair of `test_dir` into `<output>/test/test_output/{cn}-{sn}.png`
 `{cn}-{sn}-cat.png` through rpst.imageio.Pipeline (decode / PNG encode on host threads,
 ToTensor and save_image's pixel path on the GPU). With `use_mask: True` and
 `test_dataset: photoreal` the pipeline also decodes each pair's two segmentation masks and
-`src` / `multi_adain` / `ld_adain` stylise per label.
+`src` / `multi_adain` / `ld_adain` / `ld_adain4` stylise per label.
 
 Differences from test.py, by design: no TensorBoard writer, no per-step cv2 import, the
 test.py:135 `iterations=i` NameError is not reproduced (iterations=0 is passed), and
 `--synthetic-weights SEED` replaces the checkpoints with rpst.synth weights (offline
-runs, tests). Networks outside the hot path (sel_multi_adain, ld_adain2 and later, mrf, spade) and
-the 'fmt' dataset (single images, which test.py's loop cannot unpack) raise.
+runs, tests). Networks outside the hot path (sel_multi_adain, ld_adain2, ld_adain3, ld_adain5,
+mrf, spade) and the 'fmt' dataset (single images, which test.py's loop cannot unpack) raise.
 """
 from __future__ import annotations
 
@@ -34,11 +34,11 @@ logging.basicConfig(level=logging.INFO,
                     format="%(asctime)s - %(name)s - %(levelname)s - %(message)s")
 logger = logging.getLogger("stylize")
 
-OUT_OF_SCOPE = ("sel_multi_adain", "ld_adain2", "ld_adain3", "ld_adain4", "ld_adain5", "mrf",
-                "spade")
+OUT_OF_SCOPE = ("sel_multi_adain", "ld_adain2", "ld_adain3", "ld_adain5", "mrf", "spade")
 
 
-MASKED_NETWORKS = ("src", "multi_adain", "ld_adain")  # networks whose test() honours use_mask
+# networks whose test() honours use_mask
+MASKED_NETWORKS = ("src", "multi_adain", "ld_adain", "ld_adain4")
 
 
 def mask_size(kind, img_size):
@@ -70,6 +70,8 @@ def build_network(opt, synthetic_seed=None):
         m = net.MultiScaleAdaINRPNet(opt, vgg_relu4_1)
     elif kind == "ld_adain":  # test.py:102-103
         m = net.LDMSAdaINRPNet(opt, vgg_relu4_1)
+    elif kind == "ld_adain4":  # train.py:114-115 (test.py stops at ld_adain2)
+        m = net.LDMSAdaINRPNet4(opt, vgg_relu4_1)
     elif kind == "wct":
         m = net.WCTRPNet(opt, vgg_relu4_1)
     elif kind == "dynamic_sanet":
