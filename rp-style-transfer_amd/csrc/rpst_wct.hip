@@ -20,13 +20,13 @@
 #include "rpst_common.h"
 #include "rpst_wct.h"
 
+#include <climits>
 #include <cstdlib>
+#include <type_traits>
 
 namespace rpst {
 
-#ifndef RPST_WCT_BK
-#define RPST_WCT_BK 32  // k depth of a staged fp64 GEMM tile (16: wct_params 17.77 vs 16.86 ms)
-#endif
+constexpr int kWctBK = 32;  // k depth of a staged fp64 GEMM tile (16: wct_params 17.77 vs 16.86 ms)
 
 // plain fp64 / centered fp64 / centered fp32 / plain fp32
 enum { SRC_F64 = 0, SRC_F64C = 1, SRC_F32C = 2, SRC_F32 = 3 };
@@ -42,19 +42,11 @@ struct G64Args {
   const double* amean;  // per-m mean (A centering), batch stride sMean
   const double* bmean;  // per-k (B_KN) or per-n (B_NK) mean, batch stride sMean
   const double* bias;   // per-m bias (OUT_*_BIAS), batch stride sMean
-  const double* avec;   // optional per-batch alpha multiplier
-  double alpha, beta_diag;
   int M, N, K, lda, ldb, ldc;
   int64_t sA, sB, sC, sMean;
   int ksplit;           // split-K factor (OUT_PARTIAL)
   int sym;              // only upper-triangular tiles (blockIdx.x enumerates them)
   int tiles_n;
-  // dual launch: batch entries z >= dual run C2 = A2 B2 (same shape / strides; ksplit 1),
-  // so two independent products share one launch (0 = off)
-  const void* A2;
-  const void* B2;
-  void* C2;
-  int dual;
 };
 
 typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
@@ -108,7 +100,7 @@ __device__ __forceinline__ void load_run(double (&v)[N], __amdgpu_buffer_rsrc_t 
 
 template <int BT, int SRCA, int SRCB, int BLAY, int OUT, bool VEC>
 __global__ __launch_bounds__(256) void gemm_f64_kernel(G64Args g) {
-  constexpr int BK = RPST_WCT_BK, LD = BT + 16, WT = BT / 2, MT = WT / 16;
+  constexpr int BK = kWctBK, LD = BT + 16, WT = BT / 2, MT = WT / 16;
   constexpr int EPT = BT * BK / 256;  // elements staged per thread per operand
   __shared__ double As[BK * LD];
   __shared__ double Bs[BK * LD];
@@ -128,17 +120,8 @@ __global__ __launch_bounds__(256) void gemm_f64_kernel(G64Args g) {
     tj = blockIdx.x;
   }
   const int z = blockIdx.z;
-  int b = z / g.ksplit;
+  const int b = z / g.ksplit;
   const int split = z - b * g.ksplit;
-  const void* gA = g.A;
-  const void* gB = g.B;
-  void* gC = g.C;
-  if (g.dual && b >= g.dual) {
-    b -= g.dual;
-    gA = g.A2;
-    gB = g.B2;
-    gC = g.C2;
-  }
   const int m0 = ti * BT, n0 = tj * BT;
   // split-K ranges are whole BK tiles
   const int kper = ((g.K + g.ksplit - 1) / g.ksplit + BK - 1) / BK * BK;
@@ -146,8 +129,8 @@ __global__ __launch_bounds__(256) void gemm_f64_kernel(G64Args g) {
   const int kend = min(g.K, kbeg + kper);
 
   constexpr unsigned ESA = src_f32(SRCA) ? 4u : 8u, ESB = src_f32(SRCB) ? 4u : 8u;
-  const char* Ab = static_cast<const char*>(gA) + (int64_t)b * g.sA * ESA;
-  const char* Bb = static_cast<const char*>(gB) + (int64_t)b * g.sB * ESB;
+  const char* Ab = static_cast<const char*>(g.A) + (int64_t)b * g.sA * ESA;
+  const char* Bb = static_cast<const char*>(g.B) + (int64_t)b * g.sB * ESB;
   const __amdgpu_buffer_rsrc_t ra = rsrc(Ab, (unsigned)g.M * g.lda * ESA);
   const __amdgpu_buffer_rsrc_t rb =
       rsrc(Bb, BLAY == B_NK ? (unsigned)g.N * g.ldb * ESB : (unsigned)g.K * g.ldb * ESB);
@@ -239,7 +222,6 @@ __global__ __launch_bounds__(256) void gemm_f64_kernel(G64Args g) {
   }
 
   // epilogue: D col = lane&15, row = (lane>>4) + 4r
-  const double alpha = g.alpha * (g.avec ? g.avec[b] : 1.0);
 #pragma unroll
   for (int i = 0; i < MT; ++i) {
 #pragma unroll
@@ -253,14 +235,11 @@ __global__ __launch_bounds__(256) void gemm_f64_kernel(G64Args g) {
         if (n >= g.N) continue;
         const double v = acc[i][jn][r];
         if (OUT == OUT_PARTIAL) {
-          static_cast<double*>(gC)[(int64_t)z * g.sC + (int64_t)m * g.ldc + n] = v;
-        } else if (OUT == OUT_F64) {
-          static_cast<double*>(gC)[b * g.sC + (int64_t)m * g.ldc + n] =
-              alpha * v + (m == n ? g.beta_diag : 0.0);
+          static_cast<double*>(g.C)[(int64_t)z * g.sC + (int64_t)m * g.ldc + n] = v;
         } else if (OUT == OUT_F32_BIAS) {
-          static_cast<float*>(gC)[b * g.sC + (int64_t)m * g.ldc + n] = (float)(v + bias);
-        } else {
-          static_cast<double*>(gC)[b * g.sC + (int64_t)m * g.ldc + n] = v + bias;
+          static_cast<float*>(g.C)[b * g.sC + (int64_t)m * g.ldc + n] = (float)(v + bias);
+        } else {  // OUT_F64 (bias 0.0: a -0.0 product is stored as +0.0) and OUT_F64_BIAS
+          static_cast<double*>(g.C)[b * g.sC + (int64_t)m * g.ldc + n] = v + bias;
         }
       }
     }
@@ -272,20 +251,26 @@ __global__ __launch_bounds__(256) void gemm_f64_kernel(G64Args g) {
 // features, so it runs on the fp32 MFMA (2x the fp64 rate). Centering in fp32 and fp32
 // accumulation over C = 256 terms: ~1.5e-7 rel-L2 vs the fp64 product on encoder features
 // with |T| up to 100 (the fp32 output itself rounds at 6e-8).
-__global__ __launch_bounds__(256) void wct_f32_prep_kernel(const double* __restrict__ T,
-                                                           const double* __restrict__ mu,
-                                                           float* __restrict__ Tf,
-                                                           float* __restrict__ muf, int64_t nT,
-                                                           int64_t nmu, int C) {
-  // Tf = T^T per image ([k][m], output channels contiguous) so both GEMM operands stage
-  // with 16-B loads and 16-B LDS stores
+// The operands of wct_transform_f32 for out = T (x - muc) + mus: Tf = T^T per image ([k][m],
+// output channels contiguous, so both GEMM operands stage with 16-B loads and 16-B LDS
+// stores), muc and mus (n x C each) narrowed; a null muc is written as zeros (z = T x + c)
+__global__ __launch_bounds__(256) void wct_prep_kernel(const double* __restrict__ T,
+                                                       const double* __restrict__ muc,
+                                                       const double* __restrict__ mus,
+                                                       float* __restrict__ Tf,
+                                                       float* __restrict__ mucf,
+                                                       float* __restrict__ musf, int64_t nT,
+                                                       int64_t nmu, int C) {
   const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
   if (i < nT) {
     const int64_t cc = (int64_t)C * C, b = i / cc, r = i - b * cc;
     const int m = (int)(r / C), k = (int)(r - (int64_t)m * C);
     Tf[b * cc + (int64_t)k * C + m] = (float)T[i];
   }
-  if (i < nmu) muf[i] = (float)mu[i];
+  if (i < nmu) {
+    mucf[i] = muc ? (float)muc[i] : 0.f;
+    musf[i] = (float)mus[i];
+  }
 }
 
 // Block tile 128 (m = output channel) x 128 (n = pixel), K = C in steps of 32, 4 waves of
@@ -399,33 +384,25 @@ __global__ __launch_bounds__(256, 2) void wct_transform_f32_kernel(
     }
 }
 
-// out = Tf^T-staged product: out[b] = T[b] (X[b] - muc[b]) + mus[b] for fp32 features
-static int wct_transform_f32(const float* Tf, const float* X, const float* muc, const float* mus,
-                             float* out, int n, int C, int64_t HW, hipStream_t st) {
+// out[b] = T[b] (X[b] - muc[b]) + mus[b] for fp32 features on the fp32 MFMA (muc null:
+// T X + mus). T, muc, mus: fp64, narrowed into `scratch` (wct_apply_scratch_floats(n, C)).
+static int wct_transform_f32(const double* T, const double* muc, const double* mus,
+                             const float* X, float* out, int n, int C, int64_t HW,
+                             float* scratch, hipStream_t st) {
+  float* Tf = scratch;
+  float* mucf = Tf + (size_t)n * C * C;
+  float* musf = mucf + (size_t)n * C;
+  const int64_t nT = (int64_t)n * C * C, nmu = (int64_t)n * C;
+  wct_prep_kernel<<<(unsigned)((nT + 255) / 256), 256, 0, st>>>(T, muc, mus, Tf, mucf, musf, nT,
+                                                                nmu, C);
+  if (int e = launch_status("wct_prep_kernel")) return e;
   dim3 grid((unsigned)((HW + 127) / 128), (C + 127) / 128, n);
   const bool vec = (HW % 4 == 0) && (C % 4 == 0) && (reinterpret_cast<uintptr_t>(X) & 15) == 0;
   if (vec)
-    wct_transform_f32_kernel<true><<<grid, 256, 0, st>>>(Tf, X, muc, mus, out, C, (int)HW);
+    wct_transform_f32_kernel<true><<<grid, 256, 0, st>>>(Tf, X, mucf, musf, out, C, (int)HW);
   else
-    wct_transform_f32_kernel<false><<<grid, 256, 0, st>>>(Tf, X, muc, mus, out, C, (int)HW);
+    wct_transform_f32_kernel<false><<<grid, 256, 0, st>>>(Tf, X, mucf, musf, out, C, (int)HW);
   return launch_status("wct_transform_f32_kernel");
-}
-
-// Tf[b][k][m] = T[b][m][k] (fp32), muc = 0, mus = c (fp32): the operands of wct_transform_f32
-// for z = T x + c
-__global__ void wct_apply_prep_kernel(const double* __restrict__ T, const double* __restrict__ c,
-                                      float* __restrict__ Tf, float* __restrict__ muc,
-                                      float* __restrict__ mus, int64_t nT, int64_t nc, int C) {
-  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  if (i < nT) {
-    const int64_t cc = (int64_t)C * C, b = i / cc, r = i - b * cc;
-    const int m = (int)(r / C), k = (int)(r - (int64_t)m * C);
-    Tf[b * cc + (int64_t)k * C + m] = (float)T[i];
-  }
-  if (i < nc) {
-    muc[i] = 0.f;
-    mus[i] = (float)c[i];
-  }
 }
 
 size_t wct_apply_scratch_floats(int n, int C) {
@@ -434,14 +411,7 @@ size_t wct_apply_scratch_floats(int n, int C) {
 
 int wct_apply_f32(const double* T, const double* c, const float* x, float* z, int n, int C,
                   int64_t HW, float* scratch, hipStream_t st) {
-  float* Tf = scratch;
-  float* muc = Tf + (size_t)n * C * C;
-  float* mus = muc + (size_t)n * C;
-  const int64_t nT = (int64_t)n * C * C, nc = (int64_t)n * C;
-  wct_apply_prep_kernel<<<(unsigned)((std::max(nT, nc) + 255) / 256), 256, 0, st>>>(
-      T, c, Tf, muc, mus, nT, nc, C);
-  if (int e = launch_status("wct_apply_prep_kernel")) return e;
-  return wct_transform_f32(Tf, x, muc, mus, z, n, C, HW, st);
+  return wct_transform_f32(T, nullptr, c, x, z, n, C, HW, scratch, st);
 }
 
 // Row means in fp64 of `rows` rows of length L (one workgroup per row).
@@ -506,7 +476,6 @@ static void gemm64(const G64Args& g, dim3 grid, hipStream_t st) {
   auto al = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; };
   bool vec = al(g.A) && al(g.B) && g.lda % va == 0 && g.ldb % vb == 0 && g.K % va == 0 &&
              g.sA % va == 0 && g.sB % vb == 0;
-  if (g.dual) vec = vec && al(g.A2) && al(g.B2);
   if (BLAY == B_NK) vec = vec && g.K % vb == 0;
   else vec = vec && g.N % vb == 0;
   if (vec)
@@ -515,7 +484,26 @@ static void gemm64(const G64Args& g, dim3 grid, hipStream_t st) {
     gemm_f64_kernel<BT, SRCA, SRCB, BLAY, OUT, false><<<grid, 256, 0, st>>>(g);
 }
 
-static int env_int(const char* name, int dflt);
+// C[b] (M x N) = A[b] (M x K) B[b] (K x N), every operand dense in its batch (stride rows x
+// ld), one K split
+static G64Args g64(const void* A, const void* B, void* C, int M, int N, int K, int lda, int ldb,
+                   int ldc) {
+  G64Args g{};
+  g.A = A;
+  g.B = B;
+  g.C = C;
+  g.M = M;
+  g.N = N;
+  g.K = K;
+  g.lda = lda;
+  g.ldb = ldb;
+  g.ldc = ldc;
+  g.sA = (int64_t)M * lda;
+  g.sB = (int64_t)K * ldb;
+  g.sC = (int64_t)M * ldc;
+  g.ksplit = 1;
+  return g;
+}
 
 static int env_int(const char* name, int dflt) {
   const char* e = getenv(name);
@@ -524,15 +512,15 @@ static int env_int(const char* name, int dflt) {
 
 // Split-K of the covariance SYRK: a function of the per-image K only, so an image's
 // summation order (and its bits) never depend on how many images share the launch (the
-// per-image multi-GPU split relies on that). K >= kmin per split, at most 128 splits:
+// per-image multi-GPU split relies on that). K >= 4096 per split, at most 128 splits:
 // at 512^2, 64 splits of 4096 (profiles/r01_wct_blocks.log: ~8192 workgroups at n = 16,
 // 27.6 ms vs 28.9 at 4096 for the whole fuse).
 static int pick_ksplit(int64_t K) {
-  const int64_t kmin = env_int("RPST_WCT_KMIN", 4096);
-  const int64_t s = K / kmin;
+  const int64_t s = K / 4096;
   return s < 1 ? 1 : (s > 128 ? 128 : (int)s);
 }
 
+// The workspace of every entry point: a function of (n, C, HW, feature type) alone.
 struct WctLayout {
   int n, C, ksplit, BT, tiles, symtiles;
   bool v2;  // fp32 features with C <= 256: cov_syrk_kernel (rpst_wct_mat.hip)
@@ -542,57 +530,115 @@ struct WctLayout {
   size_t total;
 };
 
-// src_f32: the features are fp32 (the v2 covariance applies for C <= 256)
-static WctLayout wct_layout(int n, int C, int64_t HW, bool src_f32) {
+static WctLayout wct_layout(int n, int C, int64_t HW, bool f32) {
   WctLayout L{};
   L.n = n;
   L.C = C;
   L.HW = HW;
-  L.v2 = src_f32 && cov_v2_supported(C) && env_int("RPST_WCT_COV_V2", 1) != 0;
-  L.BT = (C >= 128 && env_int("RPST_WCT_COV_BT", 128) == 128) ? 128 : 64;
+  L.v2 = f32 && cov_v2_supported(C);
+  L.BT = C >= 128 ? 128 : 64;
   L.tiles = (C + L.BT - 1) / L.BT;
   L.symtiles = L.tiles * (L.tiles + 1) / 2;
   L.ksplit = pick_ksplit(HW);
   const size_t cc = (size_t)C * C * n;
   size_t o = 0;
   L.mu_c = o; o += (size_t)n * C;
-  L.mu_s = o; o += (size_t)n * C;
+  L.mu_s = o; o += (size_t)n * C;  // mu_s follows mu_c: one (2n x C) array
   L.mu32 = o; o += ((size_t)2 * n * C + 1) / 2;  // fp32 centring means (v2 without `means`)
   L.part = o; o += L.v2 ? cov_v2_work_doubles(n, C, HW) : (size_t)2 * n * L.ksplit * C * C;
   L.cc = o; o += cc;
   L.cs = o; o += cc;
   L.tm = o; o += cc;
   L.off = o; o += (size_t)n * C;
-  L.tf = o; o += cc / 2 + (size_t)n * C + 2;  // fp32 transform operands (wct_run)
+  L.tf = o; o += cc / 2 + (size_t)n * C + 2;  // fp32 transform operands (wct_transform)
   L.mf = o; o += matfun_wct_work_doubles(n, C);
   // whiten_and_color(method='original') (fp64 features, n = 1): (Cc + 1e-4 I)^(-1/2) and
   // (Cs + 1e-4 I)^(1/2) in SVD form, then the matrix-power workspace
   L.orig = o;
-  if (!src_f32) o += (size_t)2 * n * C * C + matfun_power_work_doubles(C, n);
+  if (!f32) o += (size_t)2 * n * C * C + matfun_power_work_doubles(C, n);
   L.total = o;
   return L;
 }
 
-// means (fp32, e.g. from the encoder's statistics epilogue: content rows then style rows,
-// 2n x C) widened to fp64
-__global__ void widen_means_kernel(const float* __restrict__ m, double* __restrict__ out,
-                                   int64_t count) {
+// fp32 <-> fp64 of the centring means (2n x C, content rows then style rows): the caller's
+// fp32 means (e.g. from the encoder's statistics epilogue) widened, or the fp64 row means
+// narrowed for cov_v2
+template <typename S, typename D>
+__global__ void convert_kernel(const S* __restrict__ in, D* __restrict__ out, int64_t count) {
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < count) out[i] = (double)m[i];
+  if (i < count) out[i] = (D)in[i];
 }
 
-__global__ void narrow_means_kernel(const double* __restrict__ m, float* __restrict__ out,
-                                    int64_t count) {
-  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < count) out[i] = (float)m[i];
+template <typename S, typename D>
+static int convert(const S* in, D* out, int64_t count, hipStream_t st) {
+  convert_kernel<<<(unsigned)((count + 255) / 256), 256, 0, st>>>(in, out, count);
+  return launch_status("convert_kernel");
 }
 
-// WCT matrices of every image (wct_rp.py:85-109): fp64 means (mu_c, mu_s in the workspace),
-// covariances, then T = Ic Mid Ic and offset = mu_s - T mu_c from the persistent matfun
-// launch (original: T = (Cs + 1e-4 I)^(1/2) (Cc + 1e-4 I)^(-1/2) in the reference's SVD form,
-// Li et al., wct_rp.py:96-101; offset unused). SRC is SRC_F32C (fp32 features) or SRC_F64C (fp64). means: optional fp32 (2n x C)
-// row means (content rows then style rows), used to centre; residual (2n, optional): final
-// Newton-Schulz residuals of (Cc + 1e-4 I) and of Mid's argument. T / offset: n x C x C / n x C.
+// Covariances of features that cov_v2 does not take (fp64, or C > 256), centred on the fp64
+// means in the workspace: upper-triangular tiles, split-K partials, fixed-order reduce.
+template <int SRC>
+static int cov_tiled(const void* cF, const void* sF, const WctLayout& L, double* ws,
+                     hipStream_t st) {
+  const int n = L.n, C = L.C;
+  double* part = ws + L.part;
+  const size_t half = (size_t)n * L.ksplit * C * C;
+  for (int which = 0; which < 2; ++which) {
+    const void* X = which == 0 ? cF : sF;
+    G64Args g = g64(X, X, part + which * half, C, C, (int)L.HW, (int)L.HW, (int)L.HW, C);
+    g.sB = g.sA;  // B_NK: X again
+    g.amean = g.bmean = ws + (which == 0 ? L.mu_c : L.mu_s);
+    g.sMean = C;
+    g.ksplit = L.ksplit;
+    g.sym = 1;
+    g.tiles_n = L.tiles;
+    dim3 grid(L.symtiles, 1, n * L.ksplit);
+    if (L.BT == 128)
+      gemm64<128, SRC, SRC, B_NK, OUT_PARTIAL>(g, grid, st);
+    else
+      gemm64<64, SRC, SRC, B_NK, OUT_PARTIAL>(g, grid, st);
+    if (int e = launch_status("gemm_f64_kernel(cov)")) return e;
+  }
+  const int64_t nel = (int64_t)n * C * C;
+  const unsigned rb = (unsigned)((nel + 255) / 256);
+  const double scale = 1.0 / (double)(L.HW - 1);
+  cov_reduce_kernel<<<rb, 256, 0, st>>>(part, ws + L.cc, C, L.ksplit, L.BT, scale, 1.0, n);
+  cov_reduce_kernel<<<rb, 256, 0, st>>>(part + half, ws + L.cs, C, L.ksplit, L.BT, scale, 0.0, n);
+  return launch_status("cov_reduce_kernel");
+}
+
+// Stages 1 and 2 of every WCT (wct_rp.py:85-94): the fp64 means mu_c, mu_s and the covariances
+// Cc (+ I), Cs of every image, left in the workspace. SRC is SRC_F32C (fp32 features) or
+// SRC_F64C (fp64). means: optional fp32 (2n x C) row means to centre on instead of computing them.
+template <int SRC>
+static int wct_moments(const void* cF, const void* sF, const float* means, const WctLayout& L,
+                       double* ws, hipStream_t st) {
+  using F = std::conditional_t<src_f32(SRC), float, double>;
+  const int n = L.n, C = L.C;
+  const int64_t cnt = (int64_t)2 * n * C;
+  double* mu = ws + L.mu_c;
+  if (!means) {
+    rowmean_kernel<F><<<2 * n * C, 256, 0, st>>>(static_cast<const F*>(cF),
+                                                static_cast<const F*>(sF), n * C, L.HW, mu);
+    if (int e = launch_status("rowmean_kernel")) return e;
+  }
+  if (L.v2) {
+    // fp32 features centred on fp32 means (given, or the fp64 row means rounded); cov_v2
+    // recovers the exact fp64 means and covariances from the centred row sums
+    const float* mu32 = means;
+    if (!mu32) {
+      float* m32 = reinterpret_cast<float*>(ws + L.mu32);
+      if (int e = convert(mu, m32, cnt, st)) return e;
+      mu32 = m32;
+    }
+    return cov_v2(static_cast<const float*>(cF), static_cast<const float*>(sF), mu32, n, C, L.HW,
+                  ws + L.cc, ws + L.cs, mu, ws + L.part, st);
+  }
+  if (means)
+    if (int e = convert(means, mu, cnt, st)) return e;
+  return cov_tiled<SRC>(cF, sF, L, ws, st);
+}
+
 // phase timing (rpst_wct_phase_timing / rpst_wct_phase_ms): events before the means, before
 // the matrix-function launch and after it, on the closed-form path
 static bool g_phase_on = false, g_phase_done = false;
@@ -608,160 +654,59 @@ static void phase_mark(int i, hipStream_t st) {
   if (i == 2) g_phase_done = true;
 }
 
+// Closed-form matrices of every image (Lu et al., wct_rp.py:102-109): the moments, then
+// Sc, Ic = (Cc + 1e-4 I)^(+-1/2), Mid = (Sc Cs Sc + 1e-4 I)^(1/2), T = Ic Mid Ic and
+// offset = mu_s - T mu_c from one persistent launch. T / offset: n x C x C / n x C; residual
+// (2n, optional): final Newton-Schulz residuals of (Cc + 1e-4 I) and of Mid's argument.
 template <int SRC>
-static int wct_matrices_impl(const void* cF, const void* sF, const float* means, int n, int C,
-                        int64_t HW, const WctLayout& L, double* ws, double* T, double* offset,
-                        double* residual, hipStream_t st, bool original = false) {
-  double *mu_c = ws + L.mu_c, *part = ws + L.part;
-  double *Cc = ws + L.cc, *Cs = ws + L.cs;
-  const int64_t cnt = (int64_t)2 * n * C;
-  if (SRC == SRC_F32C && L.v2) {
-    // centre on fp32 means (given, or the fp64 row means rounded); cov_v2 recovers the exact
-    // fp64 means and covariances from the centred row sums
-    const float* mu32 = means;
-    if (!mu32) {
-      rowmean_kernel<float><<<2 * n * C, 256, 0, st>>>(static_cast<const float*>(cF),
-                                                      static_cast<const float*>(sF), n * C, HW, mu_c);
-      float* m32 = reinterpret_cast<float*>(ws + L.mu32);
-      narrow_means_kernel<<<(unsigned)((cnt + 255) / 256), 256, 0, st>>>(mu_c, m32, cnt);
-      if (int e = launch_status("rowmean_kernel")) return e;
-      mu32 = m32;
-    }
-    if (int e = cov_v2(static_cast<const float*>(cF), static_cast<const float*>(sF), mu32, n, C,
-                       HW, Cc, Cs, mu_c, part, st))
-      return e;
-  } else {
-    // 1. means (content rows then style rows; mu_s follows mu_c in the workspace)
-    if (means) {
-      widen_means_kernel<<<(unsigned)((cnt + 255) / 256), 256, 0, st>>>(means, mu_c, cnt);
-      if (int e = launch_status("widen_means_kernel")) return e;
-    } else {
-      if (SRC == SRC_F32C)
-        rowmean_kernel<float><<<2 * n * C, 256, 0, st>>>(static_cast<const float*>(cF),
-                                                        static_cast<const float*>(sF), n * C, HW, mu_c);
-      else
-        rowmean_kernel<double><<<2 * n * C, 256, 0, st>>>(static_cast<const double*>(cF),
-                                                         static_cast<const double*>(sF), n * C, HW, mu_c);
-      if (int e = launch_status("rowmean_kernel")) return e;
-    }
-    double* mu_s = ws + L.mu_s;
-    // 2. covariances: upper-triangular tiles, split-K partials, fixed-order reduce
-    for (int which = 0; which < 2; ++which) {
-      G64Args g{};
-      g.A = g.B = which == 0 ? cF : sF;
-      g.C = part + (size_t)which * n * L.ksplit * C * C;
-      g.amean = g.bmean = which == 0 ? mu_c : mu_s;
-      g.sMean = C;
-      g.M = g.N = C;
-      g.K = (int)HW;
-      g.lda = g.ldb = (int)HW;
-      g.ldc = C;
-      g.sA = g.sB = (int64_t)C * HW;
-      g.sC = (int64_t)C * C;
-      g.ksplit = L.ksplit;
-      g.sym = 1;
-      g.tiles_n = L.tiles;
-      dim3 grid(L.symtiles, 1, n * L.ksplit);
-      if (L.BT == 128)
-        gemm64<128, SRC, SRC, B_NK, OUT_PARTIAL>(g, grid, st);
-      else
-        gemm64<64, SRC, SRC, B_NK, OUT_PARTIAL>(g, grid, st);
-      if (int e = launch_status("gemm_f64_kernel(cov)")) return e;
-    }
-    const int64_t nel = (int64_t)n * C * C;
-    const unsigned rb = (unsigned)((nel + 255) / 256);
-    cov_reduce_kernel<<<rb, 256, 0, st>>>(part, Cc, C, L.ksplit, L.BT, 1.0 / (double)(HW - 1), 1.0, n);
-    cov_reduce_kernel<<<rb, 256, 0, st>>>(part + (size_t)n * L.ksplit * C * C, Cs, C, L.ksplit, L.BT,
-                                          1.0 / (double)(HW - 1), 0.0, n);
-    if (int e = launch_status("cov_reduce_kernel")) return e;
-  }
-  if (original) {
-    // 3'. Li et al.: cF_inv_sqrt = matrix_inv_sqrt(Cc), sF_sqrt = matrix_sqrt(Cs) (each the
-    //     SVD form with the 1e-5 truncation: Newton-Schulz, Jacobi where it could differ),
-    //     T = sF_sqrt cF_inv_sqrt; sF_sqrt (cF_inv_sqrt cF) of wct_rp.py:101 is the same
-    //     product up to fp64 association. No barrier-timeout state is left in L.mf: flagged
-    //     matrices are recomputed by the Jacobi kernel.
-    double* Ai = ws + L.orig;
-    double* Bs = Ai + (size_t)n * C * C;
-    double* pw = Bs + (size_t)n * C * C;
-    if (int e = matfun_power(Cc, Ai, C, n, 1, nullptr, pw, st)) return e;
-    if (int e = matfun_power(Cs, Bs, C, n, 0, nullptr, pw, st)) return e;
-    if (int e = matfun_wct_clear_status(ws + L.mf, n, C, st)) return e;
-    G64Args g{};
-    g.A = Bs;
-    g.B = Ai;
-    g.C = T;
-    g.alpha = 1.0;
-    g.M = g.N = g.K = C;
-    g.lda = g.ldb = g.ldc = C;
-    g.sA = g.sB = g.sC = (int64_t)C * C;
-    g.ksplit = 1;
-    dim3 grid((unsigned)((C + 63) / 64), (unsigned)((C + 63) / 64), n);
-    gemm64<64, SRC_F64, SRC_F64, B_KN, OUT_F64>(g, grid, st);
-    return launch_status("gemm_f64_kernel(original T)");
-  }
-  // 3. Sc, Ic = (Cc + 1e-4 I)^(+-1/2); Mid = (Sc Cs Sc + 1e-4 I)^(1/2); T = Ic Mid Ic;
-  //    offset = mu_s - T mu_c: one persistent launch
+static int wct_closed_form(const void* cF, const void* sF, const float* means,
+                           const WctLayout& L, double* ws, double* T, double* offset,
+                           double* residual, hipStream_t st) {
+  phase_mark(0, st);
+  if (int e = wct_moments<SRC>(cF, sF, means, L, ws, st)) return e;
   phase_mark(1, st);
-  return matfun_wct(Cc, Cs, mu_c, T, offset, residual, n, C, ws + L.mf, st);
-}
-
-template <int SRC>
-static int wct_matrices(const void* cF, const void* sF, const float* means, int n, int C,
-                        int64_t HW, const WctLayout& L, double* ws, double* T, double* offset,
-                        double* residual, hipStream_t st, bool original = false) {
-  if (!original) phase_mark(0, st);
-  const int e = wct_matrices_impl<SRC>(cF, sF, means, n, C, HW, L, ws, T, offset, residual, st,
-                                       original);
-  if (!original && !e) phase_mark(2, st);
-  return e;
-}
-
-// Shared WCT body: the matrices, then out = T (cF - mu_c) + mu_s.
-template <int SRC, int OUTM>
-static int wct_run(const void* cF, const void* sF, void* out, int n, int C, int64_t HW,
-                   void* workspace, double* residual, hipStream_t st, bool original = false) {
-  const WctLayout L = wct_layout(n, C, HW, SRC == SRC_F32C);
-  double* ws = static_cast<double*>(workspace);
-  double *mu_c = ws + L.mu_c, *mu_s = ws + L.mu_s, *Tm = ws + L.tm;
-  if (int e = wct_matrices<SRC>(cF, sF, nullptr, n, C, HW, L, ws, Tm, ws + L.off, residual, st,
-                                original))
+  if (int e = matfun_wct(ws + L.cc, ws + L.cs, ws + L.mu_c, T, offset, residual, L.n, L.C,
+                         ws + L.mf, st))
     return e;
+  phase_mark(2, st);
+  return RPST_OK;
+}
 
-  // out = T (cF - mu_c) + mu_s; fp32 features -> fp32 MFMA (RPST_WCT_T_F64=1: fp64)
-  if (SRC == SRC_F32C && OUTM == OUT_F32_BIAS && !env_int("RPST_WCT_T_F64", 0)) {
-    float* Tf = reinterpret_cast<float*>(ws + L.tf);
-    float* muf = Tf + (size_t)n * C * C;
-    const int64_t nT = (int64_t)n * C * C, nmu = (int64_t)2 * n * C;  // mu_c, mu_s adjacent
-    wct_f32_prep_kernel<<<(unsigned)((std::max(nT, nmu) + 255) / 256), 256, 0, st>>>(Tm, mu_c, Tf, muf, nT, nmu, C);
-    if (int e = launch_status("wct_f32_prep_kernel")) return e;
-    return wct_transform_f32(Tf, static_cast<const float*>(cF), muf, muf + (size_t)n * C,
-                             static_cast<float*>(out), n, C, HW, st);
-  }
-  G64Args g{};
-  g.A = Tm;
-  g.B = cF;
-  g.C = out;
+// Li et al. (wct_rp.py:96-101) from the moments: cF_inv_sqrt = matrix_inv_sqrt(Cc), sF_sqrt =
+// matrix_sqrt(Cs) (each the SVD form with the 1e-5 truncation: Newton-Schulz, Jacobi where it
+// could differ), T = sF_sqrt cF_inv_sqrt; sF_sqrt (cF_inv_sqrt cF) of wct_rp.py:101 is the same
+// product up to fp64 association. No barrier-timeout state is left in L.mf: flagged matrices
+// are recomputed by the Jacobi kernel.
+static int wct_original(const WctLayout& L, double* ws, double* T, hipStream_t st) {
+  const int n = L.n, C = L.C;
+  double* Ai = ws + L.orig;
+  double* Bs = Ai + (size_t)n * C * C;
+  double* pw = Bs + (size_t)n * C * C;
+  if (int e = matfun_power(ws + L.cc, Ai, C, n, 1, nullptr, pw, st)) return e;
+  if (int e = matfun_power(ws + L.cs, Bs, C, n, 0, nullptr, pw, st)) return e;
+  if (int e = matfun_wct_clear_status(ws + L.mf, n, C, st)) return e;
+  dim3 grid((unsigned)((C + 63) / 64), (unsigned)((C + 63) / 64), n);
+  gemm64<64, SRC_F64, SRC_F64, B_KN, OUT_F64>(g64(Bs, Ai, T, C, C, C, C, C, C), grid, st);
+  return launch_status("gemm_f64_kernel(original T)");
+}
+
+// out = T (cF - mu_c) + mu_s with T in L.tm and the means in the workspace; fp32 features ->
+// fp32 out on the fp32 MFMA (RPST_WCT_T_F64=1: the fp64 product), fp64 -> fp64
+template <int SRC>
+static int wct_transform(const void* cF, void* out, const WctLayout& L, double* ws,
+                         hipStream_t st) {
+  const int n = L.n, C = L.C;
+  double *mu_c = ws + L.mu_c, *mu_s = ws + L.mu_s, *Tm = ws + L.tm;
+  if (SRC == SRC_F32C && !env_int("RPST_WCT_T_F64", 0))
+    return wct_transform_f32(Tm, mu_c, mu_s, static_cast<const float*>(cF),
+                             static_cast<float*>(out), n, C, L.HW,
+                             reinterpret_cast<float*>(ws + L.tf), st);
+  G64Args g = g64(Tm, cF, out, C, (int)L.HW, C, C, (int)L.HW, (int)L.HW);
   g.bmean = mu_c;
   g.bias = mu_s;
   g.sMean = C;
-  g.M = C;
-  g.N = (int)HW;
-  g.K = C;
-  g.lda = C;
-  g.ldb = (int)HW;
-  g.ldc = (int)HW;
-  g.sA = (int64_t)C * C;
-  g.sB = (int64_t)C * HW;
-  g.sC = (int64_t)C * HW;
-  g.ksplit = 1;
-  if (env_int("RPST_WCT_T_BT", 64) == 128) {
-    dim3 grid((unsigned)((HW + 127) / 128), (C + 127) / 128, n);
-    gemm64<128, SRC_F64, SRC, B_KN, OUTM>(g, grid, st);
-  } else {
-    dim3 grid((unsigned)((HW + 63) / 64), (C + 63) / 64, n);
-    gemm64<64, SRC_F64, SRC, B_KN, OUTM>(g, grid, st);
-  }
+  dim3 grid((unsigned)((L.HW + 63) / 64), (C + 63) / 64, n);
+  gemm64<64, SRC_F64, SRC, B_KN, SRC == SRC_F32C ? OUT_F32_BIAS : OUT_F64_BIAS>(g, grid, st);
   return launch_status("gemm_f64_kernel(transform)");
 }
 
@@ -769,24 +714,60 @@ static int wct_run(const void* cF, const void* sF, void* out, int n, int C, int6
 // the per-image folded weights W T_n of rpst_conv2d_mix (rpst_wino4.hip) on the fp64 MFMA
 int gemm_f32w_f64(const float* W, const double* T, double* out, int n, int rows, int K,
                   hipStream_t st) {
-  G64Args g{};
-  g.A = W;
-  g.B = T;
-  g.C = out;
-  g.alpha = 1.0;
-  g.M = rows;
-  g.N = K;
-  g.K = K;
-  g.lda = K;
-  g.ldb = K;
-  g.ldc = K;
+  G64Args g = g64(W, T, out, rows, K, K, K, K, K);
   g.sA = 0;
-  g.sB = (int64_t)K * K;
-  g.sC = (int64_t)rows * K;
-  g.ksplit = 1;
   dim3 grid((unsigned)((K + 63) / 64), (unsigned)((rows + 63) / 64), n);
   gemm64<64, SRC_F32, SRC_F64, B_KN, OUT_F64>(g, grid, st);
   return launch_status("gemm_f64_kernel(mix weights)");
+}
+
+// ---- argument checks of the entry points ----------------------------------------------
+// An entry's own limits on (n, C, HW). detail (wct_fuse, wct_params): the messages carry the
+// values, and a shape over the limits is reported apart from a non-positive one.
+struct EntryLimits {
+  int max_n, max_C;
+  int64_t max_HW;
+  bool detail;
+};
+
+// Null pointers, then the shape, then the workspace against need(n, C, HW) (need null: the
+// entry takes no workspace size); nothing is launched before these pass.
+static int check_entry(const char* name, bool pointers, int n, int C, int64_t HW,
+                       const EntryLimits& lim, size_t (*need)(int, int, int64_t),
+                       const void* workspace, size_t workspace_bytes) {
+  RPST_REQUIRE(pointers, "%s: null pointer", name);
+  const bool positive = n > 0 && C > 0 && HW > 1;
+  const bool fits = n <= lim.max_n && C <= lim.max_C && HW <= lim.max_HW;
+  if (lim.detail) {
+    RPST_REQUIRE(positive, "%s: bad shape n=%d C=%d HW=%lld", name, n, C, (long long)HW);
+    RPST_REQUIRE(fits, "%s: shape too large", name);
+  } else {
+    RPST_REQUIRE(positive && fits, "%s: bad shape", name);
+  }
+  if (need && (!workspace || workspace_bytes < need(n, C, HW))) {
+    if (lim.detail)
+      set_error("%s: workspace %zu < %zu bytes", name, workspace_bytes, need(n, C, HW));
+    else
+      set_error("%s: workspace too small", name);
+    return RPST_EWORKSPACE;
+  }
+  return RPST_OK;
+}
+
+// the per-image status words of the last closed-form call on `workspace` (laid out for fp32
+// or fp64 features) copied to `status`
+static int copy_status(const char* name, const void* workspace, int n, int C, int64_t HW, bool f32,
+                       int* status, rpst_stream_t stream) {
+  if (int e = check_entry(name, workspace && status, n, C, HW, {INT_MAX, 1024, INT64_MAX, false},
+                          nullptr, nullptr, 0))
+    return e;
+  const WctLayout L = wct_layout(n, C, HW, f32);
+  double* ws = static_cast<double*>(const_cast<void*>(workspace));
+  return matfun_wct_status(ws + L.mf, n, C, status, as_stream(stream));
+}
+
+static size_t matrix_power_need(int batch, int n, int64_t) {
+  return rpst_matrix_power_workspace_size(n, batch);
 }
 
 }  // namespace rpst
@@ -803,72 +784,73 @@ extern "C" size_t rpst_wct_workspace_size(int n, int C, int64_t HW) {
 extern "C" int rpst_wct_fuse(const float* content, const float* style, float* out, int n, int C,
                              int64_t HW, double* residual, void* workspace,
                              size_t workspace_bytes, rpst_stream_t stream) {
-  RPST_REQUIRE(content && style && out, "wct_fuse: null pointer");
-  RPST_REQUIRE(n > 0 && C > 0 && HW > 1, "wct_fuse: bad shape n=%d C=%d HW=%lld", n, C, (long long)HW);
-  RPST_REQUIRE(HW <= 0x7fffffffLL && n <= 32767 && C <= 1024, "wct_fuse: shape too large");
-  if (!workspace || workspace_bytes < rpst_wct_workspace_size(n, C, HW)) {
-    set_error("wct_fuse: workspace %zu < %zu bytes", workspace_bytes, rpst_wct_workspace_size(n, C, HW));
-    return RPST_EWORKSPACE;
-  }
-  return wct_run<SRC_F32C, OUT_F32_BIAS>(content, style, out, n, C, HW, workspace, residual,
-                                         as_stream(stream));
+  if (int e = check_entry("wct_fuse", content && style && out, n, C, HW,
+                          {32767, 1024, 0x7fffffffLL, true}, rpst_wct_workspace_size, workspace,
+                          workspace_bytes))
+    return e;
+  const WctLayout L = wct_layout(n, C, HW, true);
+  double* ws = static_cast<double*>(workspace);
+  hipStream_t st = as_stream(stream);
+  if (int e = wct_closed_form<SRC_F32C>(content, style, nullptr, L, ws, ws + L.tm, ws + L.off,
+                                        residual, st))
+    return e;
+  return wct_transform<SRC_F32C>(content, out, L, ws, st);
 }
 
 extern "C" int rpst_wct_params(const float* content, const float* style, const float* means,
                                double* T, double* offset, int n, int C, int64_t HW,
                                double* residual, void* workspace, size_t workspace_bytes,
                                rpst_stream_t stream) {
-  RPST_REQUIRE(content && style && T && offset, "wct_params: null pointer");
-  RPST_REQUIRE(n > 0 && C > 0 && HW > 1, "wct_params: bad shape n=%d C=%d HW=%lld", n, C,
-               (long long)HW);
-  RPST_REQUIRE(HW <= 0x7fffffffLL && n <= 65535, "wct_params: shape too large");
-  if (!workspace || workspace_bytes < rpst_wct_workspace_size(n, C, HW)) {
-    set_error("wct_params: workspace %zu < %zu bytes", workspace_bytes,
-              rpst_wct_workspace_size(n, C, HW));
-    return RPST_EWORKSPACE;
-  }
+  if (int e = check_entry("wct_params", content && style && T && offset, n, C, HW,
+                          {65535, INT_MAX, 0x7fffffffLL, true}, rpst_wct_workspace_size,
+                          workspace, workspace_bytes))
+    return e;
   RPST_REQUIRE(C <= 1024, "wct_params: C=%d > 1024", C);
-  hipStream_t st = as_stream(stream);
-  const WctLayout L = wct_layout(n, C, HW, true);
-  return wct_matrices<SRC_F32C>(content, style, means, n, C, HW, L, static_cast<double*>(workspace),
-                                T, offset, residual, st);
+  return wct_closed_form<SRC_F32C>(content, style, means, wct_layout(n, C, HW, true),
+                                   static_cast<double*>(workspace), T, offset, residual,
+                                   as_stream(stream));
 }
 
 extern "C" int rpst_whiten_and_color_f64(const double* cF, const double* sF, double* out, int C,
                                          int64_t HW, double* residual, void* workspace,
                                          size_t workspace_bytes, rpst_stream_t stream) {
-  RPST_REQUIRE(cF && sF && out, "whiten_and_color: null pointer");
-  RPST_REQUIRE(C > 0 && C <= 1024 && HW > 1 && HW <= 0x7fffffffLL, "whiten_and_color: bad shape");
-  if (!workspace || workspace_bytes < rpst_wct_workspace_size(1, C, HW)) {
-    set_error("whiten_and_color: workspace too small");
-    return RPST_EWORKSPACE;
-  }
-  return wct_run<SRC_F64C, OUT_F64_BIAS>(cF, sF, out, 1, C, HW, workspace, residual,
-                                         as_stream(stream));
+  if (int e = check_entry("whiten_and_color", cF && sF && out, 1, C, HW,
+                          {1, 1024, 0x7fffffffLL, false}, rpst_wct_workspace_size, workspace,
+                          workspace_bytes))
+    return e;
+  const WctLayout L = wct_layout(1, C, HW, false);
+  double* ws = static_cast<double*>(workspace);
+  hipStream_t st = as_stream(stream);
+  if (int e = wct_closed_form<SRC_F64C>(cF, sF, nullptr, L, ws, ws + L.tm, ws + L.off, residual,
+                                        st))
+    return e;
+  return wct_transform<SRC_F64C>(cF, out, L, ws, st);
 }
 
 extern "C" int rpst_whiten_and_color_original_f64(const double* cF, const double* sF,
                                                   double* out, int C, int64_t HW, void* workspace,
                                                   size_t workspace_bytes, rpst_stream_t stream) {
-  RPST_REQUIRE(cF && sF && out, "whiten_and_color(original): null pointer");
-  RPST_REQUIRE(C > 0 && C <= 1024 && HW > 1 && HW <= 0x7fffffffLL,
-               "whiten_and_color(original): bad shape");
-  if (!workspace || workspace_bytes < rpst_wct_workspace_size(1, C, HW)) {
-    set_error("whiten_and_color(original): workspace too small");
-    return RPST_EWORKSPACE;
-  }
-  return wct_run<SRC_F64C, OUT_F64_BIAS>(cF, sF, out, 1, C, HW, workspace, nullptr,
-                                         as_stream(stream), true);
+  if (int e = check_entry("whiten_and_color(original)", cF && sF && out, 1, C, HW,
+                          {1, 1024, 0x7fffffffLL, false}, rpst_wct_workspace_size, workspace,
+                          workspace_bytes))
+    return e;
+  const WctLayout L = wct_layout(1, C, HW, false);
+  double* ws = static_cast<double*>(workspace);
+  hipStream_t st = as_stream(stream);
+  if (int e = wct_moments<SRC_F64C>(cF, sF, nullptr, L, ws, st)) return e;
+  if (int e = wct_original(L, ws, ws + L.tm, st)) return e;
+  return wct_transform<SRC_F64C>(cF, out, L, ws, st);
 }
 
+// rpst_wct_fuse / rpst_wct_params lay the workspace out for fp32 features
 extern "C" int rpst_wct_status(const void* workspace, int n, int C, int64_t HW, int* status,
                                rpst_stream_t stream) {
-  RPST_REQUIRE(workspace && status, "wct_status: null pointer");
-  RPST_REQUIRE(n > 0 && C > 0 && C <= 1024 && HW > 1, "wct_status: bad shape");
-  // rpst_wct_fuse / rpst_wct_params lay the workspace out for fp32 features
-  const WctLayout L = wct_layout(n, C, HW, true);
-  double* ws = static_cast<double*>(const_cast<void*>(workspace));
-  return matfun_wct_status(ws + L.mf, n, C, status, as_stream(stream));
+  return copy_status("wct_status", workspace, n, C, HW, true, status, stream);
+}
+
+extern "C" int rpst_whiten_and_color_status(const void* workspace, int C, int64_t HW, int* status,
+                                            rpst_stream_t stream) {
+  return copy_status("whiten_and_color_status", workspace, 1, C, HW, false, status, stream);
 }
 
 extern "C" int rpst_wct_phase_timing(int on) {
@@ -890,15 +872,6 @@ extern "C" int rpst_wct_phase_ms(float* cov_ms, float* matfun_ms) {
   return RPST_OK;
 }
 
-extern "C" int rpst_whiten_and_color_status(const void* workspace, int C, int64_t HW, int* status,
-                                            rpst_stream_t stream) {
-  RPST_REQUIRE(workspace && status, "whiten_and_color_status: null pointer");
-  RPST_REQUIRE(C > 0 && C <= 1024 && HW > 1, "whiten_and_color_status: bad shape");
-  const WctLayout L = wct_layout(1, C, HW, false);
-  double* ws = static_cast<double*>(const_cast<void*>(workspace));
-  return matfun_wct_status(ws + L.mf, 1, C, status, as_stream(stream));
-}
-
 extern "C" size_t rpst_matrix_power_workspace_size(int n, int batch) {
   if (n <= 0 || batch <= 0) return 0;
   return matfun_power_work_doubles(n, batch) * sizeof(double);
@@ -907,12 +880,9 @@ extern "C" size_t rpst_matrix_power_workspace_size(int n, int batch) {
 extern "C" int rpst_matrix_power_psd_f64(const double* A, double* out, int n, int batch,
                                          int inverse, double* residual, void* workspace,
                                          size_t workspace_bytes, rpst_stream_t stream) {
-  RPST_REQUIRE(A && out, "matrix_power: null pointer");
-  RPST_REQUIRE(n > 0 && n <= 1024 && batch > 0 && batch <= 65535, "matrix_power: bad shape");
-  if (!workspace || workspace_bytes < rpst_matrix_power_workspace_size(n, batch)) {
-    set_error("matrix_power: workspace too small");
-    return RPST_EWORKSPACE;
-  }
+  if (int e = check_entry("matrix_power", A && out, batch, n, 2, {65535, 1024, 2, false},
+                          matrix_power_need, workspace, workspace_bytes))
+    return e;
   return matfun_power(A, out, n, batch, inverse, residual, static_cast<double*>(workspace),
                       as_stream(stream));
 }

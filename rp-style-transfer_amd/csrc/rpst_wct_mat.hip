@@ -38,9 +38,9 @@ namespace rpst {
 
 constexpr int kCovBK = 32;       // staged k depth
 constexpr int kCovSplits = 8;    // K splits per matrix (HW >= 8 x 32): 8 x 2n workgroups
-#ifndef RPST_COV_UNROLL  // cov_syrk16_kernel: k sub-steps unrolled per stage (1 / 2 / 8:
-#define RPST_COV_UNROLL 2  // wct_params 12.35 / 12.08 / 13.03 ms at n 16, C 256, 512^2)
-#endif
+// cov_syrk16_kernel: k sub-steps unrolled per stage (1 / 2 / 8: wct_params 12.35 / 12.08 /
+// 13.03 ms at n 16, C 256, 512^2)
+constexpr int kCovUnroll = 2;
 
 struct CovArgs {
   const float* X0;     // content (n, C, HW)
@@ -176,7 +176,7 @@ __global__ __launch_bounds__(512, 1) void cov_syrk_kernel(CovArgs a) {
 // sub-step: A and B share one lane map, so the registers of block row I serve as A of row I
 // and as B of column I), waves 12-15 one diagonal super-block each (10 blocks from 4 reads);
 // every SIMD (waves s, s + 4, s + 8, s + 12) carries 3 x 8 + 10 = 34 blocks. The strided map
-// of cov_syrk_kernel reads two operands per MFMA. Partials as cov_syrk_kernel<16> (KG = 1).
+// of cov_syrk_kernel reads two operands per MFMA. Partials in cov_syrk_kernel's layout (KG = 1).
 template <bool VEC>
 __global__ __launch_bounds__(1024, 1) void cov_syrk16_kernel(CovArgs a) {
   constexpr int NB = 16, R = 256, LDX = R + 16;
@@ -263,7 +263,7 @@ __global__ __launch_bounds__(1024, 1) void cov_syrk16_kernel(CovArgs a) {
       __syncthreads();  // stage st is in Xs[st & 1]; every wave is done with stage st - 1
       if (st + 1 < nst) load(st + 1);
       const double* xs = Xs[st & 1];
-#pragma unroll RPST_COV_UNROLL
+#pragma unroll kCovUnroll
       for (int ks = 0; ks < kCovBK / 4; ++ks) {
         const double* xk = xs + (4 * ks + (lane >> 4)) * LDX + (lane & 15);
         double r[4];
@@ -355,18 +355,36 @@ __global__ void cov_finish_kernel(const double* __restrict__ part, const double*
 
 bool cov_v2_supported(int C) { return C >= 1 && C <= 256; }
 
-// k per split: HW / 8 rounded up to whole 32-deep stages (512^2: 32768), so every shape
-// fills 8 x 2n workgroups (C = 128 at 256^2 ran 2 splits, C = 256 at 128^2 one); a function
-// of HW only, so an image's bits never depend on its batch
-static int64_t cov_kper(int64_t HW) {
-  const int64_t k = (HW + kCovSplits - 1) / kCovSplits;
-  return (k + kCovBK - 1) / kCovBK * kCovBK;
-}
-static int cov_ksplit(int64_t HW) { return (int)((HW + cov_kper(HW) - 1) / cov_kper(HW)); }
+// The work area of cov_v2, stated once. k per split: HW / 8 rounded up to whole 32-deep
+// stages (512^2: 32768), so every shape fills 8 x 2n workgroups (C = 128 at 256^2 ran 2
+// splits, C = 256 at 128^2 one); a function of HW only, so an image's bits never depend on
+// its batch.
+struct CovLayout {
+  int NB, nblk, kper, ksplit, PS;  // PS: partials per matrix (K splits x k groups)
+  size_t rsum, total;              // doubles: the partials at 0, the row sums after them
+};
 
-size_t cov_v2_work_doubles(int n, int C, int64_t HW) {
-  const int NB = cov_nb(C), nblk = NB * (NB + 1) / 2, ks = cov_ksplit(HW);
-  return (size_t)2 * n * ks * cov_kg(NB) * nblk * 256 + (size_t)2 * n * ks * C;
+static CovLayout cov_layout(int n, int C, int64_t HW) {
+  CovLayout L{};
+  L.NB = cov_nb(C);
+  L.nblk = L.NB * (L.NB + 1) / 2;
+  const int64_t k = (HW + kCovSplits - 1) / kCovSplits;
+  L.kper = (int)((k + kCovBK - 1) / kCovBK * kCovBK);
+  L.ksplit = (int)((HW + L.kper - 1) / L.kper);
+  L.PS = L.ksplit * cov_kg(L.NB);
+  L.rsum = (size_t)2 * n * L.PS * L.nblk * 256;
+  L.total = L.rsum + (size_t)2 * n * L.ksplit * C;
+  return L;
+}
+
+size_t cov_v2_work_doubles(int n, int C, int64_t HW) { return cov_layout(n, C, HW).total; }
+
+template <bool VEC>
+static void cov_launch(int NB, const CovArgs& a, hipStream_t st) {
+  const dim3 grid(a.ksplit, 2 * a.n);
+  if (NB == 4) cov_syrk_kernel<4, VEC><<<grid, 512, 0, st>>>(a);
+  else if (NB == 8) cov_syrk_kernel<8, VEC><<<grid, 512, 0, st>>>(a);
+  else cov_syrk16_kernel<VEC><<<grid, 1024, 0, st>>>(a);
 }
 
 int cov_v2(const float* cF, const float* sF, const float* mu32, int n, int C, int64_t HW,
@@ -375,6 +393,7 @@ int cov_v2(const float* cF, const float* sF, const float* mu32, int n, int C, in
     set_error("cov_v2: unsupported shape n=%d C=%d HW=%lld", n, C, (long long)HW);
     return RPST_EINVAL;
   }
+  const CovLayout L = cov_layout(n, C, HW);
   CovArgs a{};
   a.X0 = cF;
   a.X1 = sF;
@@ -382,31 +401,18 @@ int cov_v2(const float* cF, const float* sF, const float* mu32, int n, int C, in
   a.n = n;
   a.C = C;
   a.HW = HW;
-  a.ksplit = cov_ksplit(HW);
-  a.kper = (int)cov_kper(HW);
-  const int NB = cov_nb(C), nblk = NB * (NB + 1) / 2, PS = a.ksplit * cov_kg(NB);
+  a.ksplit = L.ksplit;
+  a.kper = L.kper;
   a.part = work;
-  a.rsum = work + (size_t)2 * n * PS * nblk * 256;
+  a.rsum = work + L.rsum;
   const bool vec = HW % 4 == 0 && (reinterpret_cast<uintptr_t>(cF) & 15) == 0 &&
                    (reinterpret_cast<uintptr_t>(sF) & 15) == 0;
-  const dim3 grid(a.ksplit, 2 * n);
-#define RPST_COV_LAUNCH(NBv)                                                   \
-  (vec ? (cov_syrk_kernel<NBv, true><<<grid, 512, 0, st>>>(a), 0)              \
-       : (cov_syrk_kernel<NBv, false><<<grid, 512, 0, st>>>(a), 0))
-  // RPST_COV_COMPACT=0: the strided 8-wave form for C > 128 too (A/B)
-  const char* ce = getenv("RPST_COV_COMPACT");
-  const bool compact = !(ce && *ce == '0');
-  if (NB == 4) RPST_COV_LAUNCH(4);
-  else if (NB == 8) RPST_COV_LAUNCH(8);
-  else if (compact) {
-    if (vec) cov_syrk16_kernel<true><<<grid, 1024, 0, st>>>(a);
-    else cov_syrk16_kernel<false><<<grid, 1024, 0, st>>>(a);
-  } else RPST_COV_LAUNCH(16);
-#undef RPST_COV_LAUNCH
+  if (vec) cov_launch<true>(L.NB, a, st);
+  else cov_launch<false>(L.NB, a, st);
   if (int e = launch_status("cov_syrk_kernel")) return e;
   const int64_t tot = (int64_t)2 * n * C * C;
-  cov_finish_kernel<<<(unsigned)((tot + 255) / 256), 256, 0, st>>>(a.part, a.rsum, mu32, Cc, Cs,
-                                                                  mu64, n, C, NB, PS, a.ksplit, HW);
+  cov_finish_kernel<<<(unsigned)((tot + 255) / 256), 256, 0, st>>>(
+      a.part, a.rsum, mu32, Cc, Cs, mu64, n, C, L.NB, L.PS, a.ksplit, HW);
   return launch_status("cov_finish_kernel");
 }
 
@@ -889,39 +895,38 @@ static int mf_resident_cap() {
   return cap;
 }
 
-// layout geometry (the workspace is sized for G = 256 / P groups, whatever the device)
-static void mf_geometry(int n, int batch, int& tpd, int& P, int& G) {
-  tpd = (n + kMT - 1) / kMT;
-  P = tpd * tpd;
-  G = 256 / P;
-  if (G < 1) G = 1;
-  if (G > batch) G = batch;
-}
+// The matfun workspace, stated once (sized for G = 256 / P groups, whatever the device):
+// per group kMfBufs n x n scratch matrices and [2][kRedSlots][P] reduction slots, then the G
+// barrier counters and the abort word (unsigned), then the per-matrix flags (int).
+struct MfLayout {
+  int tpd, P, G;      // tiles per dimension, workgroups per matrix, groups
+  size_t red, bar;    // offsets in doubles (the scratch at 0)
+  size_t total;
+  unsigned* bars(double* work) const { return reinterpret_cast<unsigned*>(work + bar); }
+  int* flags(double* work) const { return reinterpret_cast<int*>(bars(work) + G + 1); }
+};
 
-static size_t mf_work_doubles(int n, int batch) {
-  int tpd, P, G;
-  mf_geometry(n, batch, tpd, P, G);
-  // scratch, reduction slots, barrier counters + abort word, flags (ints, rounded up)
-  return (size_t)G * kMfBufs * n * n + (size_t)G * 2 * kRedSlots * P + (size_t)(G + 1 + 1) / 2 +
-         (size_t)(batch + 1) / 2 + 2;
-}
-
-// per-matrix flags of the last launch on this workspace (layout of mf_launch)
-static int* mf_flags(double* work, int n, int batch) {
-  int tpd, P, G;
-  mf_geometry(n, batch, tpd, P, G);
-  return reinterpret_cast<int*>(
-      reinterpret_cast<unsigned*>(work + (size_t)G * kMfBufs * n * n + (size_t)G * 2 * kRedSlots * P) +
-      G + 1);
+static MfLayout mf_layout(int n, int batch) {
+  MfLayout L{};
+  L.tpd = (n + kMT - 1) / kMT;
+  L.P = L.tpd * L.tpd;
+  L.G = 256 / L.P;
+  if (L.G < 1) L.G = 1;
+  if (L.G > batch) L.G = batch;
+  L.red = (size_t)L.G * kMfBufs * n * n;
+  L.bar = L.red + (size_t)L.G * 2 * kRedSlots * L.P;
+  L.total = L.bar + (size_t)(L.G + 1 + 1) / 2 + (size_t)(batch + 1) / 2 + 2;
+  return L;
 }
 
 static int mf_launch(MfArgs a, double* work, hipStream_t st) {
-  int Gl;
-  mf_geometry(a.n, a.batch, a.tpd, a.P, Gl);
+  const MfLayout L = mf_layout(a.n, a.batch);
+  a.tpd = L.tpd;
+  a.P = L.P;
   a.scratch = work;
-  a.red = a.scratch + (size_t)Gl * kMfBufs * a.n * a.n;
-  a.bar = reinterpret_cast<unsigned*>(a.red + (size_t)Gl * 2 * kRedSlots * a.P);
-  a.flags = reinterpret_cast<int*>(a.bar + Gl + 1);
+  a.red = work + L.red;
+  a.bar = L.bars(work);
+  a.flags = L.flags(work);
   // groups that the device can hold at once: the group barriers need every workgroup of a
   // group resident (a smaller device, or a grid the occupancy does not cover, gets fewer
   // groups looping over more matrices)
@@ -930,13 +935,13 @@ static int mf_launch(MfArgs a, double* work, hipStream_t st) {
     set_error("matfun: %d workgroups per matrix but only %d resident on this device", a.P, cap);
     return RPST_EINVAL;
   }
-  a.G = Gl < cap / a.P ? Gl : cap / a.P;
+  a.G = L.G < cap / a.P ? L.G : cap / a.P;
   {
     const char* e = getenv("RPST_MATFUN_DEBUG_SKIP");
     a.dbg_skip = (e && *e && atoi(e) != 0 && a.P > 1) ? 1 : 0;
   }
-  // barrier counters (the layout's Gl of them) + abort word + flags
-  if (hipMemsetAsync(a.bar, 0, sizeof(unsigned) * (Gl + 1) + sizeof(int) * a.batch, st) !=
+  // barrier counters (the layout's G of them) + abort word + flags
+  if (hipMemsetAsync(a.bar, 0, sizeof(unsigned) * (L.G + 1) + sizeof(int) * a.batch, st) !=
       hipSuccess) {
     set_error("matfun: workspace reset failed");
     return RPST_EHIP;
@@ -951,7 +956,7 @@ static int mf_launch(MfArgs a, double* work, hipStream_t st) {
 }
 
 int matfun_wct_status(double* work, int n, int C, int* status, hipStream_t st) {
-  if (hipMemcpyAsync(status, mf_flags(work, C, n), sizeof(int) * (size_t)n,
+  if (hipMemcpyAsync(status, mf_layout(C, n).flags(work), sizeof(int) * (size_t)n,
                      hipMemcpyDeviceToDevice, st) != hipSuccess) {
     set_error("wct_status: copy failed");
     return RPST_EHIP;
@@ -959,10 +964,10 @@ int matfun_wct_status(double* work, int n, int C, int* status, hipStream_t st) {
   return RPST_OK;
 }
 
-size_t matfun_wct_work_doubles(int n, int C) { return mf_work_doubles(C, n); }
+size_t matfun_wct_work_doubles(int n, int C) { return mf_layout(C, n).total; }
 
 int matfun_wct_clear_status(double* work, int n, int C, hipStream_t st) {
-  if (hipMemsetAsync(mf_flags(work, C, n), 0, sizeof(int) * (size_t)n, st) != hipSuccess) {
+  if (hipMemsetAsync(mf_layout(C, n).flags(work), 0, sizeof(int) * (size_t)n, st) != hipSuccess) {
     set_error("wct: status reset failed");
     return RPST_EHIP;
   }
@@ -988,9 +993,10 @@ int matfun_wct(const double* Cc, const double* Cs, const double* mu64, double* T
   return mf_launch(a, work, st);
 }
 
+// the matfun workspace, then the Jacobi kernel's two padded n x n matrices per input
 size_t matfun_power_work_doubles(int n, int batch) {
   const size_t np = (size_t)(n + (n & 1));
-  return mf_work_doubles(n, batch) + (size_t)batch * 2 * np * np;
+  return mf_layout(n, batch).total + (size_t)batch * 2 * np * np;
 }
 
 int matfun_power(const double* A, double* out, int n, int batch, int inverse, double* residual,
@@ -1008,9 +1014,8 @@ int matfun_power(const double* A, double* out, int n, int batch, int inverse, do
   a.inverse = inverse;
   a.residual = residual;
   if (int e = mf_launch(a, work, st)) return e;
-  double* jw = work + mf_work_doubles(n, batch);
-  const int* flags = mf_flags(work, n, batch);
-  jacobi_power_kernel<<<batch, 1024, 0, st>>>(A, out, flags, n, inverse, jw);
+  const MfLayout L = mf_layout(n, batch);
+  jacobi_power_kernel<<<batch, 1024, 0, st>>>(A, out, L.flags(work), n, inverse, work + L.total);
   return launch_status("jacobi_power_kernel");
 }
 

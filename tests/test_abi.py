@@ -53,6 +53,111 @@ def test_size_queries_are_host_only():
     assert lib.rpst_conv2d_packed_size(16, 3, 2) == 0
 
 
+WCT_SIZES = {(3, 16, 35): 1075840, (1, 64, 1023): 1796720, (1, 64, 8192): 1796720,
+             (2, 128, 384): 8268896, (2, 256, 256): 33054816, (1, 200, 117): 10090128,
+             (1, 160, 351): 6458832, (1, 320, 256): 25820880, (1, 272, 117): 18658128,
+             (1, 320, 8192): 27459280, (16, 256, 262144): 1321402688,
+             (16, 512, 4096): 503677152, (1, 512, 2): 66089040}
+POWER_SIZES = {(96, 3): 2876208, (64, 1): 426080, (256, 16): 109068440, (512, 2): 54534184,
+               (1000, 1): 104016416}
+RETIRED_WCT_KNOBS = {"RPST_WCT_KMIN": "1024", "RPST_WCT_COV_BT": "64", "RPST_WCT_COV_V2": "0",
+                     "RPST_WCT_T_BT": "128", "RPST_COV_COMPACT": "0"}
+
+
+def test_wct_workspace_sizes_are_pinned(monkeypatch):
+    """rpst_wct_workspace_size(n, C, HW) and rpst_matrix_power_workspace_size(n, batch) are
+    host-only functions of their arguments: the retired RPST_WCT_* / RPST_COV_* switches no
+    longer move them (a workspace sized under one environment serves a call under another)."""
+    lib = _lib.load()
+
+    def check():
+        for args, nbytes in WCT_SIZES.items():
+            assert lib.rpst_wct_workspace_size(*args) == nbytes, args
+        for args, nbytes in POWER_SIZES.items():
+            assert lib.rpst_matrix_power_workspace_size(*args) == nbytes, args
+
+    for k in RETIRED_WCT_KNOBS:
+        monkeypatch.delenv(k, raising=False)
+    check()
+    for k, v in RETIRED_WCT_KNOBS.items():
+        monkeypatch.setenv(k, v)
+        check()
+        monkeypatch.delenv(k)
+
+
+def _wct_entry_args(entry, first=1, n=2, C=16, HW=64, short=0):
+    """Arguments of a WCT entry point with placeholder pointers (every case below fails its
+    argument checks, which run before any launch). n / C / HW: batch, channels, pixels; for
+    rpst_matrix_power_psd_f64 the batch and the matrix size. short: bytes the workspace lacks."""
+    lib = _lib.load()
+    n1 = 1 if "whiten" in entry else n
+    ws = max(lib.rpst_wct_workspace_size(n1, C, HW) - short, 0)
+    pw = max(lib.rpst_matrix_power_workspace_size(C, n) - short, 0)
+    return {
+        "rpst_wct_fuse": (first, 1, 1, n, C, HW, None, 1, ws, None),
+        "rpst_wct_params": (first, 1, None, 1, 1, n, C, HW, None, 1, ws, None),
+        "rpst_whiten_and_color_f64": (first, 1, 1, C, HW, None, 1, ws, None),
+        "rpst_whiten_and_color_original_f64": (first, 1, 1, C, HW, 1, ws, None),
+        "rpst_wct_status": (first, n, C, HW, 1, None),
+        "rpst_whiten_and_color_status": (first, C, HW, 1, None),
+        "rpst_matrix_power_psd_f64": (first, 1, C, n, 0, None, 1, pw, None),
+    }[entry]
+
+
+# (entry, defect) -> (status, rpst_last_error()), as the entries answered before they shared
+# one check: RPST_EINVAL -1, RPST_EWORKSPACE -3
+WCT_ERRORS = {
+    ("rpst_wct_fuse", "null"): (-1, "wct_fuse: null pointer"),
+    ("rpst_wct_fuse", "n=0"): (-1, "wct_fuse: bad shape n=0 C=16 HW=64"),
+    ("rpst_wct_fuse", "HW=1"): (-1, "wct_fuse: bad shape n=2 C=16 HW=1"),
+    ("rpst_wct_fuse", "C=1025"): (-1, "wct_fuse: shape too large"),
+    ("rpst_wct_fuse", "short"): (-3, "wct_fuse: workspace 717239 < 717240 bytes"),
+    ("rpst_wct_params", "null"): (-1, "wct_params: null pointer"),
+    ("rpst_wct_params", "n=0"): (-1, "wct_params: bad shape n=0 C=16 HW=64"),
+    ("rpst_wct_params", "HW=1"): (-1, "wct_params: bad shape n=2 C=16 HW=1"),
+    ("rpst_wct_params", "C=1025"): (-1, "wct_params: C=1025 > 1024"),
+    ("rpst_wct_params", "short"): (-3, "wct_params: workspace 717239 < 717240 bytes"),
+    ("rpst_whiten_and_color_f64", "null"): (-1, "whiten_and_color: null pointer"),
+    ("rpst_whiten_and_color_f64", "HW=1"): (-1, "whiten_and_color: bad shape"),
+    ("rpst_whiten_and_color_f64", "C=1025"): (-1, "whiten_and_color: bad shape"),
+    ("rpst_whiten_and_color_f64", "short"): (-3, "whiten_and_color: workspace too small"),
+    ("rpst_whiten_and_color_original_f64", "null"):
+        (-1, "whiten_and_color(original): null pointer"),
+    ("rpst_whiten_and_color_original_f64", "HW=1"): (-1, "whiten_and_color(original): bad shape"),
+    ("rpst_whiten_and_color_original_f64", "C=1025"):
+        (-1, "whiten_and_color(original): bad shape"),
+    ("rpst_whiten_and_color_original_f64", "short"):
+        (-3, "whiten_and_color(original): workspace too small"),
+    ("rpst_wct_status", "null"): (-1, "wct_status: null pointer"),
+    ("rpst_wct_status", "n=0"): (-1, "wct_status: bad shape"),
+    ("rpst_wct_status", "HW=1"): (-1, "wct_status: bad shape"),
+    ("rpst_wct_status", "C=1025"): (-1, "wct_status: bad shape"),
+    ("rpst_whiten_and_color_status", "null"): (-1, "whiten_and_color_status: null pointer"),
+    ("rpst_whiten_and_color_status", "HW=1"): (-1, "whiten_and_color_status: bad shape"),
+    ("rpst_whiten_and_color_status", "C=1025"): (-1, "whiten_and_color_status: bad shape"),
+    ("rpst_matrix_power_psd_f64", "null"): (-1, "matrix_power: null pointer"),
+    ("rpst_matrix_power_psd_f64", "n=0"): (-1, "matrix_power: bad shape"),
+    ("rpst_matrix_power_psd_f64", "C=1025"): (-1, "matrix_power: bad shape"),
+    ("rpst_matrix_power_psd_f64", "short"): (-3, "matrix_power: workspace too small"),
+}
+WCT_DEFECTS = {"null": {"first": None}, "n=0": {"n": 0}, "HW=1": {"HW": 1}, "C=1025": {"C": 1025},
+               "short": {"short": 1}}
+
+
+@pytest.mark.parametrize("entry,defect", list(WCT_ERRORS))
+def test_wct_entry_argument_errors(entry, defect):
+    """Every WCT entry point answers a null pointer, a bad shape (n = 0, HW = 1, C = 1025: for
+    rpst_matrix_power_psd_f64 a zero batch and a 1025 x 1025 matrix) and a workspace one byte
+    short with its own status code and message, before any launch (no GPU needed)."""
+    lib = _lib.load()
+    status, message = WCT_ERRORS[(entry, defect)]
+    assert getattr(lib, entry)(*_wct_entry_args(entry, **WCT_DEFECTS[defect])) == status
+    error = lib.rpst_last_error().decode()
+    assert error == message
+    assert error.startswith(entry[len("rpst_"):].replace("_f64", "").replace(
+        "_original", "(original)").replace("_psd", "") + ":")
+
+
 @pytest.mark.parametrize("args,msg", [
     ((None, None, None, None, None, None, 1, 3, 8, 8, 16, 3, 0, 0, 1, None), "null pointer"),
     ((1, None, 1, None, None, 1, 1, 3, 8, 8, 16, 5, 0, 0, 1, None), "ksize"),

@@ -53,10 +53,11 @@ def main():
     recs = []
     for name, C, side in SHAPES:
         hw = side * side
-        c = torch.stack([torch.from_numpy(synth.conditioned_features(960 + i % 4, C, hw, 1.5))
-                         for i in range(n)]).float().view(n, C, side, side).to(dev)
-        s = torch.stack([torch.from_numpy(synth.conditioned_features(970 + i % 4, C, hw, 2.5))
-                         for i in range(n)]).float().view(n, C, side, side).to(dev)
+        # image i is the i % 4-th of four distinct ones (generated once each)
+        four = [[torch.from_numpy(synth.conditioned_features(seed + i, C, hw, dec)).float()
+                 for i in range(min(n, 4))] for seed, dec in ((960, 1.5), (970, 2.5))]
+        c, s = (torch.stack([f[i % 4] for i in range(n)]).view(n, C, side, side).to(dev)
+                for f in four)
         t_par = timed(lambda: ops.wct_params(c, s))
         t_fuse = timed(lambda: ops.wct_fuse(c, s))
         cov = 2.0 * C * (C + 1) * hw * n

@@ -10,7 +10,8 @@ entry point's name and its non-pointer arguments (a pointer is logged as null / 
 runs the case under ops.TRACE on seeded inputs and saves, with torch.save, the output tensors
 (test() outputs, or losses and every parameter gradient), the call log and TRACE.summary().
 A case passes when the tensors are torch.equal, the call logs are identical and the trace
-summaries have the same keys, launches, FLOPs and bytes. COVERAGE lists the entry points the
+summaries have the same keys, launches, FLOPs and bytes. The ops.* cases build no model: they run
+one rpst.ops function on seeded features at each listed shape and save every output. COVERAGE lists the entry points the
 parent's logs must reach over all cases. Reads nothing outside the two trees; exit status 0
 only if every case passes and the coverage is complete.
 """
@@ -25,7 +26,9 @@ import sys
 COVERAGE = """rpst_conv2d rpst_conv2d_ws rpst_conv2d_pair rpst_conv2d_pool rpst_conv2d_masked
 rpst_conv2d_skip_adain rpst_conv2d_stats rpst_conv2d_stats_store rpst_conv2d_mix rpst_conv2d_gated
 rpst_conv7 rpst_maxpool2x2_ceil rpst_upsample_nearest2x rpst_conv_wgrad_pad rpst_conv7_wgrad
-rpst_conv1x1_wgrad rpst_reflect_pad_border_grad_masked rpst_reflect_pad_backward""".split()
+rpst_conv1x1_wgrad rpst_reflect_pad_border_grad_masked rpst_reflect_pad_backward rpst_wct_fuse
+rpst_wct_params rpst_whiten_and_color_f64 rpst_whiten_and_color_original_f64
+rpst_matrix_power_psd_f64""".split()
 
 RP = {"rp_blocks": 5, "hidden_dim": 16, "content_weight": 1.0, "style_weight": 10.0,
       "resume": False, "use_mask": False}
@@ -37,7 +40,9 @@ SA = {"content_weight": 1.0, "style_weight": 3.0, "l_identity1_weight": 50.0,
 SOURCE = {"use_mask": False, "content_weight": 1.0, "style_weight": 10.0}
 
 # case -> (model class, (config, arguments after the VGG..), what runs, environment);
-# what: "test", "test_mask" (label maps at feat x feat), "forward_nograd" or an rpst.autograd entry
+# what: "test", "test_mask" (label maps at feat x feat), "forward_nograd", an rpst.autograd entry,
+# or "ops:<name>": no model, OPS[name] on each item of the arguments (the smallest shapes that
+# reach each branch of the WCT entry points)
 CASES = {
     "adain.test": ("AdaINRPNet", (RP,), "test", {}),
     "adain.test.unfused": ("AdaINRPNet", (RP,), "test", {"RPST_FUSE_ADAIN": "0"}),
@@ -67,8 +72,86 @@ CASES = {
     "source.losses": ("SourceNet", (SOURCE,), "sourcenet_losses", {}),
     "multiscale.losses": ("MultiScaleAdaINRPNet", (MS,), "multiscale_losses", {}),
     "ld.losses": ("LDMSAdaINRPNet", (LD,), "ld_losses", {}),
+    # (n, C, h, w): NB 4 scalar loads | scalar | NB 8 16-B loads | 16-wave | 16-wave, C % 16 != 0,
+    # scalar | tiled SYRK, 128 tiles, one partial | tiled, scalar | HW = 8192: two K splits
+    "ops.wct_fuse": (None, ((3, 16, 5, 7), (1, 64, 33, 31), (2, 128, 16, 24), (2, 256, 16, 16),
+                            (1, 200, 9, 13), (1, 320, 16, 16), (1, 272, 9, 13),
+                            (1, 320, 64, 128)), "ops:wct_fuse", {}),
+    "ops.wct_fuse.t_f64": (None, ((2, 128, 16, 24),), "ops:wct_fuse", {"RPST_WCT_T_F64": "1"}),
+    # (n, C, h, w, means given): the last one widens the means for the tiled SYRK
+    "ops.wct_params": (None, ((2, 64, 24, 40, False), (2, 64, 24, 40, True),
+                              (1, 320, 16, 16, True)), "ops:wct_params", {}),
+    # (method, C, HW): 64 tiles scalar | 128 tiles, one partial | two K splits | Li et al.
+    "ops.whiten_and_color": (None, (("closed-form", 64, 1023), ("closed-form", 160, 352),
+                                    ("closed-form", 64, 8192), ("original", 64, 352)),
+                             "ops:whiten_and_color", {}),
+    # a PSD batch (Newton-Schulz) and one indefinite symmetric matrix (the Jacobi route)
+    "ops.matrix_power_psd": (None, (("psd", 3, 96), ("indefinite", 1, 40)),
+                             "ops:matrix_power_psd", {}),
+    # (n, Cin, h, w, Cout): T x + c materialised (wct_apply_f32) | folded into the weights
+    "ops.conv2d_mix": (None, ((2, 8, 9, 13, 32), (1, 16, 12, 20, 32)), "ops:conv2d_mix", {}),
 }
 SHAPE = (2, 3, 64, 64)
+
+
+def features(seed: int, n: int, C: int, hw: int, dead=None):
+    """(n, C, hw) fp64 conditioned features, one seed per image; channel `dead` zeroed."""
+    import numpy as np
+    import torch
+    from rpst import synth
+    x = np.stack([synth.conditioned_features(seed + i, C, hw) for i in range(n)])
+    if dead is not None:
+        x[:, dead] = 0.0
+    return torch.from_numpy(x)
+
+
+def run_ops(name: str, items, dev) -> dict:
+    """Every output of rpst.ops.<name> on each item's seeded inputs (one dead style channel)."""
+    import torch
+    from rpst import ops, synth
+    out = {}
+
+    def pair(n, C, h, w):
+        return (features(10, n, C, h * w).float().reshape(n, C, h, w).to(dev),
+                features(20, n, C, h * w, dead=3).float().reshape(n, C, h, w).to(dev))
+
+    for item in items:
+        if name == "wct_fuse":
+            c, s = pair(*item)
+            res = ops.wct_fuse(c, s, status=True) + ops.wct_params(c, s, status=True)
+            keys = ("out", "status", "T", "offset", "residual", "params status")
+        elif name == "wct_params":
+            c, s = pair(*item[:4])
+            means = torch.cat([c.double().mean((2, 3)), s.double().mean((2, 3))]).float()
+            res = ops.wct_params(c, s, means if item[4] else None, status=True)
+            keys = ("T", "offset", "residual", "status")
+        elif name == "whiten_and_color":
+            method, C, hw = item
+            res = ops.whiten_and_color(features(30, 1, C, hw)[0].to(dev),
+                                       features(40, 1, C, hw, dead=3)[0].to(dev), method, status=True)
+            keys = ("out", "status")
+        elif name == "matrix_power_psd":
+            kind, batch, n = item
+            x = features(50, batch, n, 2 * n)
+            A = x @ x.transpose(1, 2) / (2 * n)
+            if kind == "indefinite":  # symmetric, eigenvalues of both signs
+                A = A - torch.eye(n, dtype=A.dtype) * A.diagonal(dim1=1, dim2=2).mean()
+            else:  # well inside the Newton-Schulz route
+                A = A + 0.01 * torch.eye(n, dtype=A.dtype)
+            res = tuple(ops.matrix_power_psd(A.to(dev), p) for p in (0.5, -0.5))
+            keys = ("sqrt", "inv_sqrt")
+        elif name == "conv2d_mix":
+            n, cin, h, w, cout = item
+            x, s = pair(n, cin, h, w)
+            T, c, _ = ops.wct_params(x, s)
+            wgt = torch.from_numpy(synth.conv_param(60, "mix.weight", (cout, cin, 3, 3))).to(dev)
+            bias = torch.from_numpy(synth.conv_param(60, "mix.bias", (cout,))).to(dev)
+            res = (T, c, ops.conv2d_mix(x, T, c, ops.pack_conv_weight(wgt), bias, cout, 3))
+            keys = ("T", "offset", "out")
+        else:
+            raise KeyError(name)
+        out.update({f"{item} {k}": v for k, v in zip(keys, res)})
+    return out
 
 
 def child(root: str, case: str, out_path: str) -> None:
@@ -82,9 +165,10 @@ def child(root: str, case: str, out_path: str) -> None:
     assert os.path.realpath(_lib.LIB_PATH).startswith(os.path.realpath(root)), _lib.LIB_PATH
     cls, args, what, _ = CASES[case]
     dev = torch.device("cuda:0")
-    model = getattr(net, cls)(*copy.deepcopy(args[:1]), copy.deepcopy(net.vgg), *args[1:])
-    synth.synth_module_(model, 7)
-    model = model.to(dev)
+    if cls is not None:
+        model = getattr(net, cls)(*copy.deepcopy(args[:1]), copy.deepcopy(net.vgg), *args[1:])
+        synth.synth_module_(model, 7)
+        model = model.to(dev)
     c = torch.from_numpy(synth.image(1, SHAPE)).to(dev)
     s = torch.from_numpy(synth.image(2, SHAPE)).to(dev)
 
@@ -99,7 +183,9 @@ def child(root: str, case: str, out_path: str) -> None:
     _lib.call = logged_call
     ops.TRACE = ops.Trace()
     tensors = {}
-    if what == "test":
+    if what.startswith("ops:"):
+        tensors.update(run_ops(what[4:], args, dev))
+    elif what == "test":
         tensors["out"] = model.test(c, s)
     elif what.startswith("test_mask"):
         side = int(what.split(":")[1])
