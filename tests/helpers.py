@@ -1,4 +1,7 @@
-"""Shared test helpers: model construction with synthetic weights, tolerances."""
+"""Shared test helpers: tolerances, golden sets, the kernel tests' inputs, networks built from
+golden cases, mask arguments, the fused / op-by-op switch, the launch spy, and the dataset
+tree and shared body of the stylize pipeline tests."""
+import contextlib
 import os
 
 import numpy as np
@@ -92,6 +95,168 @@ def synth_(model, seed):
 
 def state_dict_of(model):
     return {k: v.detach().cpu() for k, v in model.state_dict().items()}
+
+
+# ---- inputs ---------------------------------------------------------------------------------
+def gen(seed, shape, scale=1.0, offset=0.0, relu=False):
+    """Uniform [-1, 1) values from torch's CPU generator, scaled and shifted (then clamped at 0
+    with relu): the kernel tests' inputs."""
+    g = torch.Generator().manual_seed(seed)
+    x = (torch.rand(shape, generator=g) * 2 - 1) * scale + offset
+    return x.clamp_min(0) if relu else x
+
+
+def t(a):
+    return torch.from_numpy(np.ascontiguousarray(a))
+
+
+def dev(a, cuda):
+    return t(a).to(cuda)
+
+
+def use_conv_algo(monkeypatch, param, w4q=False):
+    """The environment of one conv_algo fixture parameter: librpst reads RPST_CONV_ALGO per
+    launch, and with w4q RPST_W4Q too ('winograd4_32' keeps every F(4x4) layer on the
+    32-channel kernel, 'winograd4q' forces the position-quarter kernel, the rest run the
+    production rule). Returns param."""
+    monkeypatch.setenv("RPST_CONV_ALGO",
+                       {"winograd4_32": "winograd4", "winograd4q": "winograd4"}.get(param, param))
+    if w4q:
+        monkeypatch.setenv("RPST_W4Q", {"winograd4_32": "0", "winograd4q": "2"}.get(param, "1"))
+    return param
+
+
+# ---- networks from golden cases -------------------------------------------------------------
+def golden_net(cls, cfg, g, key, device=None, seed=None):
+    """cls(cfg, a copy of the VGG) with the synthetic weights of the golden entry `key`
+    (g[key + 'seed'], checked against g[key + 'checksum']), or of `seed` instead (then nothing
+    is checked); moved to `device` when one is given."""
+    import copy
+
+    import network as net
+    m = cls(cfg, copy.deepcopy(net.vgg))
+    ck = synth_(m, int(g[key + "seed"]) if seed is None else seed)
+    if seed is None:
+        assert np.array_equal(ck, g[key + "checksum"]), key
+    return m if device is None else m.to(device)
+
+
+def check_net(y, ref, what):
+    err, mx = rel_l2(y, ref), max_abs_ratio(y, ref)
+    print(f"{what}: rel-L2 {err:.3e} max-abs {mx:.3e}")
+    assert err < TOL_NET and mx < TOL_NET_MAXABS, (what, err, mx)
+
+
+def mask_kw(g, key, cuda, tmp_path=None, mode="L", name="{tag}{b}.png"):
+    """The test() mask arguments of the masked golden entry `key` ({} where g[key + 'use_mask']
+    is recorded and False): the label maps as tensors at the image size (the reference's own
+    resize of its files: g[key + 'cseg'] / 'sseg'), or, with tmp_path, the mask files
+    themselves (g[key + 'cfile'] / 'sfile') written there in PNG mode `mode` under `name`."""
+    if key + "use_mask" in g and not bool(g[key + "use_mask"]):
+        return {}
+    if tmp_path is None:
+        return dict(c_mask_path=dev(g[key + "cseg"].astype(np.uint8), cuda),
+                    s_mask_path=dev(g[key + "sseg"].astype(np.uint8), cuda))
+    import masked_ref as M
+
+    def paths(tag, files):
+        return [M.write_mask_png(str(tmp_path / name.format(tag=tag, mode=mode, b=b)), files[b],
+                                 mode) for b in range(files.shape[0])]
+    return dict(c_mask_path=paths("c", g[key + "cfile"]), s_mask_path=paths("s", g[key + "sfile"]))
+
+
+# ---- switches and spies ---------------------------------------------------------------------
+@contextlib.contextmanager
+def unfused(module, attr):
+    """The op-by-op path: module.attr (FUSED_ADAIN, FUSED, FUSED_WCT) False inside the block,
+    the value it had put back after."""
+    was = getattr(module, attr)
+    setattr(module, attr, False)
+    try:
+        yield
+    finally:
+        setattr(module, attr, was)
+
+
+def traced_launches(fn):
+    """Run fn() under rpst.ops.TRACE and a torch.cat spy -> (launch names, the operand shapes of
+    every torch.cat call); both hooks are taken out again, also when fn raises."""
+    from rpst import ops
+    cats = []
+    real_cat, was = torch.cat, ops.TRACE
+
+    def spy(tensors, *a, **k):
+        cats.append([tuple(x.shape) for x in tensors])
+        return real_cat(tensors, *a, **k)
+
+    ops.TRACE = ops.Trace()
+    torch.cat = spy
+    try:
+        fn()
+        names = [r[0] for r in ops.TRACE.records]
+    finally:
+        torch.cat = real_cat
+        ops.TRACE = was
+    return names, cats
+
+
+# ---- the stylize pipeline -------------------------------------------------------------------
+def dataset_tree(root, size, mask_size, modes, rng_seed, mask_seed0, masks=True):
+    """Pairs content/in<k>.png, style/tar<k>.png (size x size, uniform bytes from
+    default_rng(rng_seed), content before style) with labelme_segmentation/<stem>.png
+    (blocks_mask seed mask_seed0 + k, PNG mode modes[k]); without masks both images of pair k
+    are named p<k>.png and no mask is written."""
+    from PIL import Image
+
+    import masked_ref as M
+    rng = np.random.default_rng(rng_seed)
+    for d in ("content", "style") + (("labelme_segmentation",) if masks else ()):
+        os.makedirs(os.path.join(root, d), exist_ok=True)
+    for k, mode in enumerate(modes):
+        for d, stem in (("content", f"in{k}"), ("style", f"tar{k}")):
+            a = rng.integers(0, 256, size=(size, size, 3), dtype=np.uint8)
+            Image.fromarray(a, "RGB").save(
+                os.path.join(root, d, (stem if masks else f"p{k}") + ".png"))
+            if masks:
+                M.write_mask_png(os.path.join(root, "labelme_segmentation", stem + ".png"),
+                                 M.blocks_mask(mask_size, mask_size, [0, 60, 120, 180],
+                                               mask_seed0 + k), mode)
+
+
+def check_pipeline(cfg, tmp_path, cuda, pairs=2):
+    """stylize.main on cfg (plus output = tmp_path / 'out', written as YAML) with
+    --synthetic-weights 5: every PNG it writes is the direct test() call's on the same pair
+    through the pipeline's own uint8 conversion, beside a -cat.png. cfg holds test_dir,
+    test_dataset, img_size and use_mask. Returns the rebuilt network and, per pair,
+    (content, style, the uint8 image)."""
+    import yaml
+    from PIL import Image
+
+    import stylize
+    from rpst.imageio import DATASETS, load_image, to_tensor, to_uint8
+    cfg = dict(cfg, output=str(tmp_path / "out"))
+    cfg_path = str(tmp_path / "cfg.yaml")
+    with open(cfg_path, "w") as f:
+        yaml.safe_dump(cfg, f)
+    assert stylize.main(["--config", cfg_path, "--synthetic-weights", "5"]) == 0
+    m = stylize.build_network(cfg, synthetic_seed=5).to(cuda)
+    ds = DATASETS[cfg["test_dataset"]](cfg["test_dir"])
+    assert len(ds) == pairs
+    size = cfg["img_size"]
+    out_dir = tmp_path / "out" / "test" / "test_output"
+    items = []
+    for i in range(len(ds)):
+        cp, sp, cn, sn, cm, sm = ds.item(i)
+        c = to_tensor(dev(load_image(cp, size)[None], cuda))
+        s = to_tensor(dev(load_image(sp, size)[None], cuda))
+        kw = dict(c_mask_path=[cm], s_mask_path=[sm]) if cfg["use_mask"] else {}
+        ref = to_uint8(m.test(c, s, **kw))[0].cpu().numpy()
+        got = np.asarray(Image.open(out_dir / f"{cn}-{sn}.png"))
+        assert got.shape == (size, size, 3)
+        assert np.array_equal(got, ref), (cn, sn)
+        assert (out_dir / f"{cn}-{sn}-cat.png").exists()
+        items.append((c, s, ref))
+    return m, items
 
 
 def rp_config(hidden, blocks=5):

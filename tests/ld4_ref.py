@@ -42,6 +42,12 @@ def config(hidden, layers, inception=0, stylized_layers=None, use_mask=False):
     return cfg
 
 
+def golden_config(g, i):
+    """The config of case i of tests/golden/ld4*.npz."""
+    return config(int(g[f"net{i}_hidden"]), int(g[f"net{i}_layers"]), int(g[f"net{i}_inception"]),
+                  int(g[f"net{i}_stylized_layers"]), bool(g[f"net{i}_use_mask"]))
+
+
 def level_bytes(hidden, layers, shape):
     n, _, h, w = shape
     return 8 * layers * n * 2 * hidden * h * w
@@ -62,16 +68,16 @@ def resize_nearest(x, size):
 
 def big(x, sd, prefix):
     """A coarse-chain level from its state_dict entries under `prefix` (Sequential indices 0, 2
-    and 5 hold the convs), float64."""
-    y = F.conv2d(x, L._d(sd[prefix + "0.weight"]), L._d(sd[prefix + "0.bias"]))
+    and 5 hold the convs), in x's dtype."""
+    y = F.conv2d(x, sd[prefix + "0.weight"], sd[prefix + "0.bias"])
     for j in (2, 5):
-        y = torch.relu(L.conv_pad(y, L._d(sd[f"{prefix}{j}.weight"]), L._d(sd[f"{prefix}{j}.bias"])))
+        y = torch.relu(L.conv_pad(y, sd[f"{prefix}{j}.weight"], sd[f"{prefix}{j}.bias"]))
     return F.max_pool2d(y, 2, 2, ceil_mode=True)
 
 
 def encode(x, sd, layers):
     fine = coarse = L._d(x)
-    feats = []
+    sd, feats = L.rp64(sd), []
     for i in range(layers):
         fine = L.block(fine, sd, f"rp_enc{i}_small_revf.")
         coarse = big(coarse, sd, f"rp_enc{i}_big_revf.")
@@ -80,6 +86,7 @@ def encode(x, sd, layers):
 
 
 def decode(cfs, sfs, sd, c_segs=None, s_segs=None):
+    sd = L.rp64(sd)
     if c_segs is not None:
         import masked_ref as M
 

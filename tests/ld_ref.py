@@ -42,6 +42,12 @@ def config(hidden, layers, inception=0, use_mask=False):
             "ld_layer_num": layers}
 
 
+def golden_config(g, i):
+    """The config of case i of tests/golden/ld.npz."""
+    return config(int(g[f"net{i}_hidden"]), int(g[f"net{i}_layers"]), int(g[f"net{i}_inception"]),
+                  bool(g[f"net{i}_use_mask"]))
+
+
 def _d(a):
     return torch.as_tensor(np.asarray(a) if not torch.is_tensor(a) else a).double()
 
@@ -54,13 +60,19 @@ def conv_pad(x, w, b, pad_mode="reflect"):
     return F.conv2d(x, w, b)
 
 
-def block(x, sd, prefix):
-    """A Conv2dBlock from its state_dict entries under `prefix`, float64."""
-    y = conv_pad(x, _d(sd[prefix + "conv.weight"]), _d(sd[prefix + "conv.bias"]))
+def rp64(sd):
+    """The rp_enc* / rp_dec* entries of a state_dict as float64 tensors (the frozen VGG is not
+    part of inference)."""
+    return {k: _d(v) for k, v in sd.items() if k.startswith("rp_")}
+
+
+def block(x, sd, prefix, pad_mode="reflect"):
+    """A Conv2dBlock from its state_dict entries under `prefix`, in x's dtype (sd in the same
+    dtype): pad k // 2, conv, the 1x1 inception convs, LeakyReLU(0.2) once at the end."""
+    y = conv_pad(x, sd[prefix + "conv.weight"], sd[prefix + "conv.bias"], pad_mode)
     j = 0
     while f"{prefix}inception.{j}.0.weight" in sd:
-        y = F.conv2d(y, _d(sd[f"{prefix}inception.{j}.0.weight"]),
-                     _d(sd[f"{prefix}inception.{j}.0.bias"]))
+        y = F.conv2d(y, sd[f"{prefix}inception.{j}.0.weight"], sd[f"{prefix}inception.{j}.0.bias"])
         j += 1
     return torch.where(y > 0, y, 0.2 * y)
 
@@ -78,8 +90,9 @@ def adain(a, b):
     return (a - ma) / sa * sb + mb
 
 
-def encode(x, sd, layers):
-    feats, x = [], _d(x)
+def levels(x, sd, layers):
+    """The encoder levels of x, in x's dtype (sd in the same dtype)."""
+    feats = []
     for i in range(layers):
         x = torch.cat([block(x, sd, f"rp_enc{i}_small_revf."),
                        block(x, sd, f"rp_enc{i}_big_revf.")], dim=1)
@@ -87,7 +100,12 @@ def encode(x, sd, layers):
     return feats
 
 
+def encode(x, sd, layers):
+    return levels(_d(x), rp64(sd), layers)
+
+
 def decode(cfs, sfs, sd, c_segs=None, s_segs=None):
+    sd = rp64(sd)
     if c_segs is not None:
         import masked_ref as M
         y = block(M._fuse(cfs[-1], sfs[-1], c_segs, s_segs), sd, "rp_dec0.")

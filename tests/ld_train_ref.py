@@ -2,7 +2,7 @@
 caller's dtype, written from the formulas of tests/ld_ref.py (not from the reference's
 modules), for the ld_adain training tests and their goldens (tests/golden/grads_ld*.npz).
 
-    cfs, sfs = levels(content), levels(style)            ld_ref: cat([small_i, big_i])
+    cfs, sfs = levels(content), levels(style)            ld_ref.levels: cat([small_i, big_i])
     y = dec_0(AdaIN(c_{L-1}, s_{L-1}))
     y = dec_j(y + AdaIN(y, s_{L-1-j}))                    j = 1 .. L-1
     losses   = style loss at VGG relu1_1..relu4_1 of y against the style's, content loss of
@@ -12,8 +12,8 @@ Only the top level's content features reach the loss; the lower content levels f
 the level above them only. grads() differentiates total_loss w.r.t. every rp_enc* / rp_dec*
 tensor with the VGG frozen.
 """
+
 import torch
-import torch.nn.functional as F
 
 import ld_ref as L
 from oracle import restate as R
@@ -37,32 +37,12 @@ def golden_config(g, i):
                   float(g[f"cw{i}"]), float(g[f"sw{i}"]))
 
 
-def block(x, sd, prefix, pad_mode="reflect"):
-    """A Conv2dBlock from its state_dict entries under `prefix`, in x's dtype: pad k // 2,
-    conv, the 1x1 inception convs, LeakyReLU(0.2) once at the end."""
-    y = L.conv_pad(x, sd[prefix + "conv.weight"], sd[prefix + "conv.bias"], pad_mode)
-    j = 0
-    while f"{prefix}inception.{j}.0.weight" in sd:
-        y = F.conv2d(y, sd[f"{prefix}inception.{j}.0.weight"], sd[f"{prefix}inception.{j}.0.bias"])
-        j += 1
-    return torch.where(y > 0, y, 0.2 * y)
-
-
-def levels(x, sd, layers):
-    feats = []
-    for i in range(layers):
-        x = torch.cat([block(x, sd, f"rp_enc{i}_small_revf."),
-                       block(x, sd, f"rp_enc{i}_big_revf.")], dim=1)
-        feats.append(x)
-    return feats
-
-
 def losses(content, style, sd, layers, content_weight, style_weight):
     """The loss dict of LDMSAdaINRPNet.forward in content's dtype (sd in the same dtype)."""
-    cfs, sfs = levels(content, sd, layers), levels(style, sd, layers)
-    y = block(L.adain(cfs[-1], sfs[-1]), sd, "rp_dec0.")
+    cfs, sfs = L.levels(content, sd, layers), L.levels(style, sd, layers)
+    y = L.block(L.adain(cfs[-1], sfs[-1]), sd, "rp_dec0.")
     for j, sf in enumerate(sfs[:-1][::-1]):
-        y = block(y + L.adain(y, sf), sd, f"rp_dec{j + 1}.")
+        y = L.block(y + L.adain(y, sf), sd, f"rp_dec{j + 1}.")
     with torch.no_grad():
         c4 = R.encode_with_intermediate(content, sd)[-1]
     return R._vgg_losses(y, style, c4, sd, content_weight, style_weight)

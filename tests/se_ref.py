@@ -16,12 +16,17 @@ import numpy as np
 import torch
 import torch.nn.functional as F
 
+from ld_ref import _d, key_table  # noqa: F401  (one definition each, shared)
+
 EPS = 1e-5
 PREFIX = "blk.attention_block."  # rpst.synth's SE rules apply to keys holding '.attention_block.'
 
 
-def _d(a):
-    return torch.as_tensor(np.asarray(a) if not torch.is_tensor(a) else a).double()
+def golden_config(g, i):
+    """The MultiScaleAdaINRPNet config of network case i of tests/golden/se.npz."""
+    from helpers import multiscale_config
+    return dict(multiscale_config(int(g[f"net{i}_hidden"]), int(g[f"net{i}_blocks"]), 0),
+                attention="se", use_mask=bool(g[f"net{i}_use_mask"]))
 
 
 def batchnorm(y, sd, name):
@@ -87,12 +92,3 @@ def synth_block_(block, seed):
     new = synth.synth_state_dict(shapes, seed)
     block.load_state_dict({k[len(PREFIX):]: torch.from_numpy(v) for k, v in new.items()})
     return np.array(synth.checksum(new))
-
-
-def key_table(sd):
-    """state_dict -> (names as a unicode array, shapes as int64 (K, 4), padded with -1)."""
-    names = np.array(list(sd.keys()))
-    shapes = np.full((len(names), 4), -1, dtype=np.int64)
-    for i, v in enumerate(sd.values()):
-        shapes[i, :len(v.shape)] = tuple(v.shape)
-    return names, shapes

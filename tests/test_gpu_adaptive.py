@@ -12,26 +12,16 @@ Network tests therefore compare against the float64 oracle with the tolerance
 max(TOL_NET, 3 x the fp32 reference's own distance to it) — `_cond_tol`."""
 import copy
 
-import numpy as np
 import pytest
 import torch
 import torch.nn.functional as Fn
 
-from helpers import TOL_NET, TOL_NET_MAXABS, max_abs_ratio, rel_l2, state_dict_of, synth_
+from helpers import (TOL_NET, TOL_NET_MAXABS, gen, max_abs_ratio, rel_l2, state_dict_of, synth_,
+                     t)
 from oracle import restate as R
 
 pytestmark = pytest.mark.gpu
 MODES = ("aea", "relu")
-
-
-def t(a):
-    return torch.from_numpy(np.ascontiguousarray(a))
-
-
-def gen(seed, shape, scale=1.0, offset=0.0, relu=False):
-    g = torch.Generator().manual_seed(seed)
-    x = (torch.rand(shape, generator=g) * 2 - 1) * scale + offset
-    return x.clamp_min(0) if relu else x
 
 
 def test_affinity_golden(cuda, golden):

@@ -17,9 +17,9 @@ import functools
 import pytest
 import torch
 
-from helpers import rel_l2
+from helpers import gen, rel_l2
 from oracle import restate as R
-from test_gpu_kernels import _conv_ref, gen
+from test_gpu_kernels import _conv_ref
 
 pytestmark = pytest.mark.gpu
 

@@ -10,19 +10,11 @@ import numpy as np
 import pytest
 import torch
 
-from helpers import TOL_NET, TOL_NET_MAXABS, TOL_STATS, max_abs_ratio, rel_l2, rp_config, synth_
+from helpers import (TOL_NET, TOL_NET_MAXABS, TOL_STATS, gen, max_abs_ratio, rel_l2, rp_config,
+                     synth_, t, unfused, use_conv_algo)
 from oracle import restate as R
 
 pytestmark = pytest.mark.gpu
-
-
-def t(a):
-    return torch.from_numpy(np.ascontiguousarray(a))
-
-
-def gen(seed, shape, scale=1.0, offset=0.0):
-    g = torch.Generator().manual_seed(seed)
-    return (torch.rand(shape, generator=g) * 2 - 1) * scale + offset
 
 
 # ---- a1/a2/a10 ----------------------------------------------------------------------
@@ -166,12 +158,7 @@ def conv_algo(request, monkeypatch):
     128), winograd4_32 keeps every F(4x4) layer on the 32-channel kernel (RPST_W4Q=0) and
     winograd4q forces the position-quarter kernel on every shape it supports (RPST_W4Q=2:
     Cin >= 16, Cin % 16 == 0, Cout >= 64)."""
-    algo = {"winograd4_32": "winograd4", "winograd4q": "winograd4"}.get(request.param,
-                                                                        request.param)
-    monkeypatch.setenv("RPST_CONV_ALGO", algo)
-    monkeypatch.setenv("RPST_W4Q", {"winograd4_32": "0", "winograd4q": "2"}.get(request.param,
-                                                                               "1"))
-    return request.param
+    return use_conv_algo(monkeypatch, request.param, w4q=True)
 
 
 @pytest.mark.parametrize("case", CONV_CASES)
@@ -653,9 +640,6 @@ def test_adain_rp_fused_equals_unfused(cuda):
     c = torch.from_numpy(synth.image(1, (2, 3, 48, 64))).to(cuda)
     s = torch.from_numpy(synth.image(2, (2, 3, 48, 64))).to(cuda)
     fused = m.test(c, s)
-    arp.FUSED_ADAIN = False
-    try:
+    with unfused(arp, "FUSED_ADAIN"):
         plain = m.test(c, s)
-    finally:
-        arp.FUSED_ADAIN = True
     assert rel_l2(fused, plain) < 1e-5

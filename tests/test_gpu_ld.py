@@ -9,30 +9,19 @@ to float64) -- 1e-5 is the project's per-conv bar; the second term is the refere
 arithmetic's own fp32 distance at K = Cin * 49, which is longer than any K the 3x3 kernels
 see. TOL_NET / TOL_NET_MAXABS end to end (tests/helpers.py)."""
 import copy
-import os
 
-import numpy as np
 import pytest
 import torch
 import torch.nn.functional as F
 
 import ld_ref as L
-import masked_ref as M
-from helpers import TOL_NET, TOL_NET_MAXABS, max_abs_ratio, rel_l2, synth_
+from helpers import (TOL_NET, TOL_NET_MAXABS, check_pipeline, dataset_tree, dev, gen, golden_net,
+                     mask_kw, max_abs_ratio, rel_l2, synth_, traced_launches, unfused)
 
 pytestmark = pytest.mark.gpu
 
 REFLECT, ZERO = 1, 0
 NONE, RELU, LRELU = 0, 1, 2
-
-
-def _dev(a, cuda):
-    return torch.from_numpy(np.ascontiguousarray(a)).to(cuda)
-
-
-def gen(seed, shape, scale=1.0, offset=0.0):
-    g = torch.Generator().manual_seed(seed)
-    return (torch.rand(shape, generator=g) * 2 - 1) * scale + offset
 
 
 def _act64(y, act):
@@ -193,30 +182,9 @@ def test_plan_runs_7x7_steps(cuda):
 
 
 # ---- the network --------------------------------------------------------------------------
-def _net(g, i, cuda, **over):
+def _net(g, i, cuda):
     import network as net
-    cfg = L.config(int(g[f"net{i}_hidden"]), int(g[f"net{i}_layers"]),
-                   int(g[f"net{i}_inception"]), bool(g[f"net{i}_use_mask"]))
-    cfg.update(over)
-    m = net.LDMSAdaINRPNet(cfg, copy.deepcopy(net.vgg))
-    assert np.array_equal(synth_(m, int(g[f"net{i}_seed"])), g[f"net{i}_checksum"])
-    return m.to(cuda)
-
-
-def _mask_kw(g, i, cuda, tmp_path=None):
-    """The masked case's label maps: as tensors at the image size (the reference's own resize
-    of its files), or, with tmp_path, as the mask files themselves."""
-    if not bool(g[f"net{i}_use_mask"]):
-        return {}
-    if tmp_path is None:
-        return dict(c_mask_path=_dev(g[f"net{i}_cseg"].astype(np.uint8), cuda),
-                    s_mask_path=_dev(g[f"net{i}_sseg"].astype(np.uint8), cuda))
-    n = g[f"net{i}_cfile"].shape[0]
-    return dict(
-        c_mask_path=[M.write_mask_png(str(tmp_path / f"c{b}.png"), g[f"net{i}_cfile"][b], "L")
-                     for b in range(n)],
-        s_mask_path=[M.write_mask_png(str(tmp_path / f"s{b}.png"), g[f"net{i}_sfile"][b], "L")
-                     for b in range(n)])
+    return golden_net(net.LDMSAdaINRPNet, L.golden_config(g, i), g, f"net{i}_", cuda)
 
 
 @pytest.mark.parametrize("i", range(len(L.CASES)))
@@ -224,8 +192,8 @@ def test_ld_test_matches_reference(cuda, golden, i, tmp_path):
     import network.adain_rp as arp
     g = golden("ld")
     m = _net(g, i, cuda)
-    c, s = _dev(g[f"net{i}_content"], cuda), _dev(g[f"net{i}_style"], cuda)
-    kw = _mask_kw(g, i, cuda)
+    c, s = dev(g[f"net{i}_content"], cuda), dev(g[f"net{i}_style"], cuda)
+    kw = mask_kw(g, f"net{i}_", cuda)
     y = m.test(c, s, **kw)
     assert m.training  # test() leaves the model in training mode, as the reference does
     ref = g[f"net{i}_out"]
@@ -236,13 +204,10 @@ def test_ld_test_matches_reference(cuda, golden, i, tmp_path):
     assert rel_l2(y, g[f"net{i}_out64"]) < TOL_NET
     assert torch.equal(y, m.test(c, s, **kw))
     if kw:  # from the mask files themselves (decoded and resized by rpst.imageio)
-        yf = m.test(c, s, **_mask_kw(g, i, cuda, tmp_path))
+        yf = m.test(c, s, **mask_kw(g, f"net{i}_", cuda, tmp_path))
         assert rel_l2(yf, ref) < TOL_NET and max_abs_ratio(yf, ref) < TOL_NET_MAXABS
-    arp.FUSED_ADAIN = False
-    try:
+    with unfused(arp, "FUSED_ADAIN"):
         plain = m.test(c, s, **kw)
-    finally:
-        arp.FUSED_ADAIN = True
     assert rel_l2(plain, ref) < TOL_NET
     assert rel_l2(y, plain) < 1e-5
     m.eval()
@@ -257,7 +222,7 @@ def test_ld_encoder_levels_match_reference(cuda, golden, i):
     g = golden("ld")
     m = _net(g, i, cuda)
     with torch.no_grad():
-        levels = m.encode_rp_intermediate(_dev(g[f"net{i}_content"], cuda))
+        levels = m.encode_rp_intermediate(dev(g[f"net{i}_content"], cuda))
     assert len(levels) == int(g[f"net{i}_layers"])
     for k, lv in enumerate(levels):
         ref = g[f"net{i}_level{k}_64"]
@@ -272,26 +237,11 @@ def test_ld_launch_sequence(cuda, golden):
     """The (16, 5) case: every 7x7 layer (32, 64, 128, 256 channels) is one conv7x7 launch
     over the [content; style] batch writing into the level tensor, and no level tensor comes
     from torch.cat."""
-    from rpst import ops
     g = golden("ld")
     m = _net(g, 2, cuda)
-    c, s = _dev(g["net2_content"], cuda), _dev(g["net2_style"], cuda)
+    c, s = dev(g["net2_content"], cuda), dev(g["net2_style"], cuda)
     m.test(c, s)  # warm: the packed weights are cached
-    cats = []
-    real_cat = torch.cat
-
-    def spy(tensors, *a, **k):
-        cats.append([tuple(t.shape) for t in tensors])
-        return real_cat(tensors, *a, **k)
-
-    ops.TRACE = ops.Trace()
-    torch.cat = spy
-    try:
-        m.test(c, s)
-        names = [r[0] for r in ops.TRACE.records]
-    finally:
-        torch.cat = real_cat
-        ops.TRACE = None
+    names, cats = traced_launches(lambda: m.test(c, s))
     k7 = [nm for nm in names if nm.startswith("conv7x7 ")]
     assert k7 == [f"conv7x7 {ch}->{ch} 16x20 N2" for ch in (32, 64, 128, 256)], names
     # the only concatenations are the AdaIN parameter vectors (1-D)
@@ -301,7 +251,7 @@ def test_ld_launch_sequence(cuda, golden):
 def test_ld_save_and_resume(cuda, golden, tmp_path):
     g = golden("ld")
     m = _net(g, 0, cuda)
-    c, s = _dev(g["net0_content"], cuda), _dev(g["net0_style"], cuda)
+    c, s = dev(g["net0_content"], cuda), dev(g["net0_style"], cuda)
     y = m.test(c, s)
     path = str(tmp_path / "1234.pth")
     m.save(path, 1234)
@@ -316,7 +266,7 @@ def test_ld_save_and_resume(cuda, golden, tmp_path):
 def test_ld_forward_losses(cuda, golden):
     g = golden("ld")
     m = _net(g, 0, cuda)
-    c, s = _dev(g["net0_content"], cuda), _dev(g["net0_style"], cuda)
+    c, s = dev(g["net0_content"], cuda), dev(g["net0_style"], cuda)
     with torch.no_grad():
         losses, total = m(c, s)
     assert set(losses) == {"style_loss", "content_loss", "total_loss"}
@@ -336,54 +286,16 @@ def test_ld_forward_losses(cuda, golden):
 
 
 # ---- pipeline -----------------------------------------------------------------------------
-def _tree(root, size, mask_size, modes, masks):
-    from PIL import Image
-    rng = np.random.default_rng(12)
-    for d in ("content", "style") + (("labelme_segmentation",) if masks else ()):
-        os.makedirs(os.path.join(root, d), exist_ok=True)
-    for k, mode in enumerate(modes):
-        for d, stem in (("content", f"in{k}"), ("style", f"tar{k}")):
-            name = stem if masks else f"p{k}"
-            a = rng.integers(0, 256, size=(size, size, 3), dtype=np.uint8)
-            Image.fromarray(a, "RGB").save(os.path.join(root, d, name + ".png"))
-            if masks:
-                M.write_mask_png(os.path.join(root, "labelme_segmentation", stem + ".png"),
-                                 M.blocks_mask(mask_size, mask_size, [0, 60, 120, 180], 30 + k),
-                                 mode)
-
-
 @pytest.mark.parametrize("use_mask", [False, True])
 def test_pipeline_with_ld_adain(cuda, tmp_path, use_mask):
     """stylize.py with `network: ld_adain` and --synthetic-weights: the PNGs it writes are the
     direct test() call's through the pipeline's own uint8 conversion."""
-    import yaml
-    from PIL import Image
-
     import network as net
-    import stylize
-    from rpst.imageio import DATASETS, load_image, to_tensor, to_uint8
     root = str(tmp_path / "data")
-    _tree(root, 40, 64, ["L", "P"], use_mask)  # images 40 -> 32, masks 64 -> 32
-    kind = "photoreal" if use_mask else "paired"
+    # images 40 -> 32, masks 64 -> 32
+    dataset_tree(root, 40, 64, ["L", "P"], rng_seed=12, mask_seed0=30, masks=use_mask)
     cfg = dict(L.config(4, 3, 0, use_mask), network="ld_adain", vgg="unused", img_size=32,
-               test_dir=root, test_dataset=kind, batch_size=2, num_workers=2,
-               output=str(tmp_path / "out"))
-    cfg_path = str(tmp_path / "cfg.yaml")
-    with open(cfg_path, "w") as f:
-        yaml.safe_dump(cfg, f)
-    assert stylize.main(["--config", cfg_path, "--synthetic-weights", "5"]) == 0
-    m = stylize.build_network(cfg, synthetic_seed=5).to(cuda)
+               test_dir=root, test_dataset="photoreal" if use_mask else "paired", batch_size=2,
+               num_workers=2)
+    m, _ = check_pipeline(cfg, tmp_path, cuda)
     assert isinstance(m, net.LDMSAdaINRPNet)
-    ds = DATASETS[kind](root)
-    assert len(ds) == 2
-    out_dir = tmp_path / "out" / "test" / "test_output"
-    for i in range(len(ds)):
-        cp, sp, cn, sn, cm, sm = ds.item(i)
-        c = to_tensor(_dev(load_image(cp, 32)[None], cuda))
-        s = to_tensor(_dev(load_image(sp, 32)[None], cuda))
-        kw = dict(c_mask_path=[cm], s_mask_path=[sm]) if use_mask else {}
-        y = m.test(c, s, **kw)
-        got = np.asarray(Image.open(out_dir / f"{cn}-{sn}.png"))
-        assert got.shape == (32, 32, 3)
-        assert np.array_equal(got, to_uint8(y)[0].cpu().numpy()), (cn, sn)
-        assert (out_dir / f"{cn}-{sn}-cat.png").exists()

@@ -8,31 +8,20 @@ Bars: TOL_STATS (1e-5 rel-L2) for statistics and the AdaIN affine, TOL_NET / TOL
 to end (tests/helpers.py), levels at max(1e-5, 3 x the reference's own fp32 distance to its
 float64 run), as tests/test_gpu_ld.py holds its convs."""
 import copy
-import os
 import re
 
-import numpy as np
 import pytest
 import torch
 import torch.nn.functional as F
 
 import ld4_ref as L4
 import ld_ref as L
-import masked_ref as M
-from helpers import TOL_NET, TOL_NET_MAXABS, TOL_STATS, max_abs_ratio, rel_l2, synth_
+from helpers import (TOL_NET, TOL_NET_MAXABS, TOL_STATS, check_pipeline, dataset_tree, dev, gen,
+                     golden_net, mask_kw, max_abs_ratio, rel_l2, traced_launches, unfused)
 
 pytestmark = pytest.mark.gpu
 
 SENTINEL = -12345.5
-
-
-def _dev(a, cuda):
-    return torch.from_numpy(np.ascontiguousarray(a)).to(cuda)
-
-
-def gen(seed, shape, scale=1.0, offset=0.0):
-    g = torch.Generator().manual_seed(seed)
-    return (torch.rand(shape, generator=g) * 2 - 1) * scale + offset
 
 
 # ---- the kernels --------------------------------------------------------------------------
@@ -161,31 +150,9 @@ def test_ld4_fuse_argument_checks(cuda):
 
 
 # ---- the network --------------------------------------------------------------------------
-def _net(g, i, cuda, **over):
+def _net(g, i, cuda):
     import network as net
-    cfg = L4.config(int(g[f"net{i}_hidden"]), int(g[f"net{i}_layers"]),
-                    int(g[f"net{i}_inception"]), int(g[f"net{i}_stylized_layers"]),
-                    bool(g[f"net{i}_use_mask"]))
-    cfg.update(over)
-    m = net.LDMSAdaINRPNet4(cfg, copy.deepcopy(net.vgg))
-    assert np.array_equal(synth_(m, int(g[f"net{i}_seed"])), g[f"net{i}_checksum"])
-    return m.to(cuda)
-
-
-def _mask_kw(g, i, cuda, tmp_path=None):
-    """The masked case's label maps: as tensors at the image size (the reference's own resize
-    of its files), or, with tmp_path, as the mask files themselves."""
-    if not bool(g[f"net{i}_use_mask"]):
-        return {}
-    if tmp_path is None:
-        return dict(c_mask_path=_dev(g[f"net{i}_cseg"].astype(np.uint8), cuda),
-                    s_mask_path=_dev(g[f"net{i}_sseg"].astype(np.uint8), cuda))
-    n = g[f"net{i}_cfile"].shape[0]
-    return dict(
-        c_mask_path=[M.write_mask_png(str(tmp_path / f"c{b}.png"), g[f"net{i}_cfile"][b], "L")
-                     for b in range(n)],
-        s_mask_path=[M.write_mask_png(str(tmp_path / f"s{b}.png"), g[f"net{i}_sfile"][b], "L")
-                     for b in range(n)])
+    return golden_net(net.LDMSAdaINRPNet4, L4.golden_config(g, i), g, f"net{i}_", cuda)
 
 
 @pytest.mark.parametrize("i", range(len(L4.CASES)))
@@ -193,9 +160,9 @@ def test_ld4_test_matches_reference(cuda, golden, i, tmp_path):
     import network.adain_rp as arp
     g = golden("ld4")
     m = _net(g, i, cuda)
-    c, s = _dev(g[f"net{i}_content"], cuda), _dev(g[f"net{i}_style"], cuda)
+    c, s = dev(g[f"net{i}_content"], cuda), dev(g[f"net{i}_style"], cuda)
     masked = bool(g[f"net{i}_use_mask"])
-    kw = _mask_kw(g, i, cuda, tmp_path if masked else None)  # the masks as files
+    kw = mask_kw(g, f"net{i}_", cuda, tmp_path if masked else None)  # the masks as files
     y = m.test(c, s, **kw)
     assert m.training  # test() leaves the model in training mode, as the reference does
     ref = g[f"net{i}_out"]
@@ -205,13 +172,10 @@ def test_ld4_test_matches_reference(cuda, golden, i, tmp_path):
     assert err < TOL_NET and mx < TOL_NET_MAXABS
     assert torch.equal(y, m.test(c, s, **kw))  # a repeated test() is bit-identical
     if masked:  # and from label maps already at the image size
-        yt = m.test(c, s, **_mask_kw(g, i, cuda))
+        yt = m.test(c, s, **mask_kw(g, f"net{i}_", cuda))
         assert rel_l2(yt, ref) < TOL_NET and max_abs_ratio(yt, ref) < TOL_NET_MAXABS
-    arp.FUSED_ADAIN = False
-    try:
+    with unfused(arp, "FUSED_ADAIN"):
         plain = m.test(c, s, **kw)
-    finally:
-        arp.FUSED_ADAIN = True
     assert rel_l2(plain, ref) < TOL_NET and max_abs_ratio(plain, ref) < TOL_NET_MAXABS
     assert rel_l2(y, plain) < TOL_NET
     m.eval()
@@ -228,7 +192,7 @@ def test_ld4_encoder_levels_match_reference(cuda, golden, i):
     assert bool(g[f"net{i}_has_levels"])
     m = _net(g, i, cuda)
     with torch.no_grad():
-        levels = m.encode_rp_intermediate(_dev(g[f"net{i}_content"], cuda))
+        levels = m.encode_rp_intermediate(dev(g[f"net{i}_content"], cuda))
     assert len(levels) == int(g[f"net{i}_layers"])
     for k, lv in enumerate(levels):
         ref = g[f"net{i}_level{k}_64"]
@@ -242,7 +206,7 @@ def test_ld4_encoder_levels_match_reference(cuda, golden, i):
 def test_ld4_batch_of_two_equals_single_images(cuda, golden):
     g = golden("ld4")
     m = _net(g, 0, cuda)
-    c, s = _dev(g["net0_content"], cuda), _dev(g["net0_style"], cuda)
+    c, s = dev(g["net0_content"], cuda), dev(g["net0_style"], cuda)
     y = m.test(c, s)
     for k in range(2):
         assert torch.equal(y[k:k + 1], m.test(c[k:k + 1], s[k:k + 1])), k
@@ -252,26 +216,11 @@ def test_ld4_launch_sequence(cuda, golden):
     """The fused test() of an L = 3 model issues, beside its convs, exactly L resized_mean_std
     and L ld4_fuse launches: no resize_nearest, no stand-alone AdaIN or statistics call, and
     no concatenation of feature maps."""
-    from rpst import ops
     g = golden("ld4")
     m = _net(g, 0, cuda)
-    c, s = _dev(g["net0_content"], cuda), _dev(g["net0_style"], cuda)
+    c, s = dev(g["net0_content"], cuda), dev(g["net0_style"], cuda)
     m.test(c, s)  # warm: the packed weights are cached
-    cats = []
-    real_cat = torch.cat
-
-    def spy(tensors, *a, **k):
-        cats.append([tuple(t.shape) for t in tensors])
-        return real_cat(tensors, *a, **k)
-
-    ops.TRACE = ops.Trace()
-    torch.cat = spy
-    try:
-        m.test(c, s)
-        names = [r[0] for r in ops.TRACE.records]
-    finally:
-        torch.cat = real_cat
-        ops.TRACE = None
+    names, cats = traced_launches(lambda: m.test(c, s))
     layers = int(g["net0_layers"])
     # conv launches are keyed '<algo><k>x<k> ...': everything else is listed here
     other = [nm for nm in names if not re.fullmatch(r"[a-z]+\d*x\d", nm.split(" ")[0])]
@@ -289,7 +238,7 @@ def test_ld4_launch_sequence(cuda, golden):
 def test_ld4_save_and_resume(cuda, golden, tmp_path):
     g = golden("ld4")
     m = _net(g, 0, cuda)
-    c, s = _dev(g["net0_content"], cuda), _dev(g["net0_style"], cuda)
+    c, s = dev(g["net0_content"], cuda), dev(g["net0_style"], cuda)
     y = m.test(c, s)
     path = str(tmp_path / "4321.pth")
     m.save(path, 4321)
@@ -304,7 +253,7 @@ def test_ld4_save_and_resume(cuda, golden, tmp_path):
 def test_ld4_forward_losses_under_no_grad(cuda, golden):
     g = golden("ld4")
     m = _net(g, 0, cuda)
-    c, s = _dev(g["net0_content"], cuda), _dev(g["net0_style"], cuda)
+    c, s = dev(g["net0_content"], cuda), dev(g["net0_style"], cuda)
     with torch.no_grad():
         losses, total = m(c, s)
     assert set(losses) == {"style_loss", "content_loss", "total_loss"}
@@ -315,49 +264,15 @@ def test_ld4_forward_losses_under_no_grad(cuda, golden):
 
 
 # ---- pipeline -----------------------------------------------------------------------------
-def _tree(root, size, mask_size, modes):
-    from PIL import Image
-    rng = np.random.default_rng(14)
-    for d in ("content", "style", "labelme_segmentation"):
-        os.makedirs(os.path.join(root, d), exist_ok=True)
-    for k, mode in enumerate(modes):
-        for d, stem in (("content", f"in{k}"), ("style", f"tar{k}")):
-            a = rng.integers(0, 256, size=(size, size, 3), dtype=np.uint8)
-            Image.fromarray(a, "RGB").save(os.path.join(root, d, stem + ".png"))
-            M.write_mask_png(os.path.join(root, "labelme_segmentation", stem + ".png"),
-                             M.blocks_mask(mask_size, mask_size, [0, 60, 120, 180], 40 + k), mode)
-
-
 def test_pipeline_with_ld_adain4_and_masks(cuda, tmp_path):
     """stylize.py with `network: ld_adain4`, `use_mask: True`, `test_dataset: photoreal` and
     --synthetic-weights: the PNGs it writes are the direct test() call's through the pipeline's
     own uint8 conversion."""
-    import yaml
-    from PIL import Image
-
     import network as net
-    import stylize
-    from rpst.imageio import DATASETS, load_image, to_tensor, to_uint8
     root = str(tmp_path / "data")
-    _tree(root, 40, 64, ["L", "P"])  # images 40 -> 32, masks 64 -> 32
+    # images 40 -> 32, masks 64 -> 32
+    dataset_tree(root, 40, 64, ["L", "P"], rng_seed=14, mask_seed0=40)
     cfg = dict(L4.config(4, 3, 0, 1, True), network="ld_adain4", vgg="unused", img_size=32,
-               test_dir=root, test_dataset="photoreal", batch_size=2, num_workers=2,
-               output=str(tmp_path / "out"))
-    cfg_path = str(tmp_path / "cfg.yaml")
-    with open(cfg_path, "w") as f:
-        yaml.safe_dump(cfg, f)
-    assert stylize.main(["--config", cfg_path, "--synthetic-weights", "5"]) == 0
-    m = stylize.build_network(cfg, synthetic_seed=5).to(cuda)
+               test_dir=root, test_dataset="photoreal", batch_size=2, num_workers=2)
+    m, _ = check_pipeline(cfg, tmp_path, cuda)
     assert isinstance(m, net.LDMSAdaINRPNet4)
-    ds = DATASETS["photoreal"](root)
-    assert len(ds) == 2
-    out_dir = tmp_path / "out" / "test" / "test_output"
-    for i in range(len(ds)):
-        cp, sp, cn, sn, cm, sm = ds.item(i)
-        c = to_tensor(_dev(load_image(cp, 32)[None], cuda))
-        s = to_tensor(_dev(load_image(sp, 32)[None], cuda))
-        y = m.test(c, s, c_mask_path=[cm], s_mask_path=[sm])
-        got = np.asarray(Image.open(out_dir / f"{cn}-{sn}.png"))
-        assert got.shape == (32, 32, 3)
-        assert np.array_equal(got, to_uint8(y)[0].cpu().numpy()), (cn, sn)
-        assert (out_dir / f"{cn}-{sn}-cat.png").exists()

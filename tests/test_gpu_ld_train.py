@@ -19,7 +19,7 @@ import torch
 
 import ld_ref as L
 import ld_train_ref as LT
-from helpers import rel_l2, state_dict_of, synth_
+from helpers import gen, rel_l2, state_dict_of, synth_
 
 pytestmark = pytest.mark.gpu
 
@@ -43,11 +43,6 @@ WGRAD_CASES = [
 ]
 DGRAD_CASES = WGRAD_CASES + [((1, 8, 4, 6, 8), (REFLECT,)), ((2, 12, 5, 4, 8), (REFLECT,)),
                              ((1, 8, 6, 5, 8), (REFLECT,))]
-
-
-def gen(seed, shape, scale=1.0, offset=0.0):
-    g = torch.Generator().manual_seed(seed)
-    return (torch.rand(shape, generator=g) * 2 - 1) * scale + offset
 
 
 def _inputs(shape):
@@ -164,7 +159,7 @@ def test_stack_backward_7x7_block(cuda, pad_type):
     def cpu_grads(dt):
         p = {k: v.detach().clone().to(dt).requires_grad_() for k, v in sd.items()}
         xd = x.detach().clone().to(dt).requires_grad_()
-        LT.block(xd, p, "", "reflect" if pad_type == "reflect" else "constant").backward(g.to(dt))
+        L.block(xd, p, "", "reflect" if pad_type == "reflect" else "constant").backward(g.to(dt))
         return dict({k: v.grad for k, v in p.items()}, input=xd.grad)
 
     g64 = cpu_grads(torch.float64)

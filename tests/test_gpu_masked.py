@@ -3,21 +3,16 @@ float64 restatement (tests/masked_ref.py) and the reference goldens
 (tests/golden/masked.*), the two networks' masked test() against the goldens, and the
 pipeline with masks."""
 import copy
-import os
 
 import numpy as np
 import pytest
 import torch
 
 import masked_ref as M
-from helpers import (SOURCE_CONFIG, TOL_NET, TOL_NET_MAXABS, TOL_STATS, max_abs_ratio,
-                     multiscale_config, rel_l2, synth_)
+from helpers import (SOURCE_CONFIG, TOL_STATS, check_net, check_pipeline, dataset_tree, dev,
+                     golden_net, mask_kw, multiscale_config, rel_l2, synth_, unfused)
 
 pytestmark = pytest.mark.gpu
-
-
-def _dev(a, cuda):
-    return torch.from_numpy(np.ascontiguousarray(a)).to(cuda)
 
 
 # ---- segment_plan ------------------------------------------------------------------------
@@ -59,7 +54,7 @@ def test_segment_plan_counts_and_flags(cuda, pad):
     c1 = np.tile(c1[:, None], (1, c_shape[1]))
     s1 = np.full(s_shape, 3, np.uint8)
     s1[:2, :5] = 200  # 10 pixels of 200 in the style: not valid
-    plan = ops.segment_plan(_dev(np.stack([c0, c1]), cuda), _dev(np.stack([s0, s1]), cuda))
+    plan = ops.segment_plan(dev(np.stack([c0, c1]), cuda), dev(np.stack([s0, s1]), cuda))
     assert plan.dtype == torch.int32 and tuple(plan.shape) == (2, 256, 4)
     plan = plan.cpu().numpy()
     for n, (c, s) in enumerate([(c0, s0), (c1, s1)]):
@@ -109,8 +104,8 @@ def test_masked_adain_params_vs_float64(cuda, golden, op_refs):
     from rpst import ops
     g = golden("masked")
     for i, name in _op_cases(g):
-        c, s = _dev(g[f"op{i}_c"], cuda), _dev(g[f"op{i}_s"], cuda)
-        cseg, sseg = _dev(g[f"op{i}_cseg"], cuda), _dev(g[f"op{i}_sseg"], cuda)
+        c, s = dev(g[f"op{i}_c"], cuda), dev(g[f"op{i}_s"], cuda)
+        cseg, sseg = dev(g[f"op{i}_cseg"], cuda), dev(g[f"op{i}_sseg"], cuda)
         got = ops.masked_adain_params(c, s, cseg, sseg).cpu().numpy()
         rows, counts = op_refs[i]
         assert got.shape == rows.shape
@@ -131,11 +126,11 @@ def test_single_label_agrees_with_calc_mean_std(cuda, golden):
     from rpst import ops
     g = golden("masked")
     i = [k for k, name in _op_cases(g) if name.startswith("single")][0]
-    c, s = _dev(g[f"op{i}_c"], cuda), _dev(g[f"op{i}_s"], cuda)
+    c, s = dev(g[f"op{i}_c"], cuda), dev(g[f"op{i}_s"], cuda)
     lab = int(g[f"op{i}_cseg"][0, 0, 0])
     assert (g[f"op{i}_cseg"] == lab).all() and (g[f"op{i}_sseg"] == lab).all()
-    p = ops.masked_adain_params(c, s, _dev(g[f"op{i}_cseg"], cuda),
-                                _dev(g[f"op{i}_sseg"], cuda))[:, :, lab].cpu().numpy()
+    p = ops.masked_adain_params(c, s, dev(g[f"op{i}_cseg"], cuda),
+                                dev(g[f"op{i}_sseg"], cuda))[:, :, lab].cpu().numpy()
     cm, cs = (t.cpu().numpy().reshape(p.shape[:2]) for t in ops.calc_mean_std(c))
     sm, ss = (t.cpu().numpy().reshape(p.shape[:2]) for t in ops.calc_mean_std(s))
     for got, ref in ((p[..., 0], cm), (p[..., 1], cs), (p[..., 2], ss), (p[..., 3], sm)):
@@ -147,8 +142,8 @@ def test_masked_adain_vs_reference_goldens(cuda, golden, op_refs):
     from rpst import ops
     g = golden("masked")
     for i, name in _op_cases(g):
-        c, s = _dev(g[f"op{i}_c"], cuda), _dev(g[f"op{i}_s"], cuda)
-        cseg, sseg = _dev(g[f"op{i}_cseg"], cuda), _dev(g[f"op{i}_sseg"], cuda)
+        c, s = dev(g[f"op{i}_c"], cuda), dev(g[f"op{i}_s"], cuda)
+        cseg, sseg = dev(g[f"op{i}_cseg"], cuda), dev(g[f"op{i}_sseg"], cuda)
         out = ops.masked_adain(c, s, cseg, sseg)
         err = rel_l2(out, g[f"op{i}_out"])
         print(f"masked_adain {name}: rel-L2 {err:.3e}")
@@ -179,8 +174,8 @@ def test_masked_adain_vs_reference_goldens(cuda, golden, op_refs):
 def test_masked_adain_batch_independent(cuda, golden):
     from rpst import ops
     g = golden("masked")
-    c, s = _dev(g["op0_c"], cuda), _dev(g["op0_s"], cuda)
-    cseg, sseg = _dev(g["op0_cseg"], cuda), _dev(g["op0_sseg"], cuda)
+    c, s = dev(g["op0_c"], cuda), dev(g["op0_s"], cuda)
+    cseg, sseg = dev(g["op0_cseg"], cuda), dev(g["op0_sseg"], cuda)
     assert c.shape[0] == 2
     both = ops.masked_adain(c, s, cseg, sseg)
     for n in range(2):
@@ -189,15 +184,7 @@ def test_masked_adain_batch_independent(cuda, golden):
 
 
 # ---- networks ----------------------------------------------------------------------------
-def _mask_paths(tmp_path, tag, files, mode):
-    return [M.write_mask_png(str(tmp_path / f"{tag}_{mode}_{b}.png"), files[b], mode)
-            for b in range(files.shape[0])]
-
-
-def _check_net(y, ref, what):
-    err, mx = rel_l2(y, ref), max_abs_ratio(y, ref)
-    print(f"{what}: rel-L2 {err:.3e} max-abs {mx:.3e}")
-    assert err < TOL_NET and mx < TOL_NET_MAXABS, (what, err, mx)
+MASK_FILE = "{tag}_{mode}_{b}.png"
 
 
 @pytest.mark.parametrize("mode", ["L", "P"])
@@ -205,29 +192,23 @@ def test_multiscale_masked_golden(cuda, golden, tmp_path, mode):
     import network as net
     import network.adain_rp as arp
     g = golden("masked")
-    m = net.MultiScaleAdaINRPNet(dict(multiscale_config(8, 5, 0), use_mask=True),
-                                 copy.deepcopy(net.vgg))
-    assert np.array_equal(synth_(m, int(g["ms_seed"])), g["ms_checksum"])
-    m = m.to(cuda)
-    c, s = _dev(g["ms_content"], cuda), _dev(g["ms_style"], cuda)
-    cps = _mask_paths(tmp_path, "c", g["ms_cfile"], mode)
-    sps = _mask_paths(tmp_path, "s", g["ms_sfile"], mode)
-    y = m.test(c, s, c_mask_path=cps, s_mask_path=sps)
-    _check_net(y, g[f"ms_out_{mode}"], f"multiscale fused {mode}")
+    m = golden_net(net.MultiScaleAdaINRPNet, dict(multiscale_config(8, 5, 0), use_mask=True), g,
+                   "ms_", cuda)
+    c, s = dev(g["ms_content"], cuda), dev(g["ms_style"], cuda)
+    kw = mask_kw(g, "ms_", cuda, tmp_path, mode, MASK_FILE)
+    y = m.test(c, s, **kw)
+    check_net(y, g[f"ms_out_{mode}"], f"multiscale fused {mode}")
     # already-decoded label maps: the same bits as the paths
-    cseg, sseg = _dev(g[f"ms_cseg_{mode}"], cuda), _dev(g[f"ms_sseg_{mode}"], cuda)
+    cseg, sseg = dev(g[f"ms_cseg_{mode}"], cuda), dev(g[f"ms_sseg_{mode}"], cuda)
     assert torch.equal(m.test(c, s, c_mask_path=cseg, s_mask_path=sseg), y)
     assert torch.equal(m.test(c, s, c_mask_path=cseg.cpu(), s_mask_path=sseg.cpu()), y)
     # op by op: test() with FUSED_ADAIN off goes through decode(..., use_mask=True)
-    arp.FUSED_ADAIN = False
-    try:
-        plain = m.test(c, s, c_mask_path=cps, s_mask_path=sps)
-    finally:
-        arp.FUSED_ADAIN = True
-    _check_net(plain, g[f"ms_out_{mode}"], f"multiscale op-by-op {mode}")
+    with unfused(arp, "FUSED_ADAIN"):
+        plain = m.test(c, s, **kw)
+    check_net(plain, g[f"ms_out_{mode}"], f"multiscale op-by-op {mode}")
     with torch.no_grad():
         cf, sf = m.encode_rp_intermediate(c), m.encode_rp_intermediate(s)
-        dec =m.decode(cf, sf, use_mask=True, c_mask_path=cps, s_mask_path=sps)
+        dec = m.decode(cf, sf, use_mask=True, **kw)
     assert torch.equal(dec, plain)
 
 
@@ -238,8 +219,8 @@ def test_multiscale_unmasked_unchanged_and_sort_still_raises(cuda, golden):
     m = net.MultiScaleAdaINRPNet(multiscale_config(8, 5, 0), copy.deepcopy(net.vgg))
     synth_(m, int(g["ms_seed"]))
     m = m.to(cuda)
-    c, s = _dev(g["ms_content"], cuda), _dev(g["ms_style"], cuda)
-    cseg = _dev(g["ms_cseg_P"], cuda)
+    c, s = dev(g["ms_content"], cuda), dev(g["ms_style"], cuda)
+    cseg = dev(g["ms_cseg_P"], cuda)
     assert torch.equal(m.test(c, s), m.test(c, s, c_mask_path=cseg, s_mask_path=cseg))
     cfg = dict(multiscale_config(8, 5, 0), use_mask=True, sort=True)
     m2 = net.MultiScaleAdaINRPNet(cfg, copy.deepcopy(net.vgg)).to(cuda)
@@ -252,69 +233,30 @@ def test_sourcenet_masked_golden(cuda, golden, tmp_path, mode):
     import network as net
     import network.base as base
     g = golden("masked")
-    m = net.SourceNet(dict(SOURCE_CONFIG, use_mask=True), copy.deepcopy(net.vgg))
-    assert np.array_equal(synth_(m, int(g["src_seed"])), g["src_checksum"])
-    m = m.to(cuda)
-    c, s = _dev(g["src_content"], cuda), _dev(g["src_style"], cuda)
-    cps = _mask_paths(tmp_path, "c", g["src_cfile"], mode)
-    sps = _mask_paths(tmp_path, "s", g["src_sfile"], mode)
-    y = m.test(c, s, c_mask_path=cps, s_mask_path=sps)
-    _check_net(y, g[f"src_out_{mode}"], f"sourcenet fused {mode}")
-    cseg, sseg = _dev(g[f"src_cseg_{mode}"], cuda), _dev(g[f"src_sseg_{mode}"], cuda)
+    m = golden_net(net.SourceNet, dict(SOURCE_CONFIG, use_mask=True), g, "src_", cuda)
+    c, s = dev(g["src_content"], cuda), dev(g["src_style"], cuda)
+    kw = mask_kw(g, "src_", cuda, tmp_path, mode, MASK_FILE)
+    y = m.test(c, s, **kw)
+    check_net(y, g[f"src_out_{mode}"], f"sourcenet fused {mode}")
+    cseg, sseg = dev(g[f"src_cseg_{mode}"], cuda), dev(g[f"src_sseg_{mode}"], cuda)
     assert tuple(cseg.shape) == (1, 8, 6)
     assert torch.equal(m.test(c, s, c_mask_path=cseg, s_mask_path=sseg), y)
-    base.FUSED = False
-    try:
-        plain = m.test(c, s, c_mask_path=cps, s_mask_path=sps)
-    finally:
-        base.FUSED = True
-    _check_net(plain, g[f"src_out_{mode}"], f"sourcenet op-by-op {mode}")
+    with unfused(base, "FUSED"):
+        plain = m.test(c, s, **kw)
+    check_net(plain, g[f"src_out_{mode}"], f"sourcenet op-by-op {mode}")
 
 
 # ---- pipeline ----------------------------------------------------------------------------
-def _photoreal_tree(root, size, mask_size, modes):
-    """Two pairs: content/in<k>.png, style/tar<k>.png, labelme_segmentation/<stem>.png."""
-    from PIL import Image
-    rng = np.random.default_rng(11)
-    for d in ("content", "style", "labelme_segmentation"):
-        os.makedirs(os.path.join(root, d), exist_ok=True)
-    for k, mode in enumerate(modes):
-        for d, stem in (("content", f"in{k}"), ("style", f"tar{k}")):
-            a = rng.integers(0, 256, size=(size, size, 3), dtype=np.uint8)
-            Image.fromarray(a, "RGB").save(os.path.join(root, d, stem + ".png"))
-            M.write_mask_png(os.path.join(root, "labelme_segmentation", stem + ".png"),
-                             M.blocks_mask(mask_size, mask_size, [0, 60, 120, 180], 20 + k), mode)
-
-
 def test_pipeline_with_masks_matches_direct_test(cuda, tmp_path):
-    import yaml
-    from PIL import Image
-
-    import stylize
-    from rpst.imageio import PhotorealisticPairedDataset, load_image, to_tensor, to_uint8
+    from rpst.imageio import to_uint8
     root = str(tmp_path / "data")
-    _photoreal_tree(root, 40, 64, ["L", "P"])  # images 40 -> 32, masks 64 -> 32
+    # images 40 -> 32, masks 64 -> 32
+    dataset_tree(root, 40, 64, ["L", "P"], rng_seed=11, mask_seed0=20)
     cfg = dict(multiscale_config(8, 3, 0), network="multi_adain", vgg="unused", use_mask=True,
                img_size=32, test_dir=root, test_dataset="photoreal", batch_size=2,
-               num_workers=2, output=str(tmp_path / "out"))
-    cfg_path = str(tmp_path / "cfg.yaml")
-    with open(cfg_path, "w") as f:
-        yaml.safe_dump(cfg, f)
-    assert stylize.main(["--config", cfg_path, "--synthetic-weights", "5"]) == 0
-    m = stylize.build_network(cfg, synthetic_seed=5).to(cuda)
-    ds = PhotorealisticPairedDataset(root)
-    assert len(ds) == 2
-    out_dir = tmp_path / "out" / "test" / "test_output"
-    for i in range(len(ds)):
-        cp, sp, cn, sn, cm, sm = ds.item(i)
-        c = to_tensor(_dev(load_image(cp, 32)[None], cuda))
-        s = to_tensor(_dev(load_image(sp, 32)[None], cuda))
-        y = m.test(c, s, c_mask_path=[cm], s_mask_path=[sm])
-        ref = to_uint8(y)[0].cpu().numpy()
-        got = np.asarray(Image.open(out_dir / f"{cn}-{sn}.png"))
-        assert np.array_equal(got, ref), (cn, sn)
-        # the masks matter: the unmasked network writes other pixels
-        m.config["use_mask"] = False
+               num_workers=2)
+    m, items = check_pipeline(cfg, tmp_path, cuda)
+    # the masks matter: the unmasked network writes other pixels
+    m.config["use_mask"] = False
+    for c, s, ref in items:
         assert not np.array_equal(to_uint8(m.test(c, s))[0].cpu().numpy(), ref)
-        m.config["use_mask"] = True
-        assert (out_dir / f"{cn}-{sn}-cat.png").exists()

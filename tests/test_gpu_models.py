@@ -6,21 +6,11 @@ import numpy as np
 import pytest
 import torch
 
-from helpers import (TOL_NET, TOL_NET_MAXABS, TOL_WCT, max_abs_ratio, rel_l2, rp_config,
-                     state_dict_of, synth_)
+from helpers import (TOL_NET, TOL_NET_MAXABS, TOL_WCT, gen, max_abs_ratio, rel_l2, rp_config,
+                     state_dict_of, synth_, t, unfused)
 from oracle import restate as R
 
 pytestmark = pytest.mark.gpu
-
-
-def t(a):
-    return torch.from_numpy(np.ascontiguousarray(a))
-
-
-def gen(seed, shape, scale=1.0, offset=0.0, relu=False):
-    g = torch.Generator().manual_seed(seed)
-    x = (torch.rand(shape, generator=g) * 2 - 1) * scale + offset
-    return x.clamp_min(0) if relu else x
 
 
 # ---- a11/a12/a13: SANet ----------------------------------------------------------------
@@ -571,11 +561,8 @@ def test_wct_rp_fused_vs_unfused(cuda):
     c = torch.from_numpy(synth.image(43, (2, 3, 64, 96))).to(cuda)
     s = torch.from_numpy(synth.image(44, (2, 3, 64, 96))).to(cuda)
     fused = m.test(c, s)
-    wrp.FUSED_WCT = False
-    try:
+    with unfused(wrp, "FUSED_WCT"):
         plain = m.test(c, s)
-    finally:
-        wrp.FUSED_WCT = True
     assert rel_l2(fused, plain) < 1e-5, rel_l2(fused, plain)
 
 

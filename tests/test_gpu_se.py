@@ -15,19 +15,11 @@ import torch.nn.functional as F
 
 import masked_ref as M
 import se_ref as S
-from helpers import (TOL_NET, TOL_NET_MAXABS, TOL_STATS, max_abs_ratio, multiscale_config, rel_l2,
-                     synth_)
+from helpers import (TOL_NET, TOL_STATS, check_net, check_pipeline, dataset_tree, dev, gen,
+                     golden_net, mask_kw, multiscale_config, rel_l2, synth_, traced_launches,
+                     unfused)
 
 pytestmark = pytest.mark.gpu
-
-
-def _dev(a, cuda):
-    return torch.from_numpy(np.ascontiguousarray(a)).to(cuda)
-
-
-def gen(seed, shape, scale=1.0, offset=0.0):
-    g = torch.Generator().manual_seed(seed)
-    return (torch.rand(shape, generator=g) * 2 - 1) * scale + offset
 
 
 # ---- the gate -----------------------------------------------------------------------------
@@ -137,7 +129,7 @@ def test_se_bottleneck_module_goldens(cuda, golden, i):
     from rpst import ops
     g = golden("se")
     blk, sd = _module(g, i, cuda)
-    x = _dev(g[f"mod{i}_x"], cuda)
+    x = dev(g[f"mod{i}_x"], cuda)
     ref, ref_gate = S.se_block(g[f"mod{i}_x"], sd)
     with torch.no_grad():
         out, gate = ops.se_bottleneck(x, blk)
@@ -158,34 +150,13 @@ def test_se_bottleneck_module_goldens(cuda, golden, i):
     rs = torch.sqrt(ref.var(dim=(2, 3), unbiased=True, keepdim=True) + 1e-5)
     assert rel_l2(mean, rm) < TOL_STATS and rel_l2(std, rs) < TOL_STATS
     # x is the residual and must come back untouched
-    assert torch.equal(x, _dev(g[f"mod{i}_x"], cuda))
+    assert torch.equal(x, dev(g[f"mod{i}_x"], cuda))
 
 
 # ---- networks -------------------------------------------------------------------------------
 def _net(g, i, cuda, seed=None):
     import network as net
-    cfg = dict(multiscale_config(int(g[f"net{i}_hidden"]), int(g[f"net{i}_blocks"]), 0),
-               attention="se", use_mask=bool(g[f"net{i}_use_mask"]))
-    m = net.MultiScaleAdaINRPNet(cfg, copy.deepcopy(net.vgg))
-    ck = synth_(m, int(g[f"net{i}_seed"]) if seed is None else seed)
-    if seed is None:
-        assert np.array_equal(ck, g[f"net{i}_checksum"])
-    return m.to(cuda)
-
-
-def _masks(g, i, tmp_path):
-    if not bool(g[f"net{i}_use_mask"]):
-        return {}
-    def paths(tag, files):
-        return [M.write_mask_png(str(tmp_path / f"{tag}{b}.png"), files[b], "L")
-                for b in range(files.shape[0])]
-    return dict(c_mask_path=paths("c", g[f"net{i}_cfile"]), s_mask_path=paths("s", g[f"net{i}_sfile"]))
-
-
-def _check_net(y, ref, what):
-    err, mx = rel_l2(y, ref), max_abs_ratio(y, ref)
-    print(f"{what}: rel-L2 {err:.3e} max-abs {mx:.3e}")
-    assert err < TOL_NET and mx < TOL_NET_MAXABS, (what, err, mx)
+    return golden_net(net.MultiScaleAdaINRPNet, S.golden_config(g, i), g, f"net{i}_", cuda, seed)
 
 
 def _check_maps(m, g, i, n, what):
@@ -209,20 +180,17 @@ def test_multiscale_se_goldens(cuda, golden, tmp_path, i):
     import network.adain_rp as arp
     g = golden("se")
     m = _net(g, i, cuda)
-    c, s = _dev(g[f"net{i}_content"], cuda), _dev(g[f"net{i}_style"], cuda)
+    c, s = dev(g[f"net{i}_content"], cuda), dev(g[f"net{i}_style"], cuda)
     n = c.shape[0]
-    kw = _masks(g, i, tmp_path)
+    kw = mask_kw(g, f"net{i}_", cuda, tmp_path)
     y = m.test(c, s, **kw)
-    _check_net(y, g[f"net{i}_out"], f"multiscale se case {i} fused")
+    check_net(y, g[f"net{i}_out"], f"multiscale se case {i} fused")
     _check_maps(m, g, i, n, "fused")
     fused_maps = [blk.attention_map.clone() for blk in m.rp_shared_encoder]
     assert torch.equal(m.test(c, s, **kw), y)
-    arp.FUSED_ADAIN = False
-    try:
+    with unfused(arp, "FUSED_ADAIN"):
         plain = m.test(c, s, **kw)
-    finally:
-        arp.FUSED_ADAIN = True
-    _check_net(plain, g[f"net{i}_out"], f"multiscale se case {i} op-by-op")
+    check_net(plain, g[f"net{i}_out"], f"multiscale se case {i} op-by-op")
     _check_maps(m, g, i, n, "op-by-op")
     assert rel_l2(y, plain) < 1e-5
     for a, blk in zip(fused_maps, m.rp_shared_encoder):
@@ -264,11 +232,8 @@ def test_models_without_attention_unchanged(cuda):
     c = torch.from_numpy(synth.image(41, (2, 3, 24, 40))).to(cuda)
     s = torch.from_numpy(synth.image(42, (2, 3, 24, 40))).to(cuda)
     y = m.test(c, s)
-    arp.FUSED_ADAIN = False
-    try:
+    with unfused(arp, "FUSED_ADAIN"):
         plain = m.test(c, s)
-    finally:
-        arp.FUSED_ADAIN = True
     assert rel_l2(y, plain) < 1e-5
     assert all(b.attention_map is None for b in m.rp_shared_encoder)
 
@@ -278,7 +243,7 @@ def test_fold_cache_follows_load_state_dict_and_to(cuda, golden):
     from rpst import plan
     g = golden("se")
     m = _net(g, 2, cuda)
-    c, s = _dev(g["net2_content"], cuda), _dev(g["net2_style"], cuda)
+    c, s = dev(g["net2_content"], cuda), dev(g["net2_style"], cuda)
     y1 = m.test(c, s)
     blk = m.rp_shared_encoder[0].attention_block
     cached = plan.se_folded(blk)
@@ -308,7 +273,7 @@ def test_se_training_paths_raise(cuda, golden):
     import network as net
     g = golden("se")
     m = _net(g, 2, cuda)
-    c, s = _dev(g["net2_content"], cuda), _dev(g["net2_style"], cuda)
+    c, s = dev(g["net2_content"], cuda), dev(g["net2_style"], cuda)
     assert torch.is_grad_enabled()
     with pytest.raises(NotImplementedError, match="inference only"):
         m(c, s)
@@ -333,65 +298,26 @@ def test_se_block_launch_sequence(cuda, golden):
     from rpst import ops
     g = golden("se")
     blk, _ = _module(g, 0, cuda)
-    x = _dev(g["mod0_x"], cuda)
+    x = dev(g["mod0_x"], cuda)
     for stats in (False, True):
         with torch.no_grad():
             ops.se_bottleneck(x, blk, stats=stats)  # warm: the fold and its packing are cached
-            ops.TRACE = ops.Trace()
-            try:
-                ops.se_bottleneck(x, blk, stats=stats)
-                names = [r[0] for r in ops.TRACE.records]
-            finally:
-                ops.TRACE = None
+            names, _ = traced_launches(lambda: ops.se_bottleneck(x, blk, stats=stats))
         kinds = [nm.split(" ")[0] for nm in names]
         assert kinds == ["conv1x1", "wino43x3", "se_gate", "gated1x1"], names
         assert all("32->32 24x40 N2" in nm for nm in (names[0], names[1], names[3])), names
 
 
 # ---- pipeline -------------------------------------------------------------------------------
-def _photoreal_tree(root, size, mask_size, modes):
-    """Pairs content/in<k>.png, style/tar<k>.png with labelme_segmentation/<stem>.png."""
-    import os
-
-    from PIL import Image
-    rng = np.random.default_rng(12)
-    for d in ("content", "style", "labelme_segmentation"):
-        os.makedirs(os.path.join(root, d), exist_ok=True)
-    for k, mode in enumerate(modes):
-        for d, stem in (("content", f"in{k}"), ("style", f"tar{k}")):
-            a = rng.integers(0, 256, size=(size, size, 3), dtype=np.uint8)
-            Image.fromarray(a, "RGB").save(os.path.join(root, d, stem + ".png"))
-            M.write_mask_png(os.path.join(root, "labelme_segmentation", stem + ".png"),
-                             M.blocks_mask(mask_size, mask_size, [0, 60, 120, 180], 30 + k), mode)
-
-
 def test_pipeline_with_se_and_masks(cuda, tmp_path):
     """stylize.py with a YAML carrying `attention: se`, `use_mask: True` and
     --synthetic-weights: the outputs it writes are the direct test() call's. The pipeline
     resizes every image to (img_size, img_size), as the reference's does, so it runs at 40x40."""
-    import yaml
-    from PIL import Image
-
-    import stylize
-    from rpst.imageio import PhotorealisticPairedDataset, load_image, to_tensor, to_uint8
     root = str(tmp_path / "data")
-    _photoreal_tree(root, 48, 80, ["L", "P"])  # images 48 -> 40, masks 80 -> 40
+    # images 48 -> 40, masks 80 -> 40
+    dataset_tree(root, 48, 80, ["L", "P"], rng_seed=12, mask_seed0=30)
     cfg = dict(multiscale_config(16, 3, 0), network="multi_adain", vgg="unused", use_mask=True,
                attention="se", img_size=40, test_dir=root, test_dataset="photoreal",
-               batch_size=2, num_workers=2, output=str(tmp_path / "out"))
-    cfg_path = str(tmp_path / "cfg.yaml")
-    with open(cfg_path, "w") as f:
-        yaml.safe_dump(cfg, f)
-    assert stylize.main(["--config", cfg_path, "--synthetic-weights", "5"]) == 0
-    m = stylize.build_network(cfg, synthetic_seed=5).to(cuda)
+               batch_size=2, num_workers=2)
+    m, _ = check_pipeline(cfg, tmp_path, cuda)
     assert m._has_attention()
-    ds = PhotorealisticPairedDataset(root)
-    out_dir = tmp_path / "out" / "test" / "test_output"
-    for i in range(len(ds)):
-        cp, sp, cn, sn, cm, sm = ds.item(i)
-        c = to_tensor(_dev(load_image(cp, 40)[None], cuda))
-        s = to_tensor(_dev(load_image(sp, 40)[None], cuda))
-        y = m.test(c, s, c_mask_path=[cm], s_mask_path=[sm])
-        got = np.asarray(Image.open(out_dir / f"{cn}-{sn}.png"))
-        assert got.shape == (40, 40, 3)
-        assert np.array_equal(got, to_uint8(y)[0].cpu().numpy()), (cn, sn)

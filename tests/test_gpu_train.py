@@ -15,15 +15,10 @@ import pytest
 import torch
 import torch.nn.functional as Fn
 
-from helpers import TOL_NET, grad_bar, rel_l2, rp_config, state_dict_of, synth_
+from helpers import TOL_NET, gen, grad_bar, rel_l2, rp_config, state_dict_of, synth_
 from oracle import restate as R
 
 pytestmark = pytest.mark.gpu
-
-
-def gen(seed, shape, scale=1.0, offset=0.0):
-    g = torch.Generator().manual_seed(seed)
-    return (torch.rand(shape, generator=g) * 2 - 1) * scale + offset
 
 
 # ---- kernels ---------------------------------------------------------------------------

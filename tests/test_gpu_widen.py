@@ -13,26 +13,16 @@ import pytest
 import torch
 import torch.nn.functional as F
 
-from helpers import (SOURCE_CONFIG, TOL_NET, TOL_NET_MAXABS, deeper_config, max_abs_ratio,
-                     multiscale_config, rel_l2, state_dict_of, synth_)
+from helpers import (SOURCE_CONFIG, TOL_NET, TOL_NET_MAXABS, deeper_config, gen, max_abs_ratio,
+                     multiscale_config, rel_l2, state_dict_of, synth_, t, unfused, use_conv_algo)
 from oracle import restate as R
 
 pytestmark = pytest.mark.gpu
 
 
-def t(a):
-    return torch.from_numpy(np.ascontiguousarray(a))
-
-
-def gen(seed, shape, scale=1.0, offset=0.0):
-    g = torch.Generator().manual_seed(seed)
-    return (torch.rand(shape, generator=g) * 2 - 1) * scale + offset
-
-
 @pytest.fixture(params=["direct", "winograd", "winograd4"])
 def conv_algo(request, monkeypatch):
-    monkeypatch.setenv("RPST_CONV_ALGO", request.param)
-    return request.param
+    return use_conv_algo(monkeypatch, request.param)
 
 
 # ---- kernel features -------------------------------------------------------------------
@@ -155,11 +145,8 @@ def test_multiscale_fused_equals_unfused(cuda):
     c = torch.from_numpy(synth.image(41, (2, 3, 40, 56))).to(cuda)
     s = torch.from_numpy(synth.image(42, (2, 3, 40, 56))).to(cuda)
     fused = m.test(c, s)
-    arp.FUSED_ADAIN = False
-    try:
+    with unfused(arp, "FUSED_ADAIN"):
         plain = m.test(c, s)
-    finally:
-        arp.FUSED_ADAIN = True
     assert rel_l2(fused, plain) < 1e-5
 
 
@@ -202,9 +189,6 @@ def test_sourcenet_vs_oracle_and_unfused(cuda):
     out = m.test(c.to(cuda), s.to(cuda))
     ref = R.sourcenet_test(c, s, sd)
     assert rel_l2(out, ref) < TOL_NET and max_abs_ratio(out, ref) < TOL_NET_MAXABS
-    base.FUSED = False
-    try:
+    with unfused(base, "FUSED"):
         plain = m.test(c.to(cuda), s.to(cuda))
-    finally:
-        base.FUSED = True
     assert rel_l2(out, plain) < 1e-5

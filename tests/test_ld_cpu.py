@@ -9,17 +9,12 @@ import torch
 import torch.nn as nn
 
 import ld_ref as L
-from helpers import rel_l2, synth_
+from helpers import golden_net, rel_l2
 
 
-def _model(g, i, **over):
+def _model(g, i):
     import network as net
-    cfg = L.config(int(g[f"net{i}_hidden"]), int(g[f"net{i}_layers"]),
-                   int(g[f"net{i}_inception"]), bool(g[f"net{i}_use_mask"]))
-    cfg.update(over)
-    m = net.LDMSAdaINRPNet(cfg, copy.deepcopy(net.vgg))
-    ck = synth_(m, int(g[f"net{i}_seed"]))
-    return m, ck
+    return golden_net(net.LDMSAdaINRPNet, L.golden_config(g, i), g, f"net{i}_")
 
 
 def test_cases_recorded(golden):
@@ -38,8 +33,7 @@ def test_restatement_matches_reference_float64(golden, i):
     """ld_ref.test / ld_ref.encode against the reference's float64 run: 1e-12 rel-L2 for the
     output and for every level of encode_rp_intermediate(content)."""
     g = golden("ld")
-    m, ck = _model(g, i)
-    assert np.array_equal(ck, g[f"net{i}_checksum"]), i
+    m = _model(g, i)  # (its checksum is the recorded one)
     sd = m.state_dict()
     layers = int(g[f"net{i}_layers"])
     segs = (g[f"net{i}_cseg"], g[f"net{i}_sseg"]) if bool(g[f"net{i}_use_mask"]) else (None, None)
@@ -58,7 +52,7 @@ def test_restatement_matches_reference_float64(golden, i):
 @pytest.mark.parametrize("i", range(len(L.CASES)))
 def test_state_dict_keys_match_reference(golden, i):
     g = golden("ld")
-    m, _ = _model(g, i)
+    m = _model(g, i)
     names, shapes = L.key_table(m.state_dict())
     assert list(names) == list(g[f"net{i}_keys"])
     assert np.array_equal(shapes, g[f"net{i}_shapes"])

@@ -11,17 +11,12 @@ import os
 
 import numpy as np
 import pytest
-import torch
 
 from helpers import (SOURCE_CONFIG, deeper_config, multiscale_config, rel_l2, rp_config,
-                     state_dict_of, synth_)
+                     state_dict_of, synth_, t)
 from oracle import restate as R
 
 GOLD = os.path.join(os.path.dirname(__file__), "golden")
-
-
-def t(a):
-    return torch.from_numpy(np.ascontiguousarray(a))
 
 
 def test_stats_bitwise(golden):
