@@ -822,9 +822,18 @@ static int logits_rowstats(Mat Fq, int n, Mat G, float* S, float* rmax, float* r
 
 using namespace rpst;
 
+// the logits and their two softmax row vectors (the two-GEMM path; the flash path takes none)
+struct SanetLayout { float *S, *rmax, *rinv; size_t bytes; };
+static SanetLayout sanet_layout(void* workspace, int B, int HW) {
+  Carver c(workspace);
+  if (B <= 0 || HW <= 0) return {};
+  const size_t rows = (size_t)B * HW;
+  float *S = c.take(rows * HW), *rmax = c.take(rows), *rinv = c.take(rows);
+  return {S, rmax, rinv, c.bytes};
+}
+
 extern "C" size_t rpst_sanet_attention_workspace_size(int B, int HW) {
-  if (B <= 0 || HW <= 0) return 0;
-  return sizeof(float) * ((size_t)B * HW * HW + 2 * (size_t)B * HW);
+  return sanet_layout(nullptr, B, HW).bytes;
 }
 
 extern "C" size_t rpst_sanet_attention_workspace_size_c(int B, int C, int HW) {
@@ -839,29 +848,31 @@ extern "C" int rpst_sanet_attention(const float* F, const float* G, const float*
   RPST_REQUIRE(B > 0 && C > 0 && HW > 0, "sanet_attention: bad shape B=%d C=%d HW=%d", B, C, HW);
   RPST_REQUIRE(B <= 65535, "sanet_attention: batch too large");
   if (sanet_flash_ok(C, HW)) return sanet_flash(F, G, H, O, B, C, HW, as_stream(stream));
-  if (!workspace || workspace_bytes < rpst_sanet_attention_workspace_size(B, HW)) {
-    set_error("sanet_attention: workspace %zu < %zu bytes", workspace_bytes,
-              rpst_sanet_attention_workspace_size(B, HW));
-    return RPST_EWORKSPACE;
-  }
+  const SanetLayout L = sanet_layout(workspace, B, HW);
+  RPST_REQUIRE_WS(L.bytes, "sanet_attention: workspace %zu < %zu bytes", workspace_bytes, L.bytes);
   hipStream_t st = as_stream(stream);
-  float* S = static_cast<float*>(workspace);
-  float* rmax = S + (size_t)B * HW * HW;
-  float* rinv = rmax + (size_t)B * HW;
   const int64_t fhw = (int64_t)C * HW;
-  if (int e = logits_rowstats({F, HW, fhw}, HW, {G, HW, fhw}, S, rmax, rinv, B, C,
+  if (int e = logits_rowstats({F, HW, fhw}, HW, {G, HW, fhw}, L.S, L.rmax, L.rinv, B, C,
                               "gemm_f32_kernel(S=F^T G)", st))
     return e;
   // O[b][c][i] = (1/l_i) sum_j H[b][c][j] exp(S[b][i][j] - m_i)
-  launch_gemm<LAY_RK, LAY_RK, BX_EXP>({.A = {H, HW, fhw}, .B = {S, HW, (int64_t)HW * HW},
+  launch_gemm<LAY_RK, LAY_RK, BX_EXP>({.A = {H, HW, fhw}, .B = {L.S, HW, (int64_t)HW * HW},
                                        .C = {O, HW, fhw}, .M = C, .N = HW, .K = HW,
-                                       .rv = {.m = rmax}, .sV = HW, .colscale = rinv}, B, st);
+                                       .rv = {.m = L.rmax}, .sV = HW, .colscale = L.rinv}, B, st);
   return launch_status("gemm_f32_kernel(O=H P^T)");
 }
 
+// the column-normalised content and style features
+struct AffinityLayout { float *cn, *sn; size_t bytes; };
+static AffinityLayout affinity_layout(void* workspace, int B, int C, int HW) {
+  Carver c(workspace);
+  if (B <= 0 || C <= 0 || HW <= 0) return {};
+  float *cn = c.take((size_t)B * C * HW), *sn = c.take((size_t)B * C * HW);
+  return {cn, sn, c.bytes};
+}
+
 extern "C" size_t rpst_cosine_affinity_workspace_size(int B, int C, int HW) {
-  if (B <= 0 || C <= 0 || HW <= 0) return 0;
-  return sizeof(float) * 2 * (size_t)B * C * HW;
+  return affinity_layout(nullptr, B, C, HW).bytes;
 }
 
 extern "C" int rpst_cosine_affinity(const float* content, const float* style, float* out,
@@ -869,18 +880,23 @@ extern "C" int rpst_cosine_affinity(const float* content, const float* style, fl
                                     size_t workspace_bytes, rpst_stream_t stream) {
   RPST_REQUIRE(content && style && out, "cosine_affinity: null pointer");
   RPST_REQUIRE(B > 0 && C > 0 && HW > 0 && B <= 65535, "cosine_affinity: bad shape");
-  if (!workspace || workspace_bytes < rpst_cosine_affinity_workspace_size(B, C, HW)) {
-    set_error("cosine_affinity: workspace too small");
-    return RPST_EWORKSPACE;
-  }
-  float* cn = static_cast<float*>(workspace);
-  return affinity(content, style, out, cn, cn + (size_t)B * C * HW, B, C, HW,
-                  as_stream(stream));
+  const AffinityLayout L = affinity_layout(workspace, B, C, HW);
+  RPST_REQUIRE_WS(L.bytes, "cosine_affinity: workspace too small");
+  return affinity(content, style, out, L.cn, L.sn, B, C, HW, as_stream(stream));
+}
+
+// f_psi's hidden activations and the relu softmax's two row vectors
+struct ClampLayout { float *Z, *m2, *inv2; size_t bytes; };
+static ClampLayout clamp_layout(void* workspace, int B, int HW, int hidden) {
+  Carver c(workspace);
+  if (B <= 0 || HW <= 0 || hidden <= 0) return {};
+  const size_t rows = (size_t)B * HW;
+  float *Z = c.take(rows * hidden), *m2 = c.take(rows), *inv2 = c.take(rows);
+  return {Z, m2, inv2, c.bytes};
 }
 
 extern "C" size_t rpst_aea_clamp_workspace_size(int B, int HW, int hidden) {
-  if (B <= 0 || HW <= 0 || hidden <= 0) return 0;
-  return sizeof(float) * ((size_t)B * HW * hidden + 2 * (size_t)B * HW);
+  return clamp_layout(nullptr, B, HW, hidden).bytes;
 }
 
 extern "C" int rpst_aea_clamp(const float* x, const float* fx, const float* w1,
@@ -891,26 +907,21 @@ extern "C" int rpst_aea_clamp(const float* x, const float* fx, const float* w1,
   RPST_REQUIRE(x && fx && w1 && b1 && w2 && b2 && out_fx && out_clamp, "aea_clamp: null pointer");
   RPST_REQUIRE(B > 0 && HW > 0 && hidden > 0 && B <= 65535, "aea_clamp: bad shape");
   RPST_REQUIRE(mode == 0 || mode == 1, "aea_clamp: mode must be 0 (aea) or 1 (relu)");
-  if (!workspace || workspace_bytes < rpst_aea_clamp_workspace_size(B, HW, hidden)) {
-    set_error("aea_clamp: workspace too small");
-    return RPST_EWORKSPACE;
-  }
+  const ClampLayout L = clamp_layout(workspace, B, HW, hidden);
+  RPST_REQUIRE_WS(L.bytes, "aea_clamp: workspace too small");
   hipStream_t st = as_stream(stream);
-  float* Z = static_cast<float*>(workspace);
-  float* m2 = Z + (size_t)B * HW * hidden;
-  float* inv2 = m2 + (size_t)B * HW;
-  if (int e = clamp_values(x, w1, b1, w2, b2, hidden, mode, from, interval, Z, out_clamp, B,
+  if (int e = clamp_values(x, w1, b1, w2, b2, hidden, mode, from, interval, L.Z, out_clamp, B,
                            HW, st))
     return e;
   const int64_t rows = (int64_t)B * HW;
   if (mode == 1) {
     rowstats_relu_kernel<false><<<(unsigned)((rows + 3) / 4), 256, 0, st>>>(
-        fx, nullptr, nullptr, out_clamp, m2, inv2, rows, HW);
+        fx, nullptr, nullptr, out_clamp, L.m2, L.inv2, rows, HW);
     if (int e = launch_status("rowstats_relu_kernel(fx)")) return e;
   }
   const int64_t n = rows * HW;
-  aea_apply_kernel<<<(unsigned)((n + 255) / 256), 256, 0, st>>>(fx, out_clamp, m2, inv2, out_fx,
-                                                                rows, HW, mode, scale);
+  aea_apply_kernel<<<(unsigned)((n + 255) / 256), 256, 0, st>>>(fx, out_clamp, L.m2, L.inv2,
+                                                                out_fx, rows, HW, mode, scale);
   return launch_status("aea_apply_kernel");
 }
 
@@ -942,17 +953,31 @@ static int adaptive_claims(const float* S, const float* rmax, const float* rinv,
   return RPST_OK;
 }
 
-// the logits' region first holds T = sn W1^T (C x hidden per image): whichever is larger.
-// On the flash path (sanet_flash_ok) S is never formed: T only.
-static size_t sq_or_t(int B, int C, int HW, int hidden) {
-  if (sanet_flash_ok(C, HW)) return clamp_t_floats(B, C, HW, hidden);
-  return std::max((size_t)B * HW * HW, clamp_t_floats(B, C, HW, hidden));
+struct AdaptiveLayout {
+  float* S;  // T = sn W1^T (C x hidden per image) first, then the logits
+  float *Z, *cn, *sn;
+  float *rmax, *rinv, *clamp, *m2, *inv2;  // (B, HW) each
+  float *cmax, *cinv;  // (B, HW) each: the flash path's row statistics of the kept maps
+  size_t bytes;
+};
+static AdaptiveLayout adaptive_layout(void* workspace, int B, int C, int HW, int hidden) {
+  Carver c(workspace);
+  AdaptiveLayout L{};
+  if (B <= 0 || C <= 0 || HW <= 0 || hidden <= 0) return L;
+  const size_t rows = (size_t)B * HW, t = clamp_t_floats(B, C, HW, hidden);
+  // whichever of T and S is larger; on the flash path (sanet_flash_ok) S is never formed
+  L.S = c.take(sanet_flash_ok(C, HW) ? t : std::max(rows * HW, t));
+  L.Z = c.take(rows * hidden);
+  L.cn = c.take(rows * C);
+  L.sn = c.take(rows * C);
+  for (float** r : {&L.rmax, &L.rinv, &L.clamp, &L.m2, &L.inv2, &L.cmax, &L.cinv})
+    *r = c.take(rows);
+  L.bytes = c.bytes;
+  return L;
 }
 
 extern "C" size_t rpst_adaptive_attention_workspace_size(int B, int C, int HW, int hidden) {
-  if (B <= 0 || C <= 0 || HW <= 0 || hidden <= 0) return 0;
-  return sizeof(float) * (sq_or_t(B, C, HW, hidden) + (size_t)B * HW * hidden +
-                          2 * (size_t)B * C * HW + 7 * (size_t)B * HW);
+  return adaptive_layout(nullptr, B, C, HW, hidden).bytes;
 }
 
 extern "C" int rpst_adaptive_attention(const float* F, const float* G, const float* H,
@@ -968,22 +993,12 @@ extern "C" int rpst_adaptive_attention(const float* F, const float* G, const flo
   RPST_REQUIRE(B > 0 && C > 0 && HW > 0 && hidden > 0 && B <= 65535,
                "adaptive_attention: bad shape B=%d C=%d HW=%d hidden=%d", B, C, HW, hidden);
   RPST_REQUIRE(mode == 0 || mode == 1, "adaptive_attention: mode must be 0 (aea) or 1 (relu)");
-  if (!workspace ||
-      workspace_bytes < rpst_adaptive_attention_workspace_size(B, C, HW, hidden)) {
-    set_error("adaptive_attention: workspace %zu < %zu bytes", workspace_bytes,
-              rpst_adaptive_attention_workspace_size(B, C, HW, hidden));
-    return RPST_EWORKSPACE;
-  }
+  const AdaptiveLayout L = adaptive_layout(workspace, B, C, HW, hidden);
+  RPST_REQUIRE_WS(L.bytes, "adaptive_attention: workspace %zu < %zu bytes", workspace_bytes,
+                  L.bytes);
   hipStream_t st = as_stream(stream);
-  float* S = static_cast<float*>(workspace);  // T = sn W1^T first, then the logits
-  float* Z = S + sq_or_t(B, C, HW, hidden);
-  float* cn = Z + (size_t)B * HW * hidden;
-  float* sn = cn + (size_t)B * C * HW;
-  float* rmax = sn + (size_t)B * C * HW;
-  float* rinv = rmax + (size_t)B * HW;
-  float* clamp = rinv + (size_t)B * HW;
-  float* m2 = clamp + (size_t)B * HW;
-  float* inv2 = m2 + (size_t)B * HW;
+  float *S = L.S, *Z = L.Z, *cn = L.cn, *sn = L.sn;
+  float *rmax = L.rmax, *rinv = L.rinv, *clamp = L.clamp, *m2 = L.m2, *inv2 = L.inv2;
   // 1. clamp values from the cosine affinity of the raw features (sanet.py:110, 45 / 66), the
   //    affinity folded into f_psi's first Linear (T in the logits' buffer, not yet written)
   if (int e = col_norms(content, style, cn, sn, B, C, HW, st)) return e;
@@ -999,13 +1014,11 @@ extern "C" int rpst_adaptive_attention(const float* F, const float* G, const flo
     // summation order, would put the maps ~1e-5 off the logits they transform, amplified by
     // the slope-50 sigmoid)
     float* Sx = claim_before ? claim_before : claim_after;
-    float* cmax = inv2 + (size_t)B * HW;
-    float* cinv = cmax + (size_t)B * HW;
     if (Sx)
-      if (int e = logits_rowstats(Fm, HW, Gm, Sx, cmax, cinv, B, C,
+      if (int e = logits_rowstats(Fm, HW, Gm, Sx, L.cmax, L.cinv, B, C,
                                   "gemm_f32_kernel(S=F^T G, claims)", st))
         return e;
-    if (int e = adaptive_claims(Sx, cmax, cinv, clamp, m2, inv2, scale, mode, claim_value,
+    if (int e = adaptive_claims(Sx, L.cmax, L.cinv, clamp, m2, inv2, scale, mode, claim_value,
                                 claim_before, claim_after, B, HW, st))
       return e;
     // 3. pass 2: S recomputed per key block, Q formed in registers, O = H Q^T
@@ -1119,17 +1132,19 @@ static int attention_backward_walk(const float* F, const float* G, const float* 
   return RPST_OK;
 }
 
-// S_q, dP_q and their two row vectors, in this order
-static WalkScratch sanet_walk_scratch(void* workspace, int B, int qc, int HWs) {
-  float* S = static_cast<float*>(workspace);
-  float* dP = S + (size_t)B * qc * HWs;
-  float* rmax = dP + (size_t)B * qc * HWs;
-  return {.S = S, .dP = dP, .rmax = rmax, .rinv = rmax + (size_t)B * qc};
+// S_q, dP_q and their two row vectors, in this order, for chunks of qc queries
+struct WalkLayout { WalkScratch w; size_t bytes; };
+static WalkLayout sanet_walk_layout(void* workspace, int B, int qc, int HWs) {
+  Carver c(workspace);
+  if (B <= 0 || qc <= 0 || HWs <= 0) return {};
+  const size_t rows = (size_t)B * qc;
+  float *S = c.take(rows * HWs), *dP = c.take(rows * HWs);
+  float *rmax = c.take(rows), *rinv = c.take(rows);
+  return {{.S = S, .dP = dP, .rmax = rmax, .rinv = rinv}, c.bytes};
 }
 
 extern "C" size_t rpst_sanet_attention_backward_workspace_size(int B, int HWc, int HWs) {
-  if (B <= 0 || HWc <= 0 || HWs <= 0) return 0;
-  return sizeof(float) * (2 * (size_t)B * HWc * HWs + 2 * (size_t)B * HWc);
+  return sanet_walk_layout(nullptr, B, HWc, HWs).bytes;
 }
 
 extern "C" int rpst_sanet_attention_backward(const float* F, const float* G, const float* H,
@@ -1139,24 +1154,19 @@ extern "C" int rpst_sanet_attention_backward(const float* F, const float* G, con
   RPST_REQUIRE(F && G && H && dO && dF && dG && dH, "sanet_attention_backward: null pointer");
   RPST_REQUIRE(B > 0 && C > 0 && HWc > 0 && HWs > 0 && B <= 65535,
                "sanet_attention_backward: bad shape B=%d C=%d HW=%d/%d", B, C, HWc, HWs);
-  if (!workspace ||
-      workspace_bytes < rpst_sanet_attention_backward_workspace_size(B, HWc, HWs)) {
-    set_error("sanet_attention_backward: workspace too small");
-    return RPST_EWORKSPACE;
-  }
+  const WalkLayout L = sanet_walk_layout(workspace, B, HWc, HWs);
+  RPST_REQUIRE_WS(L.bytes, "sanet_attention_backward: workspace too small");
   constexpr WalkNames names{"gemm_f32_kernel(S=F^T G)", "gemm_f32_kernel(dH=dO P)",
                             "gemm_f32_kernel(dP=dO^T H)", "gemm_f32_kernel(dF=G dS^T)",
                             "gemm_f32_kernel(dG=F dS)"};
   return attention_backward_walk(F, G, H, dO, dF, dG, dH, B, C, HWc, HWs, HWc,
-                                 sanet_walk_scratch(workspace, B, HWc, HWs), nullptr, names,
-                                 as_stream(stream));
+                                 L.w, nullptr, names, as_stream(stream));
 }
 
 extern "C" size_t rpst_sanet_attention_backward_chunked_workspace_size(int B, int C, int HWc,
                                                                        int HWs) {
-  if (B <= 0 || C <= 0 || HWc <= 0 || HWs <= 0) return 0;
-  const size_t qc = (size_t)std::min(HWc, kAttnQC);
-  return sizeof(float) * (2 * (size_t)B * qc * HWs + 2 * (size_t)B * qc);
+  if (C <= 0) return 0;
+  return sanet_walk_layout(nullptr, B, std::min(HWc, kAttnQC), HWs).bytes;
 }
 
 extern "C" int rpst_sanet_attention_backward_chunked(const float* F, const float* G,
@@ -1169,15 +1179,11 @@ extern "C" int rpst_sanet_attention_backward_chunked(const float* F, const float
                "sanet_attention_backward_chunked: null pointer");
   RPST_REQUIRE(B > 0 && C > 0 && HWc > 0 && HWs > 0 && B <= 65535,
                "sanet_attention_backward_chunked: bad shape B=%d C=%d HW=%d/%d", B, C, HWc, HWs);
-  if (!workspace ||
-      workspace_bytes < rpst_sanet_attention_backward_chunked_workspace_size(B, C, HWc, HWs)) {
-    set_error("sanet_attention_backward_chunked: workspace too small");
-    return RPST_EWORKSPACE;
-  }
   const int qc = std::min(HWc, kAttnQC);
-  return attention_backward_walk(F, G, H, dO, dF, dG, dH, B, C, HWc, HWs, qc,
-                                 sanet_walk_scratch(workspace, B, qc, HWs), nullptr, kChunkNames,
-                                 as_stream(stream));
+  const WalkLayout L = sanet_walk_layout(workspace, B, qc, HWs);
+  RPST_REQUIRE_WS(L.bytes, "sanet_attention_backward_chunked: workspace too small");
+  return attention_backward_walk(F, G, H, dO, dF, dG, dH, B, C, HWc, HWs, qc, L.w, nullptr,
+                                 kChunkNames, as_stream(stream));
 }
 
 // K (pixel) chunks per image of the 1x1 weight gradient: the per-image GEMM has only
@@ -1190,6 +1196,7 @@ static int wgrad1x1_ks(int N, int Cin, int Cout) {
   return (int)std::max<int64_t>(1, std::min<int64_t>(ks, 16));
 }
 
+// one region: part[N * wgrad1x1_ks][Cout][Cin], a dW partial per image and pixel chunk
 extern "C" size_t rpst_conv1x1_wgrad_workspace_size(int N, int Cin, int Cout) {
   if (N <= 0 || Cin <= 0 || Cout <= 0) return 0;
   return sizeof(float) * (size_t)N * wgrad1x1_ks(N, Cin, Cout) * Cin * Cout;
@@ -1201,10 +1208,8 @@ extern "C" int rpst_conv1x1_wgrad(const float* x, const float* dy, float* dw, fl
   RPST_REQUIRE(x && dy && dw, "conv1x1_wgrad: null pointer");
   RPST_REQUIRE(N > 0 && Cin > 0 && Cout > 0 && HW > 0 && HW <= 0x7fffffffLL && N <= 65535,
                "conv1x1_wgrad: bad shape");
-  if (!workspace || workspace_bytes < rpst_conv1x1_wgrad_workspace_size(N, Cin, Cout)) {
-    set_error("conv1x1_wgrad: workspace too small");
-    return RPST_EWORKSPACE;
-  }
+  RPST_REQUIRE_WS(rpst_conv1x1_wgrad_workspace_size(N, Cin, Cout),
+                  "conv1x1_wgrad: workspace too small");
   hipStream_t st = as_stream(stream);
   float* part = static_cast<float*>(workspace);
   // part[n][co][ci] = sum_p dy[n][co][p] x[n][ci][p]
@@ -1226,17 +1231,42 @@ extern "C" int rpst_conv1x1_wgrad(const float* x, const float* dy, float* dw, fl
   return RPST_OK;
 }
 
+struct AdaptiveBwdLayout {
+  int qc, chunks;    // queries per walk chunk; kColChunk-row chunks of the column sums
+  float* Aff;        // T, then R (C x hidden per image), never the affinity
+  float *Sq, *dQq;   // S and dQ of one query chunk: [B][qc][HW] each
+  float *Z, *du;     // [B][HW][hidden] each
+  float *cn, *sn;    // [B][C][HW] each
+  float *clamp, *dc, *dt;                        // [B][HW] each
+  float *rmax, *rinv, *clq, *m2, *inv2, *dcq;    // per query chunk: [B][qc] each
+  float* w1part;     // [B][hidden][HW]: the per-image dW1 partials
+  float* cpart;      // [chunks][3][hidden + 1]: the column-sum chunk partials
+  size_t bytes;
+};
+static AdaptiveBwdLayout adaptive_bwd_layout(void* workspace, int B, int C, int HW,
+                                             int hidden) {
+  Carver c(workspace);
+  AdaptiveBwdLayout L{};
+  if (B <= 0 || C <= 0 || HW <= 0 || hidden <= 0) return L;
+  const size_t rows = (size_t)B * HW;
+  L.qc = std::min(HW, kAttnQC);
+  L.chunks = (int)((rows + kColChunk - 1) / kColChunk);
+  L.Aff = c.take(clamp_t_floats(B, C, HW, hidden));
+  for (float** r : {&L.Sq, &L.dQq}) *r = c.take((size_t)B * L.qc * HW);
+  for (float** r : {&L.Z, &L.du}) *r = c.take(rows * hidden);
+  for (float** r : {&L.cn, &L.sn}) *r = c.take(rows * C);
+  for (float** r : {&L.clamp, &L.dc, &L.dt}) *r = c.take(rows);
+  for (float** r : {&L.rmax, &L.rinv, &L.clq, &L.m2, &L.inv2, &L.dcq})
+    *r = c.take((size_t)B * L.qc);
+  L.w1part = c.take(rows * hidden);
+  L.cpart = c.take(3 * (size_t)(hidden + 1) * L.chunks);
+  L.bytes = c.bytes;
+  return L;
+}
+
 extern "C" size_t rpst_adaptive_attention_backward_workspace_size(int B, int C, int HW,
                                                                   int hidden) {
-  if (B <= 0 || C <= 0 || HW <= 0 || hidden <= 0) return 0;
-  const size_t qc = (size_t)std::min(HW, kAttnQC);
-  const size_t chunks = ((size_t)B * HW + kColChunk - 1) / kColChunk;
-  // (the first region holds T and then R, C x hidden per image, never the affinity) + S and
-  // dQ of one query chunk + the per-image dW1 partials and the column-sum chunk partials
-  return sizeof(float) * (clamp_t_floats(B, C, HW, hidden) + 2 * (size_t)B * qc * HW +
-                          2 * (size_t)B * HW * hidden + 2 * (size_t)B * C * HW +
-                          3 * (size_t)B * HW + 6 * (size_t)B * qc + (size_t)B * hidden * HW +
-                          3 * (size_t)(hidden + 1) * chunks);
+  return adaptive_bwd_layout(nullptr, B, C, HW, hidden).bytes;
 }
 
 extern "C" int rpst_adaptive_attention_backward(
@@ -1253,51 +1283,30 @@ extern "C" int rpst_adaptive_attention_backward(
                "adaptive_attention_backward: bad shape B=%d C=%d HW=%d hidden=%d", B, C, HW,
                hidden);
   RPST_REQUIRE(mode == 0 || mode == 1, "adaptive_attention_backward: mode must be 0 or 1");
-  if (!workspace ||
-      workspace_bytes < rpst_adaptive_attention_backward_workspace_size(B, C, HW, hidden)) {
-    set_error("adaptive_attention_backward: workspace too small");
-    return RPST_EWORKSPACE;
-  }
+  const AdaptiveBwdLayout L = adaptive_bwd_layout(workspace, B, C, HW, hidden);
+  RPST_REQUIRE_WS(L.bytes, "adaptive_attention_backward: workspace too small");
   hipStream_t st = as_stream(stream);
-  const int qc = std::min(HW, kAttnQC);
-  const int64_t fhw = (int64_t)C * HW, rows = (int64_t)B * HW, sq = (int64_t)qc * HW;
-  float* Aff = static_cast<float*>(workspace);  // T, then R (C x hidden per image)
-  float* Sq = Aff + clamp_t_floats(B, C, HW, hidden);  // S and dQ of one query chunk
-  float* dQq = Sq + (size_t)B * sq;
-  float* Z = dQq + (size_t)B * sq;
-  float* du = Z + (size_t)rows * hidden;
-  float* cn = du + (size_t)rows * hidden;
-  float* sn = cn + (size_t)B * fhw;
-  float* clamp = sn + (size_t)B * fhw;
-  float* dc = clamp + rows;
-  float* dt = dc + rows;
-  float* rmax = dt + rows;  // per query chunk: [B][qc] each
-  float* rinv = rmax + (size_t)B * qc;
-  float* clq = rinv + (size_t)B * qc;
-  float* m2 = clq + (size_t)B * qc;
-  float* inv2 = m2 + (size_t)B * qc;
-  float* dcq = inv2 + (size_t)B * qc;
-  float* w1part = dcq + (size_t)B * qc;                    // [B][hidden][HW]
-  float* cpart = w1part + (size_t)B * hidden * HW;         // [chunks][3][hidden + 1]
+  const int64_t fhw = (int64_t)C * HW, rows = (int64_t)B * HW;
+  float *Aff = L.Aff, *Z = L.Z, *du = L.du, *cn = L.cn, *sn = L.sn, *dt = L.dt;
   // forward quantities: clamp (and Z) as the forward forms them (the affinity folded into
   // f_psi's first Linear; T in the Aff region), logits, softmax / relu-softmax statistics
   if (int e = col_norms(content, style, cn, sn, B, C, HW, st)) return e;
   if (int e = clamp_values_factored(cn, sn, w1, b1, w2, b2, hidden, mode, from, interval, Aff,
-                                    Z, clamp, B, C, HW, st))
+                                    Z, L.clamp, B, C, HW, st))
     return e;
   // attention part over query chunks of whole rows: S_q, its softmax / relu-softmax
   // statistics, dH += dO_q Q_q, dQ_q = dO_q^T H -> dS_q and dc, dF_q = G dS_q^T, dG += F_q dS_q
-  const WalkAdaptive ad{.clamp = clamp, .mode = mode, .scale = scale, .dc = dc, .clq = clq,
-                        .m2 = m2, .inv2 = inv2, .dcq = dcq};
+  const WalkAdaptive ad{.clamp = L.clamp, .mode = mode, .scale = scale, .dc = L.dc,
+                        .clq = L.clq, .m2 = L.m2, .inv2 = L.inv2, .dcq = L.dcq};
   WalkNames names = kChunkNames;
   names.dh = "gemm_f32_kernel(dH+=dO_q Q_q)";
   names.dp = "gemm_f32_kernel(dQ_q=dO_q^T H)";
-  if (int e = attention_backward_walk(F, G, H, dO, dF, dG, dH, B, C, HW, HW, qc,
-                                      {.S = Sq, .dP = dQq, .rmax = rmax, .rinv = rinv}, &ad,
-                                      names, st))
+  if (int e = attention_backward_walk(F, G, H, dO, dF, dG, dH, B, C, HW, HW, L.qc,
+                                      {.S = L.Sq, .dP = L.dQq, .rmax = L.rmax, .rinv = L.rinv},
+                                      &ad, names, st))
     return e;
   // f_psi: dt, du, then dW1 = du^T Aff over all B * HW query rows (one GEMM), the column sums
-  fpsi_bwd_rows_kernel<<<(unsigned)((rows + 3) / 4), 256, 0, st>>>(Z, w2, b2, dc, dt, du, rows,
+  fpsi_bwd_rows_kernel<<<(unsigned)((rows + 3) / 4), 256, 0, st>>>(Z, w2, b2, L.dc, dt, du, rows,
                                                                    hidden, mode, interval);
   if (int e = launch_status("fpsi_bwd_rows_kernel")) return e;
   // dW1 = du^T A per image with A = cn^T sn never formed: R = cn du (C x hidden, K = HW),
@@ -1311,15 +1320,15 @@ extern "C" int rpst_adaptive_attention_backward(
   if (int e = launch_status("gemm_f32_kernel(R_b=cn_b du_b)")) return e;
   // w1part[b][n][j] = sum_c R[b][c][n] sn[b][c][j]
   launch_gemm<LAY_KR, LAY_KR, BX_NONE>({.A = {R, hidden, nr}, .B = {sn, HW, fhw},
-                                        .C = {w1part, HW, nw1}, .M = hidden, .N = HW, .K = C}, B,
+                                        .C = {L.w1part, HW, nw1}, .M = hidden, .N = HW, .K = C}, B,
                                        st);
   if (int e = launch_status("gemm_f32_kernel(dW1_b=R_b^T sn_b)")) return e;
-  if (int e = partial_sum(w1part, dw1, nw1, B, 1, "partial_sum_kernel(dW1)", st)) return e;
-  const int chunks = (int)((rows + kColChunk - 1) / kColChunk);
+  if (int e = partial_sum(L.w1part, dw1, nw1, B, 1, "partial_sum_kernel(dW1)", st)) return e;
+  const int chunks = L.chunks;
   fpsi_colsum_part_kernel<<<dim3((unsigned)((hidden + 1 + 255) / 256), (unsigned)chunks), 256, 0,
-                            st>>>(Z, du, dt, cpart, rows, hidden);
+                            st>>>(Z, du, dt, L.cpart, rows, hidden);
   if (int e = launch_status("fpsi_colsum_part_kernel")) return e;
-  fpsi_colsum_final_kernel<<<(hidden + 1 + 255) / 256, 256, 0, st>>>(cpart, dw2, db1, db2, chunks,
+  fpsi_colsum_final_kernel<<<(hidden + 1 + 255) / 256, 256, 0, st>>>(L.cpart, dw2, db1, db2, chunks,
                                                                     hidden);
   return launch_status("fpsi_colsum_final_kernel");
 }

@@ -11,6 +11,7 @@
 #include <cstddef>
 #include <cstdint>
 #include <cstdio>
+#include <initializer_list>
 
 #include "../../include/rpst.h"
 
@@ -29,6 +30,22 @@ inline int launch_status(const char* what) {
   }
   return RPST_OK;
 }
+
+// A workspace is described once: a layout function takes its regions in order from a Carver
+// on the caller's buffer and returns their pointers plus `bytes`. On a null base the same
+// function only counts, and that is the *_workspace_size export. No padding, no alignment:
+// a region starts where the one before it ends.
+struct Carver {
+  char* base;
+  size_t bytes = 0;
+  explicit Carver(void* workspace) : base(static_cast<char*>(workspace)) {}
+  template <typename T = float>
+  T* take(size_t n) {
+    T* p = base ? reinterpret_cast<T*>(base + bytes) : nullptr;
+    bytes += n * sizeof(T);
+    return p;
+  }
+};
 
 constexpr int kWave = 64;
 
@@ -71,10 +88,15 @@ int wct_apply_f32(const double* T, const double* c, const float* x, float* z, in
 
 }  // namespace rpst
 
-#define RPST_REQUIRE(cond, ...)          \
-  do {                                   \
-    if (!(cond)) {                       \
-      ::rpst::set_error(__VA_ARGS__);    \
-      return RPST_EINVAL;                \
-    }                                    \
+#define RPST_REQUIRE_OR(status, cond, ...) \
+  do {                                     \
+    if (!(cond)) {                         \
+      ::rpst::set_error(__VA_ARGS__);      \
+      return status;                       \
+    }                                      \
   } while (0)
+#define RPST_REQUIRE(cond, ...) RPST_REQUIRE_OR(RPST_EINVAL, cond, __VA_ARGS__)
+// For an entry point's body only: reads its `workspace` and `workspace_bytes` parameters, which
+// every entry point of include/rpst.h spells this way. They hold `need` bytes, or RPST_EWORKSPACE.
+#define RPST_REQUIRE_WS(need, ...)                                                    \
+  RPST_REQUIRE_OR(RPST_EWORKSPACE, workspace && workspace_bytes >= (need), __VA_ARGS__)

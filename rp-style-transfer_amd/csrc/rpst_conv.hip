@@ -1141,10 +1141,7 @@ extern "C" int rpst_conv2d_ws(const float* input, const float* aux, const float*
   RPST_REQUIRE(in_op != RPST_IN_ADD_ADAIN, "conv2d: ADD_ADAIN goes through rpst_conv2d_skip_adain");
   const ConvMode m = conv_mode();
   const size_t need = fold_bytes(N, Cin, Hs, Ws, Cout, ksize, in_op, m);
-  if (need && (!workspace || workspace_bytes < need)) {
-    set_error("conv2d: workspace %zu < %zu bytes", workspace_bytes, need);
-    return RPST_EWORKSPACE;
-  }
+  if (need) RPST_REQUIRE_WS(need, "conv2d: workspace %zu < %zu bytes", workspace_bytes, need);
   return conv_common({.input = input, .aux = aux, .packed_weight = packed_weight, .bias = bias,
                       .residual = residual, .out = out, .N = N, .Cin = Cin, .Hs = Hs, .Ws = Ws,
                       .Cout = Cout, .ksize = ksize, .pad_mode = pad_mode, .in_op = in_op,
@@ -1157,16 +1154,29 @@ extern "C" int rpst_conv2d_ws(const float* input, const float* aux, const float*
 // biases (wino4_mix); other layers materialise z = T x + c (fp32 MFMA GEMM) and convolve it.
 // The fold does not depend on the quarter setting, and neither does its size (wino4_mix_floats
 // takes the larger weight image); at precise level 1 the layer runs F(2x2) on z.
-static size_t mix_bytes(int N, int Cin, int H, int W, int Cout, int ksize, const ConvMode& m) {
-  if (bad_shape(N, Cin, H, W, Cout, ksize)) return 0;
-  if (plan_folds(N, Cin, H, W, Cout, ksize, RPST_IN_NONE, m))
-    return (wino4_mix_floats(N, Cin, Cout) + 64) * sizeof(float);
-  return ((size_t)N * Cin * H * W + wct_apply_scratch_floats(N, Cin) + 64) * sizeof(float);
+// fold: the per-image weights and border biases; else z = T x + c, then wct_apply_f32's
+// scratch. Known fault, kept as it was: a ksize other than 1 or 3 sizes as 0 bytes but is
+// carved like a direct layer, and rpst_conv2d_mix writes z before conv_common refuses the ksize.
+struct MixLayout { float *fold_ws, *z, *scratch; size_t bytes; };
+static MixLayout mix_layout(void* workspace, int N, int Cin, int H, int W, int Cout, int ksize,
+                            const ConvMode& m) {
+  Carver c(workspace);
+  MixLayout L{};
+  if (bad_shape(N, Cin, H, W, Cout, 1)) return L;
+  if (plan_folds(N, Cin, H, W, Cout, ksize, RPST_IN_NONE, m)) {
+    L.fold_ws = c.take(wino4_mix_floats(N, Cin, Cout));
+  } else {
+    L.z = c.take((size_t)N * Cin * H * W);
+    L.scratch = c.take(wct_apply_scratch_floats(N, Cin));
+  }
+  c.take(64);  // spare floats the size has always carried
+  L.bytes = ksize == 1 || ksize == 3 ? c.bytes : 0;
+  return L;
 }
 
 extern "C" size_t rpst_conv2d_mix_workspace_size(int N, int Cin, int H, int W, int Cout,
                                                  int ksize) {
-  return mix_bytes(N, Cin, H, W, Cout, ksize, conv_mode());
+  return mix_layout(nullptr, N, Cin, H, W, Cout, ksize, conv_mode()).bytes;
 }
 
 extern "C" int rpst_conv2d_mix(const float* input, const double* T, const double* offset,
@@ -1177,22 +1187,16 @@ extern "C" int rpst_conv2d_mix(const float* input, const double* T, const double
   RPST_REQUIRE(input && T && offset && packed_weight && out, "conv2d_mix: null pointer");
   RPST_REQUIRE(N > 0 && Cin > 0 && Cout > 0 && H > 0 && W > 0, "conv2d_mix: bad shape");
   const ConvMode m = conv_mode();
-  const size_t need = mix_bytes(N, Cin, H, W, Cout, ksize, m);
-  if (!workspace || workspace_bytes < need) {
-    set_error("conv2d_mix: workspace %zu < %zu bytes", workspace_bytes, need);
-    return RPST_EWORKSPACE;
-  }
+  const MixLayout L = mix_layout(workspace, N, Cin, H, W, Cout, ksize, m);
+  RPST_REQUIRE_WS(L.bytes, "conv2d_mix: workspace %zu < %zu bytes", workspace_bytes, L.bytes);
   ConvReq r{.input = input, .packed_weight = packed_weight, .bias = bias, .out = out, .N = N,
             .Cin = Cin, .Hs = H, .Ws = W, .Cout = Cout, .ksize = ksize, .pad_mode = pad_mode,
             .in_op = RPST_IN_NONE, .relu = relu, .st = as_stream(stream),
-            .fold_ws = static_cast<float*>(workspace), .T = T, .offset = offset};
-  if (!plan_folds(N, Cin, H, W, Cout, ksize, RPST_IN_NONE, m)) {
-    float* z = r.fold_ws;
-    if (int e = wct_apply_f32(T, offset, input, z, N, Cin, (int64_t)H * W,
-                              z + (size_t)N * Cin * H * W, r.st))
+            .fold_ws = L.fold_ws, .T = T, .offset = offset};
+  if (L.z) {
+    if (int e = wct_apply_f32(T, offset, input, L.z, N, Cin, (int64_t)H * W, L.scratch, r.st))
       return e;
-    r.input = z;
-    r.fold_ws = nullptr;
+    r.input = L.z;
     r.T = r.offset = nullptr;
   }
   return conv_common(r, m);
@@ -1258,10 +1262,7 @@ static int conv2d_stats_impl(ConvReq r, float* mean, float* std_out, float eps, 
   const ConvMode m = conv_mode();
   const size_t sb = stat_bytes(r.N, r.Cin, r.Hs, r.Ws, r.Cout, r.ksize, r.in_op, m);
   const size_t need = sb + fold_bytes(r.N, r.Cin, r.Hs, r.Ws, r.Cout, r.ksize, r.in_op, m);
-  if (!workspace || workspace_bytes < need) {
-    set_error("conv2d_stats: workspace %zu < %zu bytes", workspace_bytes, need);
-    return RPST_EWORKSPACE;
-  }
+  RPST_REQUIRE_WS(need, "conv2d_stats: workspace %zu < %zu bytes", workspace_bytes, need);
   r.stat_part = static_cast<float2*>(workspace);
   r.skip_from = store_n < r.N ? store_n : 0;
   ConvArgs a;
@@ -1341,10 +1342,7 @@ extern "C" int rpst_conv2d_gated(const float* input, const float* packed_weight,
   const ConvMode m = conv_mode();
   if (!mean) return conv_common(r, m);
   const size_t sb = gated_stat_bytes(N, Cin, H, W, Cout, ksize);
-  if (sb && (!workspace || workspace_bytes < sb)) {
-    set_error("conv2d_gated: workspace %zu < %zu bytes", workspace_bytes, sb);
-    return RPST_EWORKSPACE;
-  }
+  if (sb) RPST_REQUIRE_WS(sb, "conv2d_gated: workspace %zu < %zu bytes", workspace_bytes, sb);
   if (!sb) {  // no statistics epilogue on this tile: convolve, then reduce the output
     if (int e = conv_common(r, m)) return e;
     return rpst_calc_mean_std(out, mean, std_out, N, Cout, (int64_t)H * W, eps, stream);

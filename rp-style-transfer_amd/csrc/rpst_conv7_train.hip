@@ -183,16 +183,25 @@ __global__ __launch_bounds__(256) void reflect_pad_backward_kernel(
   dx[t] = s;
 }
 
-static void wgrad7_geometry(int N, int Cin, int H, int W, int Cout, int* splits,
-                            int64_t* segs_per_split) {
-  const int tiles = ((Cout + kW7TC - 1) / kW7TC) * ((Cin + kW7TC - 1) / kW7TC) * 7;
+// The launch geometry and the partials it writes: part[splits][Cout][Cin][49], then
+// bpart[splits][Cout].
+struct Wgrad7Layout { int64_t tiles, sps; int splits; float *part, *bpart; size_t bytes; };
+static Wgrad7Layout wgrad7_layout(void* workspace, int N, int Cin, int H, int W, int Cout) {
+  Carver c(workspace);
+  Wgrad7Layout L{};
+  if (N <= 0 || Cin <= 0 || H <= 0 || W <= 0 || Cout <= 0) return L;
+  L.tiles = (int64_t)((Cout + kW7TC - 1) / kW7TC) * ((Cin + kW7TC - 1) / kW7TC) * 7;
   const int64_t segs = (int64_t)N * H * ((W + kW7PX - 1) / kW7PX);
   // ~1024 workgroups in all (two a CU, two rounds), at least 4 segments each
-  int64_t s = (1024 + tiles - 1) / tiles;
+  int64_t s = (1024 + L.tiles - 1) / L.tiles;
   if (s > segs / 4) s = segs / 4;
   if (s < 1) s = 1;
-  *segs_per_split = (segs + s - 1) / s;
-  *splits = (int)((segs + *segs_per_split - 1) / *segs_per_split);
+  L.sps = (segs + s - 1) / s;
+  L.splits = (int)((segs + L.sps - 1) / L.sps);
+  L.part = c.take((size_t)L.splits * Cout * Cin * 49);
+  L.bpart = c.take((size_t)L.splits * Cout);
+  L.bytes = c.bytes;
+  return L;
 }
 
 }  // namespace rpst
@@ -200,11 +209,7 @@ static void wgrad7_geometry(int N, int Cin, int H, int W, int Cout, int* splits,
 using namespace rpst;
 
 extern "C" size_t rpst_conv7_wgrad_workspace_size(int N, int Cin, int H, int W, int Cout) {
-  if (N <= 0 || Cin <= 0 || H <= 0 || W <= 0 || Cout <= 0) return 0;
-  int splits;
-  int64_t sps;
-  wgrad7_geometry(N, Cin, H, W, Cout, &splits, &sps);
-  return sizeof(float) * (size_t)splits * Cout * ((size_t)Cin * 49 + 1);
+  return wgrad7_layout(nullptr, N, Cin, H, W, Cout).bytes;
 }
 
 extern "C" int rpst_conv7_wgrad(const float* x, const float* dy, float* dw, float* db, int N,
@@ -220,28 +225,20 @@ extern "C" int rpst_conv7_wgrad(const float* x, const float* dy, float* dw, floa
   RPST_REQUIRE(((int64_t)(Cout > Cin ? Cout : Cin) + kW7TC) * H * W * 4 < (1LL << 31),
                "conv7_wgrad: one image's tensor exceeds 2 GiB");
   RPST_REQUIRE((int64_t)N * H * W < (1LL << 40), "conv7_wgrad: tensor too large");
-  if (!workspace || workspace_bytes < rpst_conv7_wgrad_workspace_size(N, Cin, H, W, Cout)) {
-    set_error("conv7_wgrad: workspace too small");
-    return RPST_EWORKSPACE;
-  }
-  int splits;
-  int64_t sps;
-  wgrad7_geometry(N, Cin, H, W, Cout, &splits, &sps);
-  const int64_t tiles =
-      (int64_t)((Cout + kW7TC - 1) / kW7TC) * ((Cin + kW7TC - 1) / kW7TC) * 7;
-  RPST_REQUIRE(tiles <= 0x7fffffffLL && splits <= 65535, "conv7_wgrad: grid too large");
+  const Wgrad7Layout L = wgrad7_layout(workspace, N, Cin, H, W, Cout);
+  RPST_REQUIRE_WS(L.bytes, "conv7_wgrad: workspace too small");
+  RPST_REQUIRE(L.tiles <= 0x7fffffffLL && L.splits <= 65535, "conv7_wgrad: grid too large");
   hipStream_t st = as_stream(stream);
-  float* part = static_cast<float*>(workspace);
-  float* bpart = part + (size_t)splits * Cout * Cin * 49;
-  conv7_wgrad_kernel<<<dim3((unsigned)tiles, (unsigned)splits), 256, 0, st>>>(
-      x, dy, part, db ? bpart : nullptr, N, Cin, H, W, Cout, sps,
+  conv7_wgrad_kernel<<<dim3((unsigned)L.tiles, (unsigned)L.splits), 256, 0, st>>>(
+      x, dy, L.part, db ? L.bpart : nullptr, N, Cin, H, W, Cout, L.sps,
       pad_mode == RPST_PAD_REFLECT);
   if (int e = launch_status("conv7_wgrad_kernel")) return e;
   const int64_t n = (int64_t)Cout * Cin * 49;
-  wgrad_reduce_kernel<<<(unsigned)((n + 255) / 256), 256, 0, st>>>(part, dw, n, splits);
+  wgrad_reduce_kernel<<<(unsigned)((n + 255) / 256), 256, 0, st>>>(L.part, dw, n, L.splits);
   if (int e = launch_status("wgrad_reduce_kernel")) return e;
   if (db) {
-    wgrad_reduce_kernel<<<(unsigned)((Cout + 255) / 256), 256, 0, st>>>(bpart, db, Cout, splits);
+    wgrad_reduce_kernel<<<(unsigned)((Cout + 255) / 256), 256, 0, st>>>(L.bpart, db, Cout,
+                                                                        L.splits);
     return launch_status("wgrad_reduce_kernel(bias)");
   }
   return RPST_OK;

@@ -329,6 +329,7 @@ extern "C" int rpst_resize_nearest(const float* src, float* dst, int N, int C, i
   return launch_status("resize_nearest_kernel");
 }
 
+// one region: how many destination rows, then columns, read each source row / column
 extern "C" size_t rpst_resized_mean_std_workspace_size(int h, int w) {
   return h > 0 && w > 0 ? sizeof(int) * ((size_t)h + (size_t)w) : 0;
 }
@@ -339,11 +340,8 @@ extern "C" int rpst_resized_mean_std(const float* src, float* mean, float* std_o
   RPST_REQUIRE(src && mean && std_out, "null pointer");
   if (int e = check_resize(N, C, h, w, H, W)) return e;
   RPST_REQUIRE((int64_t)N * C <= 0x7fffffff / 2, "too many planes");
-  if (!workspace || workspace_bytes < rpst_resized_mean_std_workspace_size(h, w)) {
-    set_error("resized_mean_std: workspace %zu < %zu bytes", workspace_bytes,
-              rpst_resized_mean_std_workspace_size(h, w));
-    return RPST_EWORKSPACE;
-  }
+  const size_t need = rpst_resized_mean_std_workspace_size(h, w);
+  RPST_REQUIRE_WS(need, "resized_mean_std: workspace %zu < %zu bytes", workspace_bytes, need);
   const Resize r = make_resize(h, w, H, W);
   int* counts = static_cast<int*>(workspace);
   hipStream_t st = as_stream(stream);

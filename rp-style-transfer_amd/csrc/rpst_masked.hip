@@ -349,6 +349,7 @@ extern "C" int rpst_segment_plan(const uint8_t* c_seg, const uint8_t* s_seg, int
   return launch_status("segment_plan_kernel");
 }
 
+// one region: partial[N * C][masked_splits(C)][kLabels][4] fp64 sums
 extern "C" size_t rpst_masked_adain_workspace_size(int N, int C) {
   if (N <= 0 || C <= 0) return 0;
   return (size_t)N * C * masked_splits(C) * kLabels * 4 * sizeof(double);
@@ -362,12 +363,13 @@ extern "C" int rpst_masked_adain_params(const float* content, const float* style
   if (int e = check_masked(N, C, HWc, HWs)) return e;
   RPST_REQUIRE(content && style && c_seg && s_seg && plan && params, "null pointer");
   RPST_REQUIRE((reinterpret_cast<uintptr_t>(params) & 15) == 0, "params must be 16-B aligned");
-  if (workspace_bytes < rpst_masked_adain_workspace_size(N, C) || !workspace ||
-      (reinterpret_cast<uintptr_t>(workspace) & 7) != 0) {
-    set_error("masked_adain_params: workspace %zu < %zu bytes (or unaligned)", workspace_bytes,
-              rpst_masked_adain_workspace_size(N, C));
-    return RPST_EWORKSPACE;
-  }
+  const size_t need = rpst_masked_adain_workspace_size(N, C);
+  // RPST_REQUIRE_WS plus the fp64 alignment
+  RPST_REQUIRE_OR(RPST_EWORKSPACE,
+                  workspace && workspace_bytes >= need &&
+                      (reinterpret_cast<uintptr_t>(workspace) & 7) == 0,
+                  "masked_adain_params: workspace %zu < %zu bytes (or unaligned)",
+                  workspace_bytes, need);
   const int splits = masked_splits(C);
   hipStream_t st = as_stream(stream);
   double* partial = static_cast<double*>(workspace);

@@ -177,8 +177,20 @@ extern "C" int rpst_calc_mean_std(const float* feat, float* mean, float* std_out
   return launch_status("plane_stats_kernel");
 }
 
+// mean and std per plane of the content, then of the style (rpst_mean_variance_norm takes
+// the same workspace and uses the first pair)
+struct StatsLayout { float *mc, *sc, *ms, *ss; size_t bytes; };
+static StatsLayout stats_layout(void* workspace, int N, int C) {
+  Carver c(workspace);
+  StatsLayout L{};
+  if (N > 0 && C > 0)
+    for (float** r : {&L.mc, &L.sc, &L.ms, &L.ss}) *r = c.take((size_t)N * C);
+  L.bytes = c.bytes;
+  return L;
+}
+
 extern "C" size_t rpst_adain_workspace_size(int N, int C) {
-  return (size_t)4 * sizeof(float) * (size_t)(N > 0 ? N : 0) * (size_t)(C > 0 ? C : 0);
+  return stats_layout(nullptr, N, C).bytes;
 }
 
 extern "C" int rpst_adain(const float* content, const float* style, float* out, int N,
@@ -186,19 +198,14 @@ extern "C" int rpst_adain(const float* content, const float* style, float* out, 
                           size_t workspace_bytes, rpst_stream_t stream) {
   if (int e = check_nchw(content, N, C, HW)) return e;
   RPST_REQUIRE(style && out, "null tensor pointer");
-  if (workspace_bytes < rpst_adain_workspace_size(N, C) || !workspace) {
-    set_error("adain: workspace %zu < %zu bytes", workspace_bytes,
-              rpst_adain_workspace_size(N, C));
-    return RPST_EWORKSPACE;
-  }
+  const StatsLayout L = stats_layout(workspace, N, C);
+  RPST_REQUIRE_WS(L.bytes, "adain: workspace %zu < %zu bytes", workspace_bytes, L.bytes);
   const int planes = N * C;
-  float* ws = static_cast<float*>(workspace);
-  float *mc = ws, *sc = ws + planes, *ms = ws + 2 * planes, *ss = ws + 3 * planes;
   hipStream_t st = as_stream(stream);
   plane_stats_kernel<<<2 * planes, kStatThreads, 0, st>>>(content, style, planes, HW, eps,
-                                                          mc, sc, ms, ss);
+                                                          L.mc, L.sc, L.ms, L.ss);
   if (int e = launch_status("plane_stats_kernel")) return e;
-  return launch_apply(true, content, out, mc, sc, ms, ss, planes, HW, st);
+  return launch_apply(true, content, out, L.mc, L.sc, L.ms, L.ss, planes, HW, st);
 }
 
 extern "C" int rpst_mean_variance_norm(const float* feat, float* out, int N, int C,
@@ -206,15 +213,12 @@ extern "C" int rpst_mean_variance_norm(const float* feat, float* out, int N, int
                                        size_t workspace_bytes, rpst_stream_t stream) {
   if (int e = check_nchw(feat, N, C, HW)) return e;
   RPST_REQUIRE(out, "null output pointer");
-  if (workspace_bytes < rpst_adain_workspace_size(N, C) || !workspace) {
-    set_error("mean_variance_norm: workspace too small");
-    return RPST_EWORKSPACE;
-  }
+  const StatsLayout L = stats_layout(workspace, N, C);
+  RPST_REQUIRE_WS(L.bytes, "mean_variance_norm: workspace too small");
   const int planes = N * C;
-  float* ws = static_cast<float*>(workspace);
   hipStream_t st = as_stream(stream);
-  plane_stats_kernel<<<planes, kStatThreads, 0, st>>>(feat, feat, planes, HW, eps, ws,
-                                                      ws + planes, ws, ws + planes);
+  plane_stats_kernel<<<planes, kStatThreads, 0, st>>>(feat, feat, planes, HW, eps, L.mc, L.sc,
+                                                      L.mc, L.sc);
   if (int e = launch_status("plane_stats_kernel")) return e;
-  return launch_apply(false, feat, out, ws, ws + planes, nullptr, nullptr, planes, HW, st);
+  return launch_apply(false, feat, out, L.mc, L.sc, nullptr, nullptr, planes, HW, st);
 }

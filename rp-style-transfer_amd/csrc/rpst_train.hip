@@ -592,6 +592,8 @@ extern "C" int rpst_maxpool2x2_ceil_backward(const float* x, const float* g, flo
   return launch_status("maxpool2_backward_kernel");
 }
 
+// one region: kRingKS copies of the border ring (the query does not know Cout;
+// ring_splits(Cout) of them are written)
 extern "C" size_t rpst_reflect_pad_border_grad_workspace_size(int N, int Cin, int H, int W) {
   if (N <= 0 || Cin <= 0 || H <= 0 || W <= 0) return 0;
   return sizeof(float) * kRingKS * (size_t)N * Cin * (2 * (size_t)(W + 2) + 2 * (size_t)H);
@@ -610,10 +612,8 @@ extern "C" int rpst_reflect_pad_border_grad_masked(const float* dy, const float*
                                                    size_t workspace_bytes, rpst_stream_t stream) {
   RPST_REQUIRE(dy && w && dx && N > 0 && Cin > 0 && Cout > 0, "reflect_border_grad: bad args");
   RPST_REQUIRE(H >= 2 && W >= 2, "reflect_border_grad: ReflectionPad2d(1) needs H, W >= 2");
-  if (!workspace || workspace_bytes < rpst_reflect_pad_border_grad_workspace_size(N, Cin, H, W)) {
-    set_error("reflect_border_grad: workspace too small");
-    return RPST_EWORKSPACE;
-  }
+  RPST_REQUIRE_WS(rpst_reflect_pad_border_grad_workspace_size(N, Cin, H, W),
+                  "reflect_border_grad: workspace too small");
   hipStream_t st = as_stream(stream);
   float* ring = static_cast<float*>(workspace);
   const int ks = ring_splits(Cout);
@@ -642,26 +642,32 @@ static int wgrad_tc(int Cin, int Cout) {
   return (Cin <= 32 && Cout <= 32) || Cin <= 8 || Cout <= 8 ? 32 : 64;
 }
 
-static void wgrad_geometry(int N, int Cin, int H, int W, int Cout, int* splits,
-                           int64_t* segs_per_split) {
-  const int tc = wgrad_tc(Cin, Cout), px = 4096 / tc;
-  const int tiles = ((Cout + tc - 1) / tc) * ((Cin + tc - 1) / tc);
+// The launch geometry and the partials it writes: part[splits * kspl][Cout][Cin][9], then
+// bpart[splits][Cout].
+struct WgradLayout { int tc, kspl, tiles, splits; int64_t sps; float *part, *bpart; size_t bytes; };
+static WgradLayout wgrad_layout(void* workspace, int N, int Cin, int H, int W, int Cout) {
+  Carver c(workspace);
+  WgradLayout L{};
+  if (N <= 0 || Cin <= 0 || H <= 0 || W <= 0 || Cout <= 0) return L;
+  L.tc = wgrad_tc(Cin, Cout);
+  L.kspl = L.tc == 32 ? 4 : 1;
+  const int px = 4096 / L.tc;
+  L.tiles = ((Cout + L.tc - 1) / L.tc) * ((Cin + L.tc - 1) / L.tc);
   const int64_t segs = (int64_t)N * H * ((W + px - 1) / px);
   // ~1024 workgroups in all, at least 4 segments each
-  int64_t s = (1024 + tiles - 1) / tiles;
+  int64_t s = (1024 + L.tiles - 1) / L.tiles;
   if (s > segs / 4) s = segs / 4;
   if (s < 1) s = 1;
-  *segs_per_split = (segs + s - 1) / s;
-  *splits = (int)((segs + *segs_per_split - 1) / *segs_per_split);
+  L.sps = (segs + s - 1) / s;
+  L.splits = (int)((segs + L.sps - 1) / L.sps);
+  L.part = c.take((size_t)L.splits * L.kspl * Cout * Cin * 9);
+  L.bpart = c.take((size_t)L.splits * Cout);
+  L.bytes = c.bytes;
+  return L;
 }
 
 extern "C" size_t rpst_conv_wgrad_workspace_size(int N, int Cin, int H, int W, int Cout) {
-  if (N <= 0 || Cin <= 0 || H <= 0 || W <= 0 || Cout <= 0) return 0;
-  int splits;
-  int64_t sps;
-  wgrad_geometry(N, Cin, H, W, Cout, &splits, &sps);
-  const size_t kspl = wgrad_tc(Cin, Cout) == 32 ? 4 : 1;
-  return sizeof(float) * (size_t)splits * Cout * (kspl * Cin * 9 + 1);
+  return wgrad_layout(nullptr, N, Cin, H, W, Cout).bytes;
 }
 
 extern "C" int rpst_conv_wgrad_pad(const float* x, const float* dy, float* dw, float* db,
@@ -674,37 +680,28 @@ extern "C" int rpst_conv_wgrad_pad(const float* x, const float* dy, float* dw, f
   RPST_REQUIRE(pad != RPST_PAD_REFLECT || (H >= 2 && W >= 2),
                "conv_wgrad: reflect padding needs H, W >= 2");
   const int reflect = pad == RPST_PAD_REFLECT;
-  if (!workspace || workspace_bytes < rpst_conv_wgrad_workspace_size(N, Cin, H, W, Cout)) {
-    set_error("conv_wgrad: workspace too small");
-    return RPST_EWORKSPACE;
-  }
+  const WgradLayout L = wgrad_layout(workspace, N, Cin, H, W, Cout);
+  RPST_REQUIRE_WS(L.bytes, "conv_wgrad: workspace too small");
   hipStream_t st = as_stream(stream);
-  int splits;
-  int64_t sps;
-  wgrad_geometry(N, Cin, H, W, Cout, &splits, &sps);
-  const int tc = wgrad_tc(Cin, Cout), kspl = tc == 32 ? 4 : 1;
-  const int tiles = ((Cout + tc - 1) / tc) * ((Cin + tc - 1) / tc);
-  RPST_REQUIRE(tiles <= 65535 * 64 && splits <= 65535, "conv_wgrad: grid too large");
-  float* part = static_cast<float*>(workspace);
-  float* bpart = part + (size_t)splits * kspl * Cout * Cin * 9;
+  RPST_REQUIRE(L.tiles <= 65535 * 64 && L.splits <= 65535, "conv_wgrad: grid too large");
   RPST_REQUIRE((int64_t)(Cout > Cin ? Cout : Cin) * H * W * 4 < (1LL << 31),
                "conv_wgrad: one image's tensor exceeds 2 GiB");
   const bool vec = (W % 4) == 0;
-  const dim3 grid(tiles, splits);
-  float* bp = db ? bpart : nullptr;
-  if (tc == 32) {
-    if (vec) conv_wgrad_kernel<true, 32><<<grid, 256, 0, st>>>(x, dy, part, bp, N, Cin, H, W, Cout, sps, reflect);
-    else conv_wgrad_kernel<false, 32><<<grid, 256, 0, st>>>(x, dy, part, bp, N, Cin, H, W, Cout, sps, reflect);
+  const dim3 grid(L.tiles, L.splits);
+  float* bp = db ? L.bpart : nullptr;
+  if (L.tc == 32) {
+    if (vec) conv_wgrad_kernel<true, 32><<<grid, 256, 0, st>>>(x, dy, L.part, bp, N, Cin, H, W, Cout, L.sps, reflect);
+    else conv_wgrad_kernel<false, 32><<<grid, 256, 0, st>>>(x, dy, L.part, bp, N, Cin, H, W, Cout, L.sps, reflect);
   } else {
-    if (vec) conv_wgrad_kernel<true, 64><<<grid, 256, 0, st>>>(x, dy, part, bp, N, Cin, H, W, Cout, sps, reflect);
-    else conv_wgrad_kernel<false, 64><<<grid, 256, 0, st>>>(x, dy, part, bp, N, Cin, H, W, Cout, sps, reflect);
+    if (vec) conv_wgrad_kernel<true, 64><<<grid, 256, 0, st>>>(x, dy, L.part, bp, N, Cin, H, W, Cout, L.sps, reflect);
+    else conv_wgrad_kernel<false, 64><<<grid, 256, 0, st>>>(x, dy, L.part, bp, N, Cin, H, W, Cout, L.sps, reflect);
   }
   if (int e = launch_status("conv_wgrad_kernel")) return e;
   const int64_t n = (int64_t)Cout * Cin * 9;
-  wgrad_reduce_kernel<<<blocks_for(n), 256, 0, st>>>(part, dw, n, splits * kspl);
+  wgrad_reduce_kernel<<<blocks_for(n), 256, 0, st>>>(L.part, dw, n, L.splits * L.kspl);
   if (int e = launch_status("wgrad_reduce_kernel")) return e;
   if (db) {
-    wgrad_reduce_kernel<<<blocks_for(Cout), 256, 0, st>>>(bpart, db, Cout, splits);
+    wgrad_reduce_kernel<<<blocks_for(Cout), 256, 0, st>>>(L.bpart, db, Cout, L.splits);
     return launch_status("wgrad_reduce_kernel(bias)");
   }
   return RPST_OK;
@@ -723,12 +720,10 @@ extern "C" int rpst_adain_backward(const float* g, const float* c, const float* 
                                    rpst_stream_t stream) {
   RPST_REQUIRE(g && c && s && stats && dc && ds && planes > 0 && HW > 1,
                "adain_backward: bad args");
-  if (!workspace || workspace_bytes < sizeof(float) * 2 * (size_t)planes) {
-    set_error("adain_backward: workspace too small");
-    return RPST_EWORKSPACE;
-  }
+  Carver ws(workspace);
+  float* sums = ws.take(2 * (size_t)planes);  // two sums per plane
+  RPST_REQUIRE_WS(ws.bytes, "adain_backward: workspace too small");
   hipStream_t st = as_stream(stream);
-  float* sums = static_cast<float*>(workspace);
   adain_backward_reduce_kernel<<<planes, 256, 0, st>>>(g, c, stats, sums, planes, HW);
   if (int e = launch_status("adain_backward_reduce_kernel")) return e;
   adain_backward_apply_kernel<<<blocks_for((int64_t)planes * HW), 256, 0, st>>>(
@@ -745,20 +740,18 @@ extern "C" int rpst_style_content_loss_grad(const float* F, const float* Fc, con
   return launch_status("loss_seed_kernel");
 }
 
-extern "C" size_t rpst_sq_diff_workspace_size(void) { return sizeof(double) * 1024; }
+constexpr int kSqDiffParts = 1024;  // fp64 block partials, at most: the whole workspace
+extern "C" size_t rpst_sq_diff_workspace_size(void) { return sizeof(double) * kSqDiffParts; }
 
 extern "C" int rpst_sq_diff_sum(const float* a, const float* b, int64_t n, double scale,
                                 float* out, void* workspace, size_t workspace_bytes,
                                 rpst_stream_t stream) {
   RPST_REQUIRE(a && b && out && n > 0, "sq_diff_sum: bad args");
-  if (!workspace || workspace_bytes < rpst_sq_diff_workspace_size()) {
-    set_error("sq_diff_sum: workspace too small");
-    return RPST_EWORKSPACE;
-  }
+  RPST_REQUIRE_WS(rpst_sq_diff_workspace_size(), "sq_diff_sum: workspace too small");
+  double* part = static_cast<double*>(workspace);
   hipStream_t st = as_stream(stream);
   int64_t nb = (n + 255) / 256;
-  const int parts = (int)(nb < 1024 ? nb : 1024);
-  double* part = static_cast<double*>(workspace);
+  const int parts = (int)(nb < kSqDiffParts ? nb : kSqDiffParts);
   sq_diff_partial_kernel<<<parts, 256, 0, st>>>(a, b, part, n);
   if (int e = launch_status("sq_diff_partial_kernel")) return e;
   sq_diff_final_kernel<<<1, 256, 0, st>>>(part, parts, scale, out);

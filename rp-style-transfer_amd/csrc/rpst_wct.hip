@@ -744,14 +744,12 @@ static int check_entry(const char* name, bool pointers, int n, int C, int64_t HW
   } else {
     RPST_REQUIRE(positive && fits, "%s: bad shape", name);
   }
-  if (need && (!workspace || workspace_bytes < need(n, C, HW))) {
-    if (lim.detail)
-      set_error("%s: workspace %zu < %zu bytes", name, workspace_bytes, need(n, C, HW));
-    else
-      set_error("%s: workspace too small", name);
-    return RPST_EWORKSPACE;
-  }
-  return RPST_OK;
+  if (!need) return RPST_OK;
+  const size_t bytes = need(n, C, HW);
+  if (workspace && workspace_bytes >= bytes) return RPST_OK;
+  if (lim.detail) set_error("%s: workspace %zu < %zu bytes", name, workspace_bytes, bytes);
+  else set_error("%s: workspace too small", name);
+  return RPST_EWORKSPACE;
 }
 
 // the per-image status words of the last closed-form call on `workspace` (laid out for fp32

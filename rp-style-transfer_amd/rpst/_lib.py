@@ -11,6 +11,8 @@ import ctypes
 import os
 import threading
 
+import torch
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("RPST_LIB", os.path.join(os.path.dirname(_HERE), "csrc", "librpst.so"))
 
@@ -168,6 +170,22 @@ def check(status: int, what: str) -> None:
     if status != 0:
         msg = load().rpst_last_error().decode(errors="replace")
         raise RpstError(f"{what} failed (status {status}): {msg}")
+
+
+def workspace_bytes(name: str, *dims) -> int:
+    """rpst_<name>_workspace_size(*dims): the bytes the C call is told it has."""
+    return getattr(load(), f"rpst_{name}_workspace_size")(*dims)
+
+
+def scratch(nbytes: int, like):
+    """The one workspace allocation, on like's device (16 bytes at least: never null)."""
+    return torch.empty(max(nbytes, 16), device=like.device, dtype=torch.uint8)
+
+
+def workspace(name: str, like, *dims):
+    """Size and allocate the workspace of one launch -> (uint8 tensor, nbytes)."""
+    nbytes = workspace_bytes(name, *dims)
+    return scratch(nbytes, like), nbytes
 
 
 def call(name: str, *args):

@@ -44,10 +44,6 @@ from . import _lib, ops, plan
 from .ops import _stream
 
 
-def _ws(nbytes: int, like: torch.Tensor) -> torch.Tensor:
-    return torch.empty(max(nbytes, 16), device=like.device, dtype=torch.uint8)
-
-
 def relu_backward(g: torch.Tensor, y: torch.Tensor) -> torch.Tensor:
     out = torch.empty_like(g)
     _lib.call("rpst_relu_backward", g.data_ptr(), y.data_ptr(), out.data_ptr(), g.numel(),
@@ -84,8 +80,7 @@ def conv_dgrad(g: torch.Tensor, step: plan.ConvStep,
     if k == 3 and step.pad == ops.PAD_REFLECT:
         n, _, h, w = g.shape
         wd = c.weight.detach().contiguous()
-        nbytes = _lib.load().rpst_reflect_pad_border_grad_workspace_size(n, c.in_channels, h, w)
-        ws = _ws(nbytes, g)
+        ws, nbytes = _lib.workspace("reflect_pad_border_grad", g, n, c.in_channels, h, w)
         _lib.call("rpst_reflect_pad_border_grad_masked", g.data_ptr(), wd.data_ptr(),
                   None if mask is None else mask.data_ptr(), dx.data_ptr(), n, c.in_channels,
                   c.out_channels, h, w, ws.data_ptr(), nbytes, _stream(g))
@@ -148,8 +143,7 @@ def conv_wgrad(x: torch.Tensor, g: torch.Tensor, conv: nn.Conv2d, pad: int = ops
     assert conv.kernel_size == (3, 3) and tuple(g.shape) == (n, cout, h, w)
     dw = torch.empty_like(conv.weight, memory_format=torch.contiguous_format)
     db = torch.empty_like(conv.bias) if conv.bias is not None else None
-    nbytes = _lib.load().rpst_conv_wgrad_workspace_size(n, cin, h, w, cout)
-    ws = _ws(nbytes, x)
+    ws, nbytes = _lib.workspace("conv_wgrad", x, n, cin, h, w, cout)
     with ops._traced(f"wgrad3x3 {cin}->{cout} {h}x{w} N{n} op0{' reflect' if pad else ''}",
                      2.0 * n * cout * cin * 9 * h * w, 4.0 * (x.numel() + g.numel())):
         _lib.call("rpst_conv_wgrad_pad", x.data_ptr(), g.data_ptr(), dw.data_ptr(),
@@ -170,8 +164,7 @@ def conv_wgrad7(x: torch.Tensor, g: torch.Tensor, conv: nn.Conv2d, pad: int = op
     x, g = ops._c(x), ops._c(g)
     dw = torch.empty_like(conv.weight, memory_format=torch.contiguous_format)
     db = torch.empty_like(conv.bias) if conv.bias is not None else None
-    nbytes = _lib.load().rpst_conv7_wgrad_workspace_size(n, cin, h, w, cout)
-    ws = _ws(nbytes, x)
+    ws, nbytes = _lib.workspace("conv7_wgrad", x, n, cin, h, w, cout)
     with ops._traced(f"wgrad7x7 {cin}->{cout} {h}x{w} N{n}{' reflect' if pad else ''}",
                      2.0 * n * cout * cin * 49 * h * w, 4.0 * (7 * x.numel() + 7 * g.numel())):
         _lib.call("rpst_conv7_wgrad", x.data_ptr(), g.data_ptr(), dw.data_ptr(),
@@ -189,8 +182,7 @@ def _lin_grads(dY, X):
     dY, X = dY.contiguous(), X.contiguous()
     dw = torch.empty((co, ci, 1, 1), device=X.device, dtype=torch.float32)
     db = torch.empty(co, device=X.device, dtype=torch.float32)
-    nbytes = _lib.load().rpst_conv1x1_wgrad_workspace_size(b, ci, co)
-    ws = _ws(nbytes, X)
+    ws, nbytes = _lib.workspace("conv1x1_wgrad", X, b, ci, co)
     _lib.call("rpst_conv1x1_wgrad", X.data_ptr(), dY.data_ptr(), dw.data_ptr(), db.data_ptr(),
               b, ci, hw, co, ws.data_ptr(), nbytes, _stream(X))
     return dw, db
@@ -213,8 +205,7 @@ def _acc(grads: Dict[int, torch.Tensor], p: torch.Tensor, g: torch.Tensor) -> No
 def sq_diff_mean(a: torch.Tensor, b: torch.Tensor) -> torch.Tensor:
     """nn.MSELoss()(a, b) (mean reduction) as a 0-dim device tensor."""
     out = torch.empty((), device=a.device, dtype=torch.float32)
-    nbytes = _lib.load().rpst_sq_diff_workspace_size()
-    ws = _ws(nbytes, a)
+    ws, nbytes = _lib.workspace("sq_diff", a)
     _lib.call("rpst_sq_diff_sum", a.data_ptr(), b.data_ptr(), a.numel(), 1.0 / a.numel(),
               out.data_ptr(), ws.data_ptr(), nbytes, _stream(a))
     return out
@@ -553,8 +544,7 @@ def _sanet_backward(m, saved, d_out, grads):
         w1, b1, w2, b2, hid = ops._mlp_params(al.f_psi)
         dw1, db1 = torch.empty_like(w1), torch.empty_like(b1)
         dw2, db2 = torch.empty_like(w2), torch.empty_like(b2)
-        nbytes = _lib.load().rpst_adaptive_attention_backward_workspace_size(b, ch, hwc, hid)
-        ws = _ws(nbytes, F)
+        ws, nbytes = _lib.workspace("adaptive_attention_backward", F, b, ch, hwc, hid)
         _lib.call("rpst_adaptive_attention_backward", F.data_ptr(), G.data_ptr(), H.data_ptr(),
                   c.data_ptr(), s.data_ptr(), w1.data_ptr(), b1.data_ptr(), w2.data_ptr(),
                   b2.data_ptr(), hid, al.mode, float(al.scale_value), float(al.from_value),
@@ -568,8 +558,7 @@ def _sanet_backward(m, saved, d_out, grads):
         # rpst_sanet_attention_backward_chunked: S = F^T G and dP for 2048 queries at a time
         # on gemm_f32_kernel, the softmax probabilities formed while S is staged,
         # dS = P (dP - rowsum(dP P)) -- no B x HW x HW workspace
-        nbytes = _lib.load().rpst_sanet_attention_backward_chunked_workspace_size(b, ch, hwc, hws)
-        ws = _ws(nbytes, F)
+        ws, nbytes = _lib.workspace("sanet_attention_backward_chunked", F, b, ch, hwc, hws)
         _lib.call("rpst_sanet_attention_backward_chunked", F.data_ptr(), G.data_ptr(),
                   H.data_ptr(), dO.data_ptr(), dF.data_ptr(), dG.data_ptr(), dH.data_ptr(), b,
                   ch, hwc, hws, ws.data_ptr(), nbytes, _stream(F))

@@ -175,8 +175,7 @@ def adaptive_instance_normalization(content: torch.Tensor, style: torch.Tensor,
     hw = content.numel() // (N * C)
     if out is None:
         out = torch.empty_like(content)
-    nbytes = _lib.load().rpst_adain_workspace_size(N, C)
-    ws = torch.empty(nbytes, device=content.device, dtype=torch.uint8)
+    ws, nbytes = _lib.workspace("adain", content, N, C)
     with _traced(f"adain C{C} {hw}px N{N}", 0.0, 3.0 * 4 * N * C * hw):
         _lib.call("rpst_adain", content.data_ptr(), style.data_ptr(), out.data_ptr(), N, C, hw,
                   eps, ws.data_ptr(), nbytes, _stream(content))
@@ -248,8 +247,7 @@ def _masked_params(content, style, c_seg, s_seg, plan, eps):
     N, C = content.shape[:2]
     hwc, hws = c_seg[0].numel(), s_seg[0].numel()
     params = torch.empty((N, C, SEG_LABELS, 4), device=content.device, dtype=torch.float32)
-    nbytes = _lib.load().rpst_masked_adain_workspace_size(N, C)
-    ws = torch.empty(nbytes, device=content.device, dtype=torch.uint8)
+    ws, nbytes = _lib.workspace("masked_adain", content, N, C)
     with _traced(f"masked stats C{C} {hwc}px N{N}", 0.0, (4.0 * C + 1) * N * (hwc + hws)):
         _lib.call("rpst_masked_adain_params", content.data_ptr(), style.data_ptr(),
                   c_seg.data_ptr(), s_seg.data_ptr(), plan.data_ptr(), N, C, hwc, hws, eps,
@@ -294,8 +292,7 @@ def mean_variance_norm(feat: torch.Tensor, eps: float = 1e-5) -> torch.Tensor:
     N, C = feat.shape[:2]
     hw = feat.numel() // (N * C)
     out = torch.empty_like(feat)
-    nbytes = _lib.load().rpst_adain_workspace_size(N, C)
-    ws = torch.empty(nbytes, device=feat.device, dtype=torch.uint8)
+    ws, nbytes = _lib.workspace("adain", feat, N, C)
     _lib.call("rpst_mean_variance_norm", feat.data_ptr(), out.data_ptr(), N, C, hw, eps,
               ws.data_ptr(), nbytes, _stream(feat))
     return out
@@ -494,12 +491,12 @@ def conv2d(x: torch.Tensor, packed: torch.Tensor, bias: Optional[torch.Tensor], 
         else:
             assert tuple(aux.shape) == (n, cin, h // 2, w // 2)
     with _conv_traced(x.shape, cout, ksize, in_op, x.numel() + out.numel()):
-        nbytes = _lib.load().rpst_conv2d_workspace_size(n, cin, hs, ws, cout, ksize,
-                                                        in_op) if fold else 0
+        nbytes = _lib.workspace_bytes("conv2d", n, cin, hs, ws, cout, ksize,
+                                      in_op) if fold else 0
         args = (x.data_ptr(), _ptr(aux), packed.data_ptr(), _bias_ptr(bias), _ptr(residual),
                 out.data_ptr(), n, cin, hs, ws, cout, ksize, pad, in_op, _act(relu))
         if nbytes:
-            ws_t = torch.empty(nbytes, device=x.device, dtype=torch.uint8)
+            ws_t = _lib.scratch(nbytes, x)
             _lib.call("rpst_conv2d_ws", *args, ws_t.data_ptr(), nbytes, _stream(x))
         else:
             _lib.call("rpst_conv2d", *args, _stream(x))
@@ -577,8 +574,7 @@ def conv2d_stats(x: torch.Tensor, packed: torch.Tensor, bias: Optional[torch.Ten
     out = _conv_out(x, (n, cout, *conv_out_hw(hs, ws, in_op)))
     mean = torch.empty((n, cout, 1, 1), device=x.device, dtype=torch.float32)
     std = torch.empty_like(mean)
-    nbytes = _lib.load().rpst_conv2d_stats_workspace_size(n, cin, hs, ws, cout, ksize, in_op)
-    ws_t = torch.empty(nbytes, device=x.device, dtype=torch.uint8)
+    ws_t, nbytes = _lib.workspace("conv2d_stats", x, n, cin, hs, ws, cout, ksize, in_op)
     args = (x.data_ptr(), _ptr(aux), packed.data_ptr(), _bias_ptr(bias), None, out.data_ptr(), n,
             cin, hs, ws, cout, ksize, pad, in_op, _act(relu), mean.data_ptr(), std.data_ptr(), eps)
     with _conv_traced(x.shape, cout, ksize, in_op, x.numel() + out.numel()):
@@ -628,8 +624,8 @@ def conv2d_gated(x: torch.Tensor, packed: torch.Tensor, bias: Optional[torch.Ten
     if stats:
         mean = torch.empty((n, cout, 1, 1), device=x.device, dtype=torch.float32)
         std = torch.empty_like(mean)
-        nbytes = _lib.load().rpst_conv2d_gated_workspace_size(n, cin, h, w, cout, ksize)
-    ws_t = torch.empty(nbytes, device=x.device, dtype=torch.uint8) if nbytes else None
+        nbytes = _lib.workspace_bytes("conv2d_gated", n, cin, h, w, cout, ksize)
+    ws_t = _lib.scratch(nbytes, x) if nbytes else None
     with _conv_traced(x.shape, cout, ksize, IN_NONE, x.numel() + 2 * out.numel(),
                       f"gated{ksize}x{ksize} {cin}->{cout} {h}x{w} N{n}"):
         _lib.call("rpst_conv2d_gated", x.data_ptr(), packed.data_ptr(), _bias_ptr(bias),
@@ -719,8 +715,7 @@ def resized_mean_std(src: torch.Tensor, size,
     src = _c(src)
     mean = torch.empty((n, c, 1, 1), device=src.device, dtype=torch.float32)
     std = torch.empty_like(mean)
-    nbytes = _lib.load().rpst_resized_mean_std_workspace_size(h, w)
-    ws = torch.empty(nbytes, device=src.device, dtype=torch.uint8)
+    ws, nbytes = _lib.workspace("resized_mean_std", src, h, w)
     with _traced(f"resized_mean_std C{c} {h}x{w}->{H}x{W} N{n}", 0.0, 4.0 * n * c * h * w):
         _lib.call("rpst_resized_mean_std", src.data_ptr(), mean.data_ptr(), std.data_ptr(), n, c,
                   h, w, H, W, eps, ws.data_ptr(), nbytes, _stream(src))
@@ -820,7 +815,7 @@ def sanet_attention(F: torch.Tensor, G: torch.Tensor, H: torch.Tensor) -> torch.
     per_img = lib.rpst_sanet_attention_workspace_size_c(1, C, hw)
     chunk = B if per_img == 0 else max(1, min(B, SANET_WS_CAP // per_img))
     ws_bytes = lib.rpst_sanet_attention_workspace_size_c(chunk, C, hw)
-    ws = torch.empty(max(ws_bytes, 16), device=F.device, dtype=torch.uint8)
+    ws = _lib.scratch(ws_bytes, F)
     for b0 in range(0, B, chunk):
         nb = min(chunk, B - b0)
         with _traced(f"sanet_attention C{C} HW{hw} N{nb}", 4.0 * nb * hw * hw * C, 0.0):
@@ -838,8 +833,7 @@ def cosine_affinity(content: torch.Tensor, style: torch.Tensor) -> torch.Tensor:
     B, C, h, w = content.shape
     hw = h * w
     out = torch.empty((B, hw, hw), device=content.device, dtype=torch.float32)
-    nbytes = _lib.load().rpst_cosine_affinity_workspace_size(B, C, hw)
-    ws = torch.empty(nbytes, device=content.device, dtype=torch.uint8)
+    ws, nbytes = _lib.workspace("cosine_affinity", content, B, C, hw)
     _lib.call("rpst_cosine_affinity", content.data_ptr(), style.data_ptr(), out.data_ptr(), B, C,
               hw, ws.data_ptr(), nbytes, _stream(content))
     return out
@@ -868,8 +862,7 @@ def aea_clamp(x: torch.Tensor, f_x: torch.Tensor, f_psi, mode: int, scale: float
     assert w1.shape[1] == hw, "f_psi input width must equal HW (spatial_dims)"
     out = torch.empty_like(f_x)
     clamp = torch.empty((B, hw, 1), device=x.device, dtype=torch.float32)
-    nbytes = _lib.load().rpst_aea_clamp_workspace_size(B, hw, hid)
-    ws = torch.empty(nbytes, device=x.device, dtype=torch.uint8)
+    ws, nbytes = _lib.workspace("aea_clamp", x, B, hw, hid)
     _lib.call("rpst_aea_clamp", x.data_ptr(), f_x.data_ptr(), w1.data_ptr(), b1.data_ptr(),
               w2.data_ptr(), b2.data_ptr(), hid, mode, scale, from_value, interval,
               out.data_ptr(), clamp.data_ptr(), B, hw, ws.data_ptr(), nbytes, _stream(x))
@@ -899,8 +892,7 @@ def adaptive_attention(F: torch.Tensor, G: torch.Tensor, H: torch.Tensor,
     lib = _lib.load()
     per_img = lib.rpst_adaptive_attention_workspace_size(1, C, hw, hid)
     chunk = max(1, min(B, SANET_WS_CAP // max(per_img, 1)))
-    ws_bytes = lib.rpst_adaptive_attention_workspace_size(chunk, C, hw, hid)
-    ws = torch.empty(ws_bytes, device=F.device, dtype=torch.uint8)
+    ws, ws_bytes = _lib.workspace("adaptive_attention", F, chunk, C, hw, hid)
     for b0 in range(0, B, chunk):
         nb = min(chunk, B - b0)
         # S = F^T G and O = H Q^T (4 HW^2 C) + f_psi's first Linear without the affinity:
@@ -931,8 +923,7 @@ def matrix_power_psd(A: torch.Tensor, p: float) -> torch.Tensor:
     batch = A.numel() // (n * n)
     out = torch.empty_like(A)
     res = torch.empty(batch, device=A.device, dtype=torch.float64)
-    nbytes = _lib.load().rpst_matrix_power_workspace_size(n, batch)
-    ws = torch.empty(nbytes, device=A.device, dtype=torch.uint8)
+    ws, nbytes = _lib.workspace("matrix_power", A, n, batch)
     _lib.call("rpst_matrix_power_psd_f64", A.data_ptr(), out.data_ptr(), n, batch,
               int(p < 0), res.data_ptr(), ws.data_ptr(), nbytes, _stream(A))
     return out
@@ -952,8 +943,7 @@ def whiten_and_color(cF: torch.Tensor, sF: torch.Tensor, method: str = 'closed-f
     cF, sF = _c(cF), _c(sF)
     C, hw = cF.shape
     out = torch.empty_like(cF)
-    nbytes = _lib.load().rpst_wct_workspace_size(1, C, hw)
-    ws = torch.empty(nbytes, device=cF.device, dtype=torch.uint8)
+    ws, nbytes = _lib.workspace("wct", cF, 1, C, hw)
     if method == 'original':
         _lib.call("rpst_whiten_and_color_original_f64", cF.data_ptr(), sF.data_ptr(),
                   out.data_ptr(), C, hw, ws.data_ptr(), nbytes, _stream(cF))
@@ -1039,8 +1029,7 @@ def wct_fuse(content: torch.Tensor, style: torch.Tensor, status: bool = False):
     n, C, h, w = content.shape
     out = torch.empty_like(content)
     res = torch.empty(2 * n, device=content.device, dtype=torch.float64)
-    nbytes = _lib.load().rpst_wct_workspace_size(n, C, h * w)
-    ws = torch.empty(nbytes, device=content.device, dtype=torch.uint8)
+    ws, nbytes = _lib.workspace("wct", content, n, C, h * w)
     with _traced(f"wct_fuse C{C} {h * w}px N{n}", 6.0 * n * C * C * h * w, 0.0):
         _lib.call("rpst_wct_fuse", content.data_ptr(), style.data_ptr(), out.data_ptr(), n, C,
                   h * w, res.data_ptr(), ws.data_ptr(), nbytes, _stream(content))
@@ -1065,8 +1054,7 @@ def wct_params(content: torch.Tensor, style: torch.Tensor, means: Optional[torch
     T = torch.empty((n, C, C), device=content.device, dtype=torch.float64)
     c = torch.empty((n, C), device=content.device, dtype=torch.float64)
     res = torch.empty(2 * n, device=content.device, dtype=torch.float64)
-    nbytes = _lib.load().rpst_wct_workspace_size(n, C, h * w)
-    ws = torch.empty(nbytes, device=content.device, dtype=torch.uint8)
+    ws, nbytes = _lib.workspace("wct", content, n, C, h * w)
     with _traced(f"wct_params C{C} {h * w}px N{n}", 2.0 * n * C * (C + 1) * h * w, 0.0):
         _lib.call("rpst_wct_params", content.data_ptr(), style.data_ptr(), _ptr(means),
                   T.data_ptr(), c.data_ptr(), n, C, h * w, res.data_ptr(), ws.data_ptr(), nbytes,
@@ -1086,8 +1074,7 @@ def conv2d_mix(x: torch.Tensor, T: torch.Tensor, offset: torch.Tensor, packed: t
     T, offset = _c(T), _c(offset)
     assert tuple(T.shape) == (n, cin, cin) and tuple(offset.shape) == (n, cin)
     out = _conv_out(x, (n, cout, h, w))
-    nbytes = _lib.load().rpst_conv2d_mix_workspace_size(n, cin, h, w, cout, ksize)
-    ws = torch.empty(nbytes, device=x.device, dtype=torch.uint8)
+    ws, nbytes = _lib.workspace("conv2d_mix", x, n, cin, h, w, cout, ksize)
     with _conv_traced(x.shape, cout, ksize, IN_NONE, x.numel() + out.numel(),
                       _conv_name(ksize, cin, cout, h, w, n, IN_NONE).replace(" op0", " mix")):
         _lib.call("rpst_conv2d_mix", x.data_ptr(), T.data_ptr(), offset.data_ptr(),

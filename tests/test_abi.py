@@ -368,3 +368,328 @@ def test_plan_rejects_unfused_first_transform():
         plan.run(steps, x, first_in_op=ops.IN_ADAIN)
     with pytest.raises(NotImplementedError, match="first_mix"):
         plan.run([], x, first_mix=(None, None))
+
+
+# ---- workspaces: every size export and every refusal, pinned ------------------------------
+SIZE_ENV = ("RPST_CONV_ALGO", "RPST_CONV_NARROW", "RPST_W4Q", "RPST_WGRAD_TC", "RPST_SANET_FLASH")
+# export (without rpst_ / _workspace_size) -> argument tuples, chosen to reach every branch of
+# its layout: flash-eligible C (64 / 128 / 256 / 512 with HW % 4 == 0) and not, HW below and
+# above the 2048-query chunk, B * HW off the 128-row column chunks, T larger than the logits;
+# wgrad with both channel counts <= 32, one side <= 8 and wide, W off the segment width;
+# conv1x1_wgrad's pixel split clamped at 16 and down at 1
+WS_SHAPES = {
+    "adain": [(2, 3), (1, 64), (0, 5)],
+    "masked_adain": [(2, 3), (1, 64), (2, 512)],
+    "resized_mean_std": [(5, 7), (0, 3)],
+    "sanet_attention": [(2, 48), (1, 2304)],
+    "sanet_attention_workspace_size_c": [(2, 24, 48), (2, 64, 64), (1, 64, 50), (1, 128, 2304),
+                                         (1, 256, 64), (1, 512, 64)],
+    "cosine_affinity": [(2, 24, 48), (1, 64, 2304)],
+    "aea_clamp": [(2, 48, 16), (1, 2304, 8)],
+    "adaptive_attention": [(2, 24, 48, 16), (2, 64, 64, 16), (1, 24, 2304, 16), (1, 512, 16, 64),
+                           (1, 24, 16, 64), (3, 64, 43, 16)],
+    "sanet_attention_backward": [(2, 48, 40), (1, 2304, 100)],
+    "sanet_attention_backward_chunked": [(2, 64, 48, 40), (1, 64, 2304, 40), (1, 64, 2048, 8)],
+    "adaptive_attention_backward": [(2, 64, 48, 16), (1, 24, 2304, 8), (2, 64, 64, 16),
+                                    (3, 512, 16, 64)],
+    "conv1x1_wgrad": [(1, 8, 8), (64, 512, 512), (8, 512, 512), (2, 100, 300)],
+    "reflect_pad_border_grad": [(2, 3, 5, 7), (1, 64, 32, 48)],
+    "conv_wgrad": [(2, 16, 9, 13, 32), (2, 64, 9, 13, 3), (2, 8, 9, 13, 64), (2, 64, 33, 70, 128),
+                   (1, 128, 64, 256, 128), (4, 32, 64, 200, 32)],
+    "conv7_wgrad": [(2, 3, 9, 13, 16), (1, 16, 40, 300, 3), (4, 64, 64, 64, 64)],
+    "sq_diff": [()],
+}
+# the conv sizes, taken at every rpst_conv2d_set_precise level x rpst_conv2d_set_quarter setting
+CONV_WS_SHAPES = {
+    "conv2d_stats": [(2, 128, 37, 200, 256, 3, 0), (2, 3, 16, 16, 16, 3, 0),
+                     (2, 64, 16, 16, 128, 1, 0), (2, 256, 37, 70, 96, 3, 4)],
+    "conv2d": [(2, 256, 37, 70, 96, 3, 4), (2, 256, 37, 70, 96, 3, 0), (2, 8, 9, 13, 32, 3, 4)],
+    "conv2d_mix": [(2, 128, 37, 70, 96, 3), (2, 8, 9, 13, 32, 3), (1, 16, 12, 20, 32, 3),
+                   (2, 8, 9, 13, 32, 1), (2, 8, 9, 13, 32, 5)],
+    "conv2d_gated": [(2, 32, 16, 16, 32, 1), (2, 32, 16, 16, 128, 1), (2, 32, 16, 16, 32, 3)],
+}
+CONV_MODES = [(level, quarter) for level in (0, 1, 2) for quarter in (-1, 0, 2)]
+
+
+def _size_export(lib, name):
+    return getattr(lib, f"rpst_{name}" if name.endswith("_c") else f"rpst_{name}_workspace_size")
+
+
+def _workspace_sizes(lib):
+    """{(export, arguments): bytes}; for the conv exports a tuple of bytes, one per CONV_MODES."""
+    out = {(name, args): _size_export(lib, name)(*args)
+           for name, shapes in WS_SHAPES.items() for args in shapes}
+    conv = {(name, args): [] for name, shapes in CONV_WS_SHAPES.items() for args in shapes}
+    for level, quarter in CONV_MODES:
+        p, q = lib.rpst_conv2d_set_precise(level), lib.rpst_conv2d_set_quarter(quarter)
+        try:
+            for name, args in conv:
+                conv[(name, args)].append(_size_export(lib, name)(*args))
+        finally:
+            lib.rpst_conv2d_set_precise(p)
+            lib.rpst_conv2d_set_quarter(q)
+    out.update({k: tuple(v) for k, v in conv.items()})
+    return out
+
+
+WS_SIZES = {('adain', (2, 3)): 96,
+ ('adain', (1, 64)): 1024,
+ ('adain', (0, 5)): 0,
+ ('masked_adain', (2, 3)): 786432,
+ ('masked_adain', (1, 64)): 4194304,
+ ('masked_adain', (2, 512)): 8388608,
+ ('resized_mean_std', (5, 7)): 48,
+ ('resized_mean_std', (0, 3)): 0,
+ ('sanet_attention', (2, 48)): 19200,
+ ('sanet_attention', (1, 2304)): 21252096,
+ ('sanet_attention_workspace_size_c', (2, 24, 48)): 19200,
+ ('sanet_attention_workspace_size_c', (2, 64, 64)): 0,
+ ('sanet_attention_workspace_size_c', (1, 64, 50)): 10400,
+ ('sanet_attention_workspace_size_c', (1, 128, 2304)): 0,
+ ('sanet_attention_workspace_size_c', (1, 256, 64)): 0,
+ ('sanet_attention_workspace_size_c', (1, 512, 64)): 0,
+ ('cosine_affinity', (2, 24, 48)): 18432,
+ ('cosine_affinity', (1, 64, 2304)): 1179648,
+ ('aea_clamp', (2, 48, 16)): 6912,
+ ('aea_clamp', (1, 2304, 8)): 92160,
+ ('adaptive_attention', (2, 24, 48, 16)): 45696,
+ ('adaptive_attention', (2, 64, 64, 16)): 85504,
+ ('adaptive_attention', (1, 24, 2304, 16)): 21888000,
+ ('adaptive_attention', (1, 512, 16, 64)): 201152,
+ ('adaptive_attention', (1, 24, 16, 64)): 13760,
+ ('adaptive_attention', (3, 64, 43, 16)): 100104,
+ ('sanet_attention_backward', (2, 48, 40)): 31488,
+ ('sanet_attention_backward', (1, 2304, 100)): 1861632,
+ ('sanet_attention_backward_chunked', (2, 64, 48, 40)): 31488,
+ ('sanet_attention_backward_chunked', (1, 64, 2304, 40)): 671744,
+ ('sanet_attention_backward_chunked', (1, 64, 2048, 8)): 147456,
+ ('adaptive_attention_backward', (2, 64, 48, 16)): 116300,
+ ('adaptive_attention_backward', (1, 24, 2304, 8)): 38494872,
+ ('adaptive_attention_backward', (2, 64, 64, 16)): 168652,
+ ('adaptive_attention_backward', (3, 512, 16, 64)): 635340,
+ ('conv1x1_wgrad', (1, 8, 8)): 4096,
+ ('conv1x1_wgrad', (64, 512, 512)): 67108864,
+ ('conv1x1_wgrad', (8, 512, 512)): 67108864,
+ ('conv1x1_wgrad', (2, 100, 300)): 3840000,
+ ('reflect_pad_border_grad', (2, 3, 5, 7)): 2688,
+ ('reflect_pad_border_grad', (1, 64, 32, 48)): 167936,
+ ('conv_wgrad', (2, 16, 9, 13, 32)): 295424,
+ ('conv_wgrad', (2, 64, 9, 13, 3)): 110640,
+ ('conv_wgrad', (2, 8, 9, 13, 64)): 295936,
+ ('conv_wgrad', (2, 64, 33, 70, 128)): 9748992,
+ ('conv_wgrad', (1, 128, 64, 256, 128)): 37781504,
+ ('conv_wgrad', (4, 32, 64, 200, 32)): 18890752,
+ ('conv7_wgrad', (2, 3, 9, 13, 16)): 37888,
+ ('conv7_wgrad', (1, 16, 40, 300, 3)): 471000,
+ ('conv7_wgrad', (4, 64, 64, 64, 64)): 51396608,
+ ('sq_diff', ()): 8192,
+ ('conv2d_stats', (2, 128, 37, 200, 256, 3, 0)): (196608, 196608, 196608, 196608, 196608, 196608,
+                                                  196608, 196608, 196608),
+ ('conv2d_stats', (2, 3, 16, 16, 16, 3, 0)): (2048, 2048, 2048, 2048, 2048, 2048, 2048, 2048,
+                                              2048),
+ ('conv2d_stats', (2, 64, 16, 16, 128, 1, 0)): (16384, 16384, 16384, 16384, 16384, 16384, 16384,
+                                                16384, 16384),
+ ('conv2d_stats', (2, 256, 37, 70, 96, 3, 4)): (11250440, 11250440, 11250440, 11250440, 11250440,
+                                                11250440, 11250440, 11250440, 11250440),
+ ('conv2d', (2, 256, 37, 70, 96, 3, 4)): (11213576, 11213576, 11213576, 11213576, 11213576,
+                                          11213576, 11213576, 11213576, 11213576),
+ ('conv2d', (2, 256, 37, 70, 96, 3, 0)): (0, 0, 0, 0, 0, 0, 0, 0, 0),
+ ('conv2d', (2, 8, 9, 13, 32, 3, 4)): (0, 0, 0, 0, 0, 0, 0, 0, 0),
+ ('conv2d_mix', (2, 128, 37, 70, 96, 3)): (7822360, 7822360, 7822360, 2785792, 2785792, 2785792,
+                                           7822360, 7822360, 7822360),
+ ('conv2d_mix', (2, 8, 9, 13, 32, 3)): (8640, 8640, 8640, 8640, 8640, 8640, 8640, 8640, 8640),
+ ('conv2d_mix', (1, 16, 12, 20, 32, 3)): (241048, 241048, 241048, 17024, 17024, 17024, 241048,
+                                          241048, 241048),
+ ('conv2d_mix', (2, 8, 9, 13, 32, 1)): (8640, 8640, 8640, 8640, 8640, 8640, 8640, 8640, 8640),
+ ('conv2d_mix', (2, 8, 9, 13, 32, 5)): (0, 0, 0, 0, 0, 0, 0, 0, 0),
+ ('conv2d_gated', (2, 32, 16, 16, 32, 1)): (2048, 2048, 2048, 2048, 2048, 2048, 2048, 2048, 2048),
+ ('conv2d_gated', (2, 32, 16, 16, 128, 1)): (0, 0, 0, 0, 0, 0, 0, 0, 0),
+ ('conv2d_gated', (2, 32, 16, 16, 32, 3)): (0, 0, 0, 0, 0, 0, 0, 0, 0)}
+
+
+def test_workspace_sizes_are_pinned(monkeypatch):
+    """Every *_workspace_size export returns exactly these bytes (host-only; the WCT sizes are
+    pinned above)."""
+    for k in SIZE_ENV:
+        monkeypatch.delenv(k, raising=False)
+    got = _workspace_sizes(_lib.load())
+    assert list(got) == list(WS_SIZES)
+    wrong = {k: (v, WS_SIZES[k]) for k, v in got.items() if v != WS_SIZES[k]}
+    assert not wrong, wrong
+
+
+# entry -> (size export, its arguments, the entry's arguments): placeholder pointers (16:
+# aligned for every entry), "ws" / "nb" where the workspace and its byte count go. Valid small
+# shapes whose workspace is not empty; the check runs before any launch. (Were a check to let
+# one of these calls through, it would launch on the placeholder pointers: on a machine with a
+# GPU that is a fault there, which is how a regression of a refusal would show.)
+_P = 16
+WS_ENTRIES = {
+    "rpst_adain": ("adain", (2, 3), (_P, _P, _P, 2, 3, 16, 1e-5, "ws", "nb", None)),
+    "rpst_mean_variance_norm": ("adain", (2, 3), (_P, _P, 2, 3, 16, 1e-5, "ws", "nb", None)),
+    "rpst_masked_adain_params": ("masked_adain", (2, 3), (_P, _P, _P, _P, _P, 2, 3, 16, 12, 1e-5,
+                                                          _P, "ws", "nb", None)),
+    "rpst_conv2d_ws": ("conv2d", (2, 256, 37, 70, 96, 3, 4),
+                       (_P, _P, _P, None, None, _P, 2, 256, 37, 70, 96, 3, 0, 4, 1, "ws", "nb",
+                        None)),
+    "rpst_conv2d_stats": ("conv2d_stats", (2, 128, 37, 200, 256, 3, 0),
+                          (_P, None, _P, None, None, _P, 2, 128, 37, 200, 256, 3, 0, 0, 1, _P, _P,
+                           1e-5, "ws", "nb", None)),
+    "rpst_conv2d_stats_store": ("conv2d_stats", (2, 128, 37, 200, 256, 3, 0),
+                                (_P, None, _P, None, None, _P, 2, 128, 37, 200, 256, 3, 0, 0, 1,
+                                 _P, _P, 1e-5, 1, "ws", "nb", None)),
+    "rpst_conv2d_gated": ("conv2d_gated", (2, 32, 16, 16, 32, 1),
+                          (_P, _P, None, _P, _P, _P, 2, 32, 16, 16, 32, 1, _P, _P, 1e-5, "ws",
+                           "nb", None)),
+    "rpst_conv2d_mix": ("conv2d_mix", (2, 8, 9, 13, 32, 3),
+                        (_P, _P, _P, _P, None, _P, 2, 8, 9, 13, 32, 3, 0, 1, "ws", "nb", None)),
+    "rpst_resized_mean_std": ("resized_mean_std", (5, 7),
+                              (_P, _P, _P, 2, 3, 5, 7, 10, 14, 1e-5, "ws", "nb", None)),
+    "rpst_sanet_attention": ("sanet_attention", (2, 48),
+                             (_P, _P, _P, _P, 2, 24, 48, "ws", "nb", None)),
+    "rpst_cosine_affinity": ("cosine_affinity", (2, 24, 48),
+                             (_P, _P, _P, 2, 24, 48, "ws", "nb", None)),
+    "rpst_aea_clamp": ("aea_clamp", (2, 48, 16),
+                       (_P, _P, _P, _P, _P, _P, 16, 0, 50.0, 0.0, 1.0, _P, _P, 2, 48, "ws", "nb",
+                        None)),
+    "rpst_adaptive_attention": ("adaptive_attention", (2, 24, 48, 16),
+                                (_P, _P, _P, _P, _P, _P, _P, _P, _P, 16, 1, 50.0, 0.0, 1.0, _P,
+                                 None, None, None, 2, 24, 48, "ws", "nb", None)),
+    "rpst_sanet_attention_backward": ("sanet_attention_backward", (2, 48, 40),
+                                      (_P, _P, _P, _P, _P, _P, _P, 2, 64, 48, 40, "ws", "nb",
+                                       None)),
+    "rpst_sanet_attention_backward_chunked": ("sanet_attention_backward_chunked", (2, 64, 48, 40),
+                                              (_P, _P, _P, _P, _P, _P, _P, 2, 64, 48, 40, "ws",
+                                               "nb", None)),
+    "rpst_adaptive_attention_backward": ("adaptive_attention_backward", (2, 64, 48, 16),
+                                         (_P, _P, _P, _P, _P, _P, _P, _P, _P, 16, 0, 50.0, 0.0,
+                                          1.0, _P, _P, _P, _P, _P, _P, _P, _P, 2, 64, 48, "ws",
+                                          "nb", None)),
+    "rpst_conv1x1_wgrad": ("conv1x1_wgrad", (2, 100, 300),
+                           (_P, _P, _P, _P, 2, 100, 48, 300, "ws", "nb", None)),
+    "rpst_reflect_pad_border_grad": ("reflect_pad_border_grad", (2, 3, 5, 7),
+                                     (_P, _P, _P, 2, 3, 16, 5, 7, "ws", "nb", None)),
+    "rpst_reflect_pad_border_grad_masked": ("reflect_pad_border_grad", (2, 3, 5, 7),
+                                            (_P, _P, None, _P, 2, 3, 16, 5, 7, "ws", "nb", None)),
+    "rpst_conv_wgrad": ("conv_wgrad", (2, 16, 9, 13, 32),
+                        (_P, _P, _P, _P, 2, 16, 9, 13, 32, "ws", "nb", None)),
+    "rpst_conv_wgrad_pad": ("conv_wgrad", (2, 16, 9, 13, 32),
+                            (_P, _P, _P, _P, 2, 16, 9, 13, 32, 1, "ws", "nb", None)),
+    "rpst_conv7_wgrad": ("conv7_wgrad", (2, 3, 9, 13, 16),
+                         (_P, _P, _P, _P, 2, 3, 9, 13, 16, 1, "ws", "nb", None)),
+    # no size export: two floats per plane
+    "rpst_adain_backward": (None, 2 * 6 * 4, (_P, _P, _P, _P, _P, _P, 6, 16, "ws", "nb", None)),
+    "rpst_sq_diff_sum": ("sq_diff", (), (_P, _P, 100, 0.01, _P, "ws", "nb", None)),
+    "rpst_wct_fuse": ("wct", (2, 16, 64), (_P, _P, _P, 2, 16, 64, None, "ws", "nb", None)),
+    "rpst_wct_params": ("wct", (2, 16, 64),
+                        (_P, _P, None, _P, _P, 2, 16, 64, None, "ws", "nb", None)),
+    "rpst_whiten_and_color_f64": ("wct", (1, 16, 64), (_P, _P, _P, 16, 64, None, "ws", "nb",
+                                                       None)),
+    "rpst_whiten_and_color_original_f64": ("wct", (1, 16, 64),
+                                           (_P, _P, _P, 16, 64, "ws", "nb", None)),
+    "rpst_matrix_power_psd_f64": ("matrix_power", (16, 2),
+                                  (_P, _P, 16, 2, 0, None, "ws", "nb", None)),
+}
+
+
+def _refusals(lib):
+    """{(entry, "short" | "null"): (status, rpst_last_error())}: the workspace one byte short,
+    then null with the full byte count."""
+    out = {}
+    for entry, (size, size_args, args) in WS_ENTRIES.items():
+        need = size_args if size is None else _size_export(lib, size)(*size_args)
+        assert need > 1, entry
+        for defect, ws, nb in (("short", _P, need - 1), ("null", None, need)):
+            call = tuple({"ws": ws, "nb": nb}.get(a, a) if isinstance(a, str) else a for a in args)
+            status = getattr(lib, entry)(*call)
+            out[(entry, defect)] = (status, lib.rpst_last_error().decode())
+    return out
+
+
+WS_REFUSALS = {('rpst_adain', 'short'): (-3, 'adain: workspace 95 < 96 bytes'),
+ ('rpst_adain', 'null'): (-3, 'adain: workspace 96 < 96 bytes'),
+ ('rpst_mean_variance_norm', 'short'): (-3, 'mean_variance_norm: workspace too small'),
+ ('rpst_mean_variance_norm', 'null'): (-3, 'mean_variance_norm: workspace too small'),
+ ('rpst_masked_adain_params', 'short'): (-3,
+                                         'masked_adain_params: workspace 786431 < 786432 bytes '
+                                         '(or unaligned)'),
+ ('rpst_masked_adain_params', 'null'): (-3,
+                                        'masked_adain_params: workspace 786432 < 786432 bytes '
+                                        '(or unaligned)'),
+ ('rpst_conv2d_ws', 'short'): (-3, 'conv2d: workspace 11213575 < 11213576 bytes'),
+ ('rpst_conv2d_ws', 'null'): (-3, 'conv2d: workspace 11213576 < 11213576 bytes'),
+ ('rpst_conv2d_stats', 'short'): (-3, 'conv2d_stats: workspace 196607 < 196608 bytes'),
+ ('rpst_conv2d_stats', 'null'): (-3, 'conv2d_stats: workspace 196608 < 196608 bytes'),
+ ('rpst_conv2d_stats_store', 'short'): (-3, 'conv2d_stats: workspace 196607 < 196608 bytes'),
+ ('rpst_conv2d_stats_store', 'null'): (-3, 'conv2d_stats: workspace 196608 < 196608 bytes'),
+ ('rpst_conv2d_gated', 'short'): (-3, 'conv2d_gated: workspace 2047 < 2048 bytes'),
+ ('rpst_conv2d_gated', 'null'): (-3, 'conv2d_gated: workspace 2048 < 2048 bytes'),
+ ('rpst_conv2d_mix', 'short'): (-3, 'conv2d_mix: workspace 8639 < 8640 bytes'),
+ ('rpst_conv2d_mix', 'null'): (-3, 'conv2d_mix: workspace 8640 < 8640 bytes'),
+ ('rpst_resized_mean_std', 'short'): (-3, 'resized_mean_std: workspace 47 < 48 bytes'),
+ ('rpst_resized_mean_std', 'null'): (-3, 'resized_mean_std: workspace 48 < 48 bytes'),
+ ('rpst_sanet_attention', 'short'): (-3, 'sanet_attention: workspace 19199 < 19200 bytes'),
+ ('rpst_sanet_attention', 'null'): (-3, 'sanet_attention: workspace 19200 < 19200 bytes'),
+ ('rpst_cosine_affinity', 'short'): (-3, 'cosine_affinity: workspace too small'),
+ ('rpst_cosine_affinity', 'null'): (-3, 'cosine_affinity: workspace too small'),
+ ('rpst_aea_clamp', 'short'): (-3, 'aea_clamp: workspace too small'),
+ ('rpst_aea_clamp', 'null'): (-3, 'aea_clamp: workspace too small'),
+ ('rpst_adaptive_attention', 'short'): (-3, 'adaptive_attention: workspace 45695 < 45696 bytes'),
+ ('rpst_adaptive_attention', 'null'): (-3, 'adaptive_attention: workspace 45696 < 45696 bytes'),
+ ('rpst_sanet_attention_backward', 'short'): (-3,
+                                              'sanet_attention_backward: workspace too small'),
+ ('rpst_sanet_attention_backward', 'null'): (-3, 'sanet_attention_backward: workspace too small'),
+ ('rpst_sanet_attention_backward_chunked', 'short'): (-3,
+                                                      'sanet_attention_backward_chunked: '
+                                                      'workspace too small'),
+ ('rpst_sanet_attention_backward_chunked', 'null'): (-3,
+                                                     'sanet_attention_backward_chunked: '
+                                                     'workspace too small'),
+ ('rpst_adaptive_attention_backward', 'short'): (-3,
+                                                 'adaptive_attention_backward: workspace too '
+                                                 'small'),
+ ('rpst_adaptive_attention_backward', 'null'): (-3,
+                                                'adaptive_attention_backward: workspace too '
+                                                'small'),
+ ('rpst_conv1x1_wgrad', 'short'): (-3, 'conv1x1_wgrad: workspace too small'),
+ ('rpst_conv1x1_wgrad', 'null'): (-3, 'conv1x1_wgrad: workspace too small'),
+ ('rpst_reflect_pad_border_grad', 'short'): (-3, 'reflect_border_grad: workspace too small'),
+ ('rpst_reflect_pad_border_grad', 'null'): (-3, 'reflect_border_grad: workspace too small'),
+ ('rpst_reflect_pad_border_grad_masked', 'short'): (-3,
+                                                    'reflect_border_grad: workspace too small'),
+ ('rpst_reflect_pad_border_grad_masked', 'null'): (-3,
+                                                   'reflect_border_grad: workspace too small'),
+ ('rpst_conv_wgrad', 'short'): (-3, 'conv_wgrad: workspace too small'),
+ ('rpst_conv_wgrad', 'null'): (-3, 'conv_wgrad: workspace too small'),
+ ('rpst_conv_wgrad_pad', 'short'): (-3, 'conv_wgrad: workspace too small'),
+ ('rpst_conv_wgrad_pad', 'null'): (-3, 'conv_wgrad: workspace too small'),
+ ('rpst_conv7_wgrad', 'short'): (-3, 'conv7_wgrad: workspace too small'),
+ ('rpst_conv7_wgrad', 'null'): (-3, 'conv7_wgrad: workspace too small'),
+ ('rpst_adain_backward', 'short'): (-3, 'adain_backward: workspace too small'),
+ ('rpst_adain_backward', 'null'): (-3, 'adain_backward: workspace too small'),
+ ('rpst_sq_diff_sum', 'short'): (-3, 'sq_diff_sum: workspace too small'),
+ ('rpst_sq_diff_sum', 'null'): (-3, 'sq_diff_sum: workspace too small'),
+ ('rpst_wct_fuse', 'short'): (-3, 'wct_fuse: workspace 717239 < 717240 bytes'),
+ ('rpst_wct_fuse', 'null'): (-3, 'wct_fuse: workspace 717240 < 717240 bytes'),
+ ('rpst_wct_params', 'short'): (-3, 'wct_params: workspace 717239 < 717240 bytes'),
+ ('rpst_wct_params', 'null'): (-3, 'wct_params: workspace 717240 < 717240 bytes'),
+ ('rpst_whiten_and_color_f64', 'short'): (-3, 'whiten_and_color: workspace too small'),
+ ('rpst_whiten_and_color_f64', 'null'): (-3, 'whiten_and_color: workspace too small'),
+ ('rpst_whiten_and_color_original_f64', 'short'): (-3,
+                                                   'whiten_and_color(original): workspace too '
+                                                   'small'),
+ ('rpst_whiten_and_color_original_f64', 'null'): (-3,
+                                                  'whiten_and_color(original): workspace too '
+                                                  'small'),
+ ('rpst_matrix_power_psd_f64', 'short'): (-3, 'matrix_power: workspace too small'),
+ ('rpst_matrix_power_psd_f64', 'null'): (-3, 'matrix_power: workspace too small')}
+
+
+def test_workspace_one_byte_short_is_refused(monkeypatch):
+    """Every entry point that takes a workspace refuses one that is a byte short, and a null
+    one, with RPST_EWORKSPACE (-3) and its own message, before any launch (no GPU needed)."""
+    for k in SIZE_ENV:
+        monkeypatch.delenv(k, raising=False)
+    got = _refusals(_lib.load())
+    assert all(status == -3 for status, _ in WS_REFUSALS.values())
+    assert got == WS_REFUSALS

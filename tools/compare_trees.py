@@ -28,7 +28,10 @@ rpst_conv2d_skip_adain rpst_conv2d_stats rpst_conv2d_stats_store rpst_conv2d_mix
 rpst_conv7 rpst_maxpool2x2_ceil rpst_upsample_nearest2x rpst_conv_wgrad_pad rpst_conv7_wgrad
 rpst_conv1x1_wgrad rpst_reflect_pad_border_grad_masked rpst_reflect_pad_backward rpst_wct_fuse
 rpst_wct_params rpst_whiten_and_color_f64 rpst_whiten_and_color_original_f64
-rpst_matrix_power_psd_f64""".split()
+rpst_matrix_power_psd_f64 rpst_adain rpst_mean_variance_norm rpst_masked_adain_params
+rpst_resized_mean_std rpst_sanet_attention rpst_cosine_affinity rpst_aea_clamp
+rpst_adaptive_attention rpst_sanet_attention_backward rpst_sanet_attention_backward_chunked
+rpst_adaptive_attention_backward rpst_adain_backward rpst_sq_diff_sum""".split()
 
 RP = {"rp_blocks": 5, "hidden_dim": 16, "content_weight": 1.0, "style_weight": 10.0,
       "resume": False, "use_mask": False}
@@ -63,6 +66,7 @@ CASES = {
     "multiscale.test.mask": ("MultiScaleAdaINRPNet", (dict(MS, use_mask=True),), "test_mask:64",
                              {}),
     "ld.test": ("LDMSAdaINRPNet", (LD,), "test", {}),
+    "ld4.test": ("LDMSAdaINRPNet4", (LD,), "test", {}),
     "ld.test.inception1": ("LDMSAdaINRPNet", (dict(LD, inception_num=1),), "test", {}),
     "adain.losses": ("AdaINRPNet", (RP,), "adain_rp_losses", {}),
     "wct.losses": ("WCTRPNet", (RP,), "wct_rp_losses", {}),
@@ -90,6 +94,22 @@ CASES = {
                              "ops:matrix_power_psd", {}),
     # (n, Cin, h, w, Cout): T x + c materialised (wct_apply_f32) | folded into the weights
     "ops.conv2d_mix": (None, ((2, 8, 9, 13, 32), (1, 16, 12, 20, 32)), "ops:conv2d_mix", {}),
+    # the workspace layouts no model case reaches, at the smallest shapes that reach each branch
+    # (mode, B, HW, hidden): AEAModule | AEALReluModule
+    "ops.aea_clamp": (None, ((0, 2, 48, 16), (1, 2, 48, 16)), "ops:aea_clamp", {}),
+    "ops.cosine_affinity": (None, ((2, 24, 6, 8),), "ops:cosine_affinity", {}),
+    # C = 24: the two-GEMM path with S in the workspace
+    "ops.sanet_attention": (None, ((2, 24, 6, 8),), "ops:sanet_attention", {}),
+    # (B, C, h, w, mode, claim maps kept): two-GEMM path | flash path (C = 64, HW = 64)
+    "ops.adaptive_attention": (None, ((2, 24, 6, 8, 0, False), (2, 24, 6, 8, 1, True),
+                                      (2, 64, 8, 8, 1, False), (2, 64, 8, 8, 0, True)),
+                               "ops:adaptive_attention", {}),
+    # (entry, B, C, HWc, HWs[, hidden, mode]): the single pass | HW = 2304: two query chunks
+    "ops.attention_backward": (None, (("sanet_attention_backward", 2, 64, 48, 40),
+                                      ("sanet_attention_backward_chunked", 1, 64, 2304, 40),
+                                      ("adaptive_attention_backward", 1, 24, 2304, 2304, 8, 1)),
+                               "ops:attention_backward", {}),
+    "ops.adain": (None, ((2, 24, 6, 8),), "ops:adain", {}),
 }
 SHAPE = (2, 3, 64, 64)
 
@@ -115,8 +135,40 @@ def run_ops(name: str, items, dev) -> dict:
         return (features(10, n, C, h * w).float().reshape(n, C, h, w).to(dev),
                 features(20, n, C, h * w, dead=3).float().reshape(n, C, h, w).to(dev))
 
+    def rnd(seed, *shape):
+        return torch.randn(*shape, generator=torch.Generator().manual_seed(seed)).to(dev)
+
+    def f_psi(hw, hid):
+        torch.manual_seed(70)
+        return torch.nn.Sequential(torch.nn.Linear(hw, hid), torch.nn.LeakyReLU(0.2),
+                                   torch.nn.Linear(hid, 1)).to(dev).requires_grad_(False)
+
     for item in items:
-        if name == "wct_fuse":
+        if name == "aea_clamp":
+            mode, B, hw, hid = item
+            res = ops.aea_clamp(rnd(71, B, hw, hw).tanh(), rnd(72, B, hw, hw).softmax(-1),
+                                f_psi(hw, hid), mode, 50.0, 0.0, 1.0)
+            keys = ("clamp_fx", "clamp_value")
+        elif name == "cosine_affinity":
+            res = (ops.cosine_affinity(rnd(73, *item), rnd(74, *item)),)
+            keys = ("affinity",)
+        elif name == "sanet_attention":
+            res = (ops.sanet_attention(rnd(75, *item), rnd(76, *item), rnd(77, *item)),)
+            keys = ("out",)
+        elif name == "adaptive_attention":
+            B, C, h, w, mode, keep = item
+            res = ops.adaptive_attention(*(rnd(80 + i, B, C, h, w) for i in range(5)),
+                                         f_psi(h * w, 16), mode, 50.0, 0.0, 1.0, keep_claims=keep)
+            res = tuple(r for r in res if r is not None)
+            keys = ("out", "claim_value", "claim_before", "claim_after")
+        elif name == "attention_backward":
+            res = attention_backward(rnd, f_psi, *item)
+            keys = ("dF", "dG", "dH", "dw1", "db1", "dw2", "db2")
+        elif name == "adain":
+            x, y = rnd(90, *item), rnd(91, *item)
+            res = (ops.adaptive_instance_normalization(x, y), ops.mean_variance_norm(x))
+            keys = ("adain", "mean_variance_norm")
+        elif name == "wct_fuse":
             c, s = pair(*item)
             res = ops.wct_fuse(c, s, status=True) + ops.wct_params(c, s, status=True)
             keys = ("out", "status", "T", "offset", "residual", "params status")
@@ -152,6 +204,33 @@ def run_ops(name: str, items, dev) -> dict:
             raise KeyError(name)
         out.update({f"{item} {k}": v for k, v in zip(keys, res)})
     return out
+
+
+def attention_backward(rnd, f_psi, entry, B, C, hwc, hws, hid=0, mode=0):
+    """One attention backward entry point, called as rpst.autograd calls it, on seeded features
+    (no autograd function reaches the single pass or two query chunks at the model cases'
+    sizes) -> (dF, dG, dH[, dw1, db1, dw2, db2])."""
+    import torch
+    from rpst import _lib, ops
+    F, dO = rnd(92, B, C, hwc), rnd(93, B, C, hwc)
+    G, H = rnd(94, B, C, hws), rnd(95, B, C, hws)
+    out = [torch.empty_like(t) for t in (F, G, H)]
+    size = getattr(_lib.load(), f"rpst_{entry}_workspace_size")
+    if entry == "adaptive_attention_backward":
+        c, s = rnd(96, B, C, hwc), rnd(97, B, C, hws)
+        w1, b1, w2, b2, _ = ops._mlp_params(f_psi(hwc, hid))
+        out += [torch.empty_like(t) for t in (w1, b1, w2, b2)]
+        nbytes = size(B, C, hwc, hid)
+        args = ([t.data_ptr() for t in (F, G, H, c, s, w1, b1, w2, b2)] +
+                [hid, mode, 50.0, 0.0, 1.0, dO.data_ptr()] + [t.data_ptr() for t in out] +
+                [B, C, hwc])
+    else:
+        nbytes = size(B, hwc, hws) if entry == "sanet_attention_backward" else size(B, C, hwc, hws)
+        args = ([t.data_ptr() for t in (F, G, H, dO)] + [t.data_ptr() for t in out] +
+                [B, C, hwc, hws])
+    ws = torch.empty(nbytes, device=F.device, dtype=torch.uint8)
+    _lib.call(f"rpst_{entry}", *args, ws.data_ptr(), nbytes, ops._stream(F))
+    return tuple(out)
 
 
 def child(root: str, case: str, out_path: str) -> None:
