@@ -748,6 +748,64 @@ def gen_grad_floors(net):
     np.savez_compressed(os.path.join(HERE, "grad_floors.npz"), **out)
 
 
+FSCALES = (1.0, 0.5, 0.3, 0.2, 0.15, 0.1)
+
+
+def scan_adaptive_fscale(net):
+    """python gen_golden.py fscale_scan: how live the AEA clamp of the reference
+    AdaptiveSAModel ('aea', 64 x 64, seed 40, images 3702 / 3802) is, and what its f_psi
+    gradients' fp32 floors are (gen_grad_floors' RMS over FLOOR_SAMPLES inputs), with the
+    query convs transform.sanet4_1.f and sanet5_1.f scaled by each of FSCALES after the
+    synthetic weights: the table behind the choice of a live grads_adaptive case
+    (profiles/aea_live/fscale_scan.txt). Liveness (helpers.clamp_liveness) is of sanet4_1,
+    from the float64 oracle on the same weights. Writes no golden."""
+    sys.path.insert(0, REPO)
+    from oracle import restate as R
+    shp, seed = (1, 3, 64, 64), 40
+    c0, s0 = synth.image(3702, shp), synth.image(3802, shp)
+    print("fscale  live4_1  median max P   worst f_psi floor (RMS)   worst other floor")
+    for fs in FSCALES:
+        def model(dt):
+            m = net.AdaptiveSAModel(dict(SAM_CFG, ada_module="aea"), copy.deepcopy(net.vgg), 0,
+                                    shp[-1])
+            m.decoder = copy.deepcopy(m.decoder)
+            synth_model_(m, seed)
+            with torch.no_grad():
+                for sa in (m.transform.sanet4_1, m.transform.sanet5_1):
+                    sa.f.weight *= fs
+                    sa.f.bias *= fs
+            return m.to(dt)
+        sd = {k: v.detach().double() for k, v in model(torch.float32).state_dict().items()}
+        with torch.no_grad():
+            cf = R.encode_with_intermediate(t(c0).double(), sd, 5)[3]
+            sf = R.encode_with_intermediate(t(s0).double(), sd, 5)[3]
+            pre = "transform.sanet4_1."
+            Fm = R.conv(R.mean_variance_norm(cf), sd, pre + "f", "none", False).flatten(2)
+            Gm = R.conv(R.mean_variance_norm(sf), sd, pre + "g", "none", False).flatten(2)
+            P = torch.softmax(torch.bmm(Fm.transpose(1, 2), Gm), -1)
+            clamp = R.adaptive_sanet(cf, sf, sd, pre, "aea")[1]
+        sq = {}
+        for smp in range(FLOOR_SAMPLES):
+            c, s = c0, s0
+            if smp:
+                c, s = _ulp_perturbed(c, 7000 + 2 * smp), _ulp_perturbed(s, 7001 + 2 * smp)
+            res = {}
+            for dt in (torch.float32, torch.float64):
+                m = model(dt)
+                m.zero_grad()
+                m.forward(t(c).to(dt), t(s).to(dt))[1].backward()
+                res[dt] = {k: p.grad.detach() for k, p in m.named_parameters()
+                           if p.grad is not None}
+            for k, g64 in res[torch.float64].items():
+                sq[k] = sq.get(k, 0.0) + helpers.rel_l2(res[torch.float32][k], g64) ** 2
+        fl = {k: float(np.sqrt(v / FLOOR_SAMPLES)) for k, v in sq.items()
+              if not k.endswith("g.bias")}
+        print(f"{fs:6.2f}  {helpers.clamp_liveness(P, clamp, 'aea'):7.3f}  "
+              f"{float(P.amax(-1).median()):12.3f}   "
+              f"{max(v for k, v in fl.items() if 'f_psi' in k):23.3e}   "
+              f"{max(v for k, v in fl.items() if 'f_psi' not in k):17.3e}", flush=True)
+
+
 def gen_keys(net):
     """state_dict key/shape lists of the reference models (checkpoint compatibility)."""
     import json
@@ -782,12 +840,12 @@ GENERATORS = {"keys": gen_keys, "stats": gen_stats, "adain_rp": gen_adain_rp,
 
 
 def main():
-    """python gen_golden.py [name ...]  (default: all)"""
+    """python gen_golden.py [name ...]  (default: all; fscale_scan only by name)"""
     torch.set_num_threads(8)
     torch.manual_seed(0)
     net = _import_reference()
     for name in (sys.argv[1:] or list(GENERATORS)):
-        GENERATORS[name](net)
+        dict(GENERATORS, fscale_scan=scan_adaptive_fscale)[name](net)
     print("goldens written to", HERE)
 
 

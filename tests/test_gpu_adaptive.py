@@ -16,8 +16,8 @@ import pytest
 import torch
 import torch.nn.functional as Fn
 
-from helpers import (TOL_NET, TOL_NET_MAXABS, gen, max_abs_ratio, rel_l2, state_dict_of, synth_,
-                     t)
+from helpers import (TOL_NET, TOL_NET_MAXABS, flat_or_live, gen, max_abs_ratio, rel_l2,
+                     state_dict_of, synth_, t)
 from oracle import restate as R
 
 pytestmark = pytest.mark.gpu
@@ -154,56 +154,56 @@ def test_adaptive_attention_relu4_1_at_1024(cuda, mode):
     assert rel_l2(out, ref.view(B, C, h, w)) < 1e-5
 
 
-@pytest.mark.parametrize("mode", MODES)
-@pytest.mark.parametrize("shape", [(2, 512, 32, 32), (2, 48, 8, 10)])
-def test_factored_clamp_production_shape(cuda, mode, shape):
+@pytest.mark.parametrize("mode,shape,inputs", flat_or_live(
+    [(f"shape{i}-{mode}", (mode, shape)) for mode in MODES
+     for i, shape in enumerate([(2, 512, 32, 32), (2, 48, 8, 10)])]))
+def test_factored_clamp_production_shape(cuda, mode, shape, inputs):
     """The factored AEA clamp (Z = cn^T (sn W1^T), dW1 = (cn du)^T sn: the B x HW x HW
     affinity never formed) at a production shape (C = 512, HW = 1024, hid = 64) and at a
     ragged hidden width (HW = 80 -> hid = 5), forward clamp and backward dW1 / db1 / dW2 / db2
-    against the float64 two-GEMM form (affinity formed, torch autograd)."""
+    against the float64 two-GEMM form (affinity formed, torch autograd).
+    flat: F and G uniform x 0.2, so P ~ 1 / HW and the clamp is dead: 'aea' has Q < 1e-13 and
+    f_psi gradients of norm ~1e-12 (held to 1e-4); with 'relu' no entry of P passes its clamp
+    and dF, dG and the f_psi gradients are exactly zero on both sides, asserted as such.
+    live: F and G from helpers.peaked_attention_inputs (helpers.aea_live_case), the four f_psi
+    gradients and dF, dG, dH under the conditions and bars of helpers.aea_live_bars."""
     import network as net
-    from rpst import _lib, ops
+    from rpst import ops
+    from helpers import (aea_attention_grads, aea_backward_abi, aea_live_case, check_aea_grads,
+                         clamp_liveness)
     B, C, h, w = shape
-    hw = h * w
-    mod = net.AEAModule(hw) if mode == "aea" else net.AEALReluModule(hw)
-    synth_(mod, 11)
-    hid = mod.f_psi[0].out_features
-    assert hid == hw // 16
-    sd = {k: v.double().clone().requires_grad_(True) for k, v in state_dict_of(mod).items()}
-    F = gen(21, (B, C, h, w), 0.2)
-    G = gen(22, (B, C, h, w), 0.2)
-    H = gen(23, (B, C, h, w), 1.0)
-    c = gen(24, (B, C, h, w), 1.0, 0.2, relu=True)
-    s = gen(25, (B, C, h, w), 1.0, 0.2, relu=True)
-    dO = gen(26, (B, C, h, w), 1.0)
-    S = torch.bmm(F.view(B, C, -1).permute(0, 2, 1).double(), G.view(B, C, -1).double())
-    A = R.cal_affinity_matrix(c.double(), s.double())
-    Q, clamp = R.aea(A, torch.softmax(S, -1), sd, "", mode)
-    O = torch.bmm(H.view(B, C, -1).double(), Q.permute(0, 2, 1))
-    (O * dO.view(B, C, -1).double()).sum().backward()
+    what = f"factored clamp {mode} {shape} {inputs}"
+    if inputs == "live":
+        case = aea_live_case(mode, shape)
+        mod, clamp, O, g64 = copy.deepcopy(case.mod), case.clamp, case.out, case.g64
+        host = (case.F, case.G, case.H, case.c, case.s, case.dO)
+    else:
+        mod = net.AEAModule(h * w) if mode == "aea" else net.AEALReluModule(h * w)
+        synth_(mod, 11)
+        host = (gen(21, shape, 0.2), gen(22, shape, 0.2), gen(23, shape, 1.0),
+                gen(24, shape, 1.0, 0.2, relu=True), gen(25, shape, 1.0, 0.2, relu=True),
+                gen(26, shape, 1.0))
+        O, clamp, P, Q, g64 = aea_attention_grads(*host, state_dict_of(mod), mode, torch.float64)
+        assert clamp_liveness(P, clamp, mode) == 0.0
+    assert mod.f_psi[0].out_features == h * w // 16
     mod = mod.to(cuda)
-    args = [x.to(cuda) for x in (F, G, H, c, s)]
+    args = [x.to(cuda) for x in host]
     with torch.no_grad():
-        out, cl, _, _ = ops.adaptive_attention(*args, mod.f_psi, mod.mode, 50.0, 0.4, 0.5,
+        out, cl, _, _ = ops.adaptive_attention(*args[:5], mod.f_psi, mod.mode, 50.0, 0.4, 0.5,
                                                keep_claims=True)
-    assert rel_l2(cl, clamp.detach()) < 1e-6, rel_l2(cl, clamp.detach())
-    assert rel_l2(out, O.detach().view(B, C, h, w)) < 1e-5
-    with torch.no_grad():
-        w1, b1, w2, b2, hid2 = ops._mlp_params(mod.f_psi)
-    assert hid2 == hid
-    dF, dG, dH = (torch.empty_like(a) for a in args[:3])
-    dw1, db1, dw2, db2 = (torch.empty_like(x) for x in (w1, b1, w2, b2))
-    nbytes = _lib.load().rpst_adaptive_attention_backward_workspace_size(B, C, hw, hid)
-    ws = torch.empty(nbytes, device=cuda, dtype=torch.uint8)
-    _lib.call("rpst_adaptive_attention_backward", *(a.data_ptr() for a in args),
-              w1.data_ptr(), b1.data_ptr(), w2.data_ptr(), b2.data_ptr(), hid, mod.mode, 50.0,
-              0.4, 0.5, dO.to(cuda).data_ptr(), dF.data_ptr(), dG.data_ptr(), dH.data_ptr(),
-              dw1.data_ptr(), db1.data_ptr(), dw2.data_ptr(), db2.data_ptr(), B, C, hw,
-              ws.data_ptr(), nbytes, ops._stream(args[0]))
-    for got, key in ((dw1, "f_psi.0.weight"), (db1, "f_psi.0.bias"), (dw2, "f_psi.2.weight"),
-                     (db2, "f_psi.2.bias")):
-        ref = sd[key].grad
-        assert rel_l2(got.view_as(ref), ref) < 1e-4, (key, rel_l2(got.view_as(ref), ref))
+    assert rel_l2(cl, clamp) < 1e-6, rel_l2(cl, clamp)
+    assert rel_l2(out, O) < 1e-5
+    got, _ = aea_backward_abi(mod, *args)
+    if inputs == "live":
+        check_aea_grads(got, g64, case.bars, what)
+        return
+    fpsi = [k for k in g64 if k.startswith("f_psi")]
+    if mode == "relu":  # relu never active: zero on both sides, exactly
+        for k in ["dF", "dG"] + fpsi:
+            assert not g64[k].any() and not got[k].any(), k
+    else:
+        assert Q.max() < 1e-13
+        check_aea_grads(got, {k: g64[k] for k in fpsi}, dict.fromkeys(fpsi, 1e-4), what)
 
 
 @pytest.mark.parametrize("mode", MODES)

@@ -5,10 +5,12 @@ float64 torch autograd of O = H softmax(F^T G)^T, with a ragged last query chunk
 one chunk (HW = 600). Tolerance rel-L2 1e-5 (fp32 vs fp64, logits of moderate spread).
 The workspace has no B x HW x HW term. The single pass (rpst_sanet_attention_backward, S and
 dP whole) is the same walk with one chunk: checked against the chunked entry bit for bit."""
+import copy
+
 import pytest
 import torch
 
-from helpers import rel_l2
+from helpers import flat_or_live, rel_l2
 
 pytestmark = pytest.mark.gpu
 
@@ -89,20 +91,25 @@ def test_sanet_attention_backward_single_pass(cuda, shape):
         assert torch.equal(one[2], many[2]), "dH"
 
 
-@pytest.mark.parametrize("mode", ("aea", "relu"))
-def test_adaptive_attention_backward_query_chunks(cuda, mode):
-    """rpst_adaptive_attention_backward over query chunks (HW = 2400: 2048 + 352): the
+@pytest.mark.parametrize("mode,inputs", flat_or_live([("aea", ("aea",)), ("relu", ("relu",))]))
+def test_adaptive_attention_backward_query_chunks(cuda, mode, inputs):
+    """rpst_adaptive_attention_backward over query chunks (HW = 2400: 2048 + 352): all seven
     gradients of O = H AEA(A, softmax(F^T G))^T against float64 torch autograd of the oracle's
-    restatement (R.aea), and a workspace with no B x HW x HW term."""
+    restatement (R.aea), and a workspace with no B x HW x HW term.
+    flat: F and G are normal x 0.2, so P ~ 1 / HW (max 0.0027) and the clamp is dead. dF, dG, dH
+    within 1e-5, the f_psi gradients within max(1e-5, 3 x the oracle's own fp32 distance to
+    float64); with 'relu' no entry of P passes its clamp, so dF, dG and the f_psi gradients are
+    exactly zero on both sides, and that is what is asserted of them.
+    live: F and G from helpers.peaked_attention_inputs, all seven under the conditions and
+    bars of helpers.aea_live_bars."""
     import network as net
-    from oracle import restate as R
-    from rpst import _lib, ops
-    from helpers import state_dict_of, synth_
+    from helpers import (aea_attention_grads, aea_backward_abi, aea_fp32_forms, aea_live_bars,
+                         check_aea_grads, clamp_liveness, peaked_attention_inputs, state_dict_of,
+                         synth_)
     B, C, h, w = 1, 64, 40, 60
     hw = h * w
     mod = net.AEAModule(hw) if mode == "aea" else net.AEALReluModule(hw)
     synth_(mod, 13)
-    hid = mod.f_psi[0].out_features
     g = torch.Generator(device=cuda).manual_seed(4)
     F = torch.randn((B, C, hw), device=cuda, generator=g) * 0.2
     G = torch.randn((B, C, hw), device=cuda, generator=g) * 0.2
@@ -110,23 +117,59 @@ def test_adaptive_attention_backward_query_chunks(cuda, mode):
     c = torch.rand((B, C, hw), device=cuda, generator=g)
     s = torch.rand((B, C, hw), device=cuda, generator=g)
     dO = torch.randn((B, C, hw), device=cuda, generator=g)
-    sd = {k: v.double().to(cuda) for k, v in state_dict_of(mod).items()}
-    Fd, Gd, Hd = (x.double().clone().requires_grad_(True) for x in (F, G, H))
-    A = R.cal_affinity_matrix(c.double().view(B, C, h, w), s.double().view(B, C, h, w))
-    Q, _ = R.aea(A, torch.softmax(torch.bmm(Fd.transpose(1, 2), Gd), -1), sd, "", mode)
-    (torch.bmm(Hd, Q.transpose(1, 2)) * dO.double()).sum().backward()
-    mod = mod.to(cuda)
-    with torch.no_grad():
-        w1, b1, w2, b2, _ = ops._mlp_params(mod.f_psi)
-    nbytes = _lib.load().rpst_adaptive_attention_backward_workspace_size(B, C, hw, hid)
+    if inputs == "live":
+        F, G = (x.view(B, C, hw).to(cuda) for x in peaked_attention_inputs(B, C, h, w, 3))
+    host = [x.cpu().view(B, C, h, w) for x in (F, G, H, c, s, dO)]
+    sd = state_dict_of(mod)
+    _, clamp, P, Q, g64 = aea_attention_grads(*host, sd, mode, torch.float64)
+    g32s = aea_fp32_forms(*host, sd, mode)
+    what = f"query chunks {mode} {inputs}"
+    got, nbytes = aea_backward_abi(mod.to(cuda), F, G, H, c, s, dO)
     assert nbytes < 2 * B * hw * hw * 4, nbytes  # the single pass's S and dQ alone
-    ws = torch.empty(nbytes, device=cuda, dtype=torch.uint8)
-    dF, dG, dH = (torch.empty_like(x) for x in (F, G, H))
-    dw1, db1, dw2, db2 = (torch.empty_like(x) for x in (w1, b1, w2, b2))
-    _lib.call("rpst_adaptive_attention_backward", F.data_ptr(), G.data_ptr(), H.data_ptr(),
-              c.data_ptr(), s.data_ptr(), w1.data_ptr(), b1.data_ptr(), w2.data_ptr(),
-              b2.data_ptr(), hid, mod.mode, 50.0, 0.4, 0.5, dO.data_ptr(), dF.data_ptr(),
-              dG.data_ptr(), dH.data_ptr(), dw1.data_ptr(), db1.data_ptr(), dw2.data_ptr(),
-              db2.data_ptr(), B, C, hw, ws.data_ptr(), nbytes, ops._stream(F))
-    for got, ref, name in ((dF, Fd.grad, "dF"), (dG, Gd.grad, "dG"), (dH, Hd.grad, "dH")):
-        assert rel_l2(got, ref) < 1e-5, (name, rel_l2(got, ref))
+    if inputs == "live":
+        check_aea_grads(got, g64, aea_live_bars(g32s, g64, P, Q, clamp, mode), what)
+        return
+    assert clamp_liveness(P, clamp, mode) == 0.0
+    dead = ("dF", "dG") + tuple(k for k in g64 if k.startswith("f_psi")) if mode == "relu" else ()
+    for k in dead:  # relu never active: zero on both sides, exactly
+        assert not g64[k].any() and not got[k].any(), k
+    bars = {k: 1e-5 if k in ("dF", "dG", "dH")
+            else max(1e-5, 3.0 * max(rel_l2(g32[k], g64[k]) for g32 in g32s))
+            for k in g64 if k not in dead}
+    check_aea_grads(got, {k: g64[k] for k in bars}, bars, what)
+
+
+@pytest.mark.parametrize("mode", ("aea", "relu"))
+@pytest.mark.parametrize("shape", [(2, 48, 8, 10), (3, 64, 9, 7), (1, 512, 32, 32),
+                                   (1, 64, 35, 60)])
+def test_adaptive_attention_backward_live_clamp(cuda, mode, shape):
+    """rpst_adaptive_attention_backward where the AEA clamp is live: every query has one
+    dominant key whose probability is spread over [0.3, 0.97] (helpers.peaked_attention_inputs),
+    so the sigmoid's mid-range and both tails ('aea'), the ReLU mask and the second softmax
+    ('relu'), dc = -sum dP and the chain into f_psi all carry weight. Shapes: C = 48 is no
+    flash width (the forward's GEMM path forms S) with hid = 5; HW = 63 is odd (no 16-byte
+    rows), hid = 3, three images; (1, 512, 32, 32) is the production width, hid = 64;
+    HW = 2100 crosses the 2048-query chunk seam with a 52-row last chunk. The forward with
+    keep_claims at the bars of test_adaptive_attention_peaked, then all seven gradients against
+    float64 autograd of the oracle's restatement, each within max(1e-5, 3 x the oracle's own
+    fp32 CPU autograd's distance to float64, in the worse of its two forms)
+    (helpers.aea_live_case and aea_live_bars, which also assert the liveness conditions and
+    that no bar passes 1e-4; the generator's seed is 3, and 10 at C = 512), and a second call
+    bit for bit (the sums are fixed-order)."""
+    from rpst import ops
+    from helpers import aea_backward_abi, aea_live_case, check_aea_grads
+    case = aea_live_case(mode, shape)
+    mod = copy.deepcopy(case.mod).to(cuda)
+    F, G, H, c, s, dO = (x.to(cuda) for x in (case.F, case.G, case.H, case.c, case.s, case.dO))
+    with torch.no_grad():
+        out, cl, before, after = ops.adaptive_attention(F, G, H, c, s, mod.f_psi, mod.mode, 50.0,
+                                                        0.4, 0.5, keep_claims=True)
+    for got, ref, bar, name in ((cl, case.clamp, 1e-6, "clamp"), (before, case.P, 1e-5, "before"),
+                                (after, case.Q, 1e-5, "after"), (out, case.out, 1e-5, "out")):
+        print(f"live clamp {mode} {shape} {name}: rel-L2 {rel_l2(got, ref):.3e} (bar {bar:.0e})")
+        assert rel_l2(got, ref) < bar, (name, rel_l2(got, ref))
+    got, _ = aea_backward_abi(mod, F, G, H, c, s, dO)
+    check_aea_grads(got, case.g64, case.bars, f"live clamp {mode} {shape}")
+    again, _ = aea_backward_abi(mod, F, G, H, c, s, dO)
+    for k in got:
+        assert torch.equal(got[k], again[k]), k
