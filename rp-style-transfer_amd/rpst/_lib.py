@@ -1,5 +1,7 @@
 """ctypes binding of librpst.so (the C ABI declared in include/rpst.h).
 
+The header is the single statement of the ABI: every entry point's types and every RPST_*
+code are parsed from it at import (parse_header), not written down here again.
 The library is built in-tree (`make -C rp-style-transfer_amd/csrc`, or
 `__graft_entry__.build()`) and loaded from there; RPST_LIB overrides the path.
 There is no fallback: if the library is missing or a call fails, a RuntimeError is
@@ -9,140 +11,90 @@ from __future__ import annotations
 
 import ctypes
 import os
+import re
 import threading
 
 import torch
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("RPST_LIB", os.path.join(os.path.dirname(_HERE), "csrc", "librpst.so"))
+HEADER_PATH = os.path.join(os.path.dirname(os.path.dirname(_HERE)), "include", "rpst.h")
 
-_c_float_p = ctypes.c_void_p
 _P = ctypes.c_void_p
-_I = ctypes.c_int
-_I64 = ctypes.c_int64
-_F = ctypes.c_float
-_D = ctypes.c_double
-_SZ = ctypes.c_size_t
+# scalar type in rpst.h -> ctypes; every pointer parameter is _P, whatever it points at
+_SCALARS = {"int": ctypes.c_int, "int64_t": ctypes.c_int64, "float": ctypes.c_float,
+            "double": ctypes.c_double, "size_t": ctypes.c_size_t, "rpst_stream_t": _P}
 
-# name -> (restype, argtypes); must match include/rpst.h exactly
-SIGNATURES = {
-    "rpst_version": (_I, []),
-    "rpst_last_error": (ctypes.c_char_p, []),
-    "rpst_calc_mean_std": (_I, [_P, _P, _P, _I, _I, _I64, _F, _P]),
-    "rpst_adain_workspace_size": (_SZ, [_I, _I]),
-    "rpst_adain": (_I, [_P, _P, _P, _I, _I, _I64, _F, _P, _SZ, _P]),
-    "rpst_mean_variance_norm": (_I, [_P, _P, _I, _I, _I64, _F, _P, _SZ, _P]),
-    "rpst_segment_plan": (_I, [_P, _P, _I, _I64, _I64, _P, _P]),
-    "rpst_masked_adain_workspace_size": (_SZ, [_I, _I]),
-    "rpst_masked_adain_params": (_I, [_P, _P, _P, _P, _P, _I, _I, _I64, _I64, _F, _P, _P, _SZ,
-                                      _P]),
-    "rpst_masked_adain_apply": (_I, [_P, _P, _P, _P, _P, _I, _I, _I64, _P]),
-    "rpst_conv2d_packed_size": (_SZ, [_I, _I, _I]),
-    "rpst_conv2d_pack": (_I, [_P, _P, _I, _I, _I, _P]),
-    "rpst_conv2d_grid_threads": (_I64, [_I, _I, _I, _I, _I, _I, _I]),
-    "rpst_conv2d_algorithm": (_I, [_I, _I, _I, _I, _I, _I]),
-    "rpst_conv2d_set_precise": (_I, [_I]),
-    "rpst_conv2d_set_quarter": (_I, [_I]),
-    "rpst_conv2d_quarter": (_I, [_I, _I, _I, _I, _I, _I]),
-    "rpst_conv2d_stats_workspace_size": (_SZ, [_I, _I, _I, _I, _I, _I, _I]),
-    "rpst_conv2d_stats": (_I, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I,
-                               _P, _P, _F, _P, _SZ, _P]),
-    "rpst_conv2d_stats_store": (_I, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I,
-                                     _I, _P, _P, _F, _I, _P, _SZ, _P]),
-    "rpst_conv2d": (_I, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P]),
-    "rpst_conv2d_pool": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P]),
-    "rpst_conv2d_masked": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P]),
-    "rpst_conv2d_pair": (_I, [_P, _P, _I, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _P]),
-    "rpst_conv2d_workspace_size": (_SZ, [_I, _I, _I, _I, _I, _I, _I]),
-    "rpst_conv2d_ws": (_I, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I,
-                            _P, _SZ, _P]),
-    "rpst_conv2d_skip_adain": (_I, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _P]),
-    "rpst_se_gate": (_I, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _P]),
-    "rpst_conv2d_gated_workspace_size": (_SZ, [_I, _I, _I, _I, _I, _I]),
-    "rpst_conv2d_gated": (_I, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P, _P, _F, _P,
-                               _SZ, _P]),
-    "rpst_conv7_packed_size": (_SZ, [_I, _I]),
-    "rpst_conv7_pack": (_I, [_P, _P, _I, _I, _P]),
-    "rpst_conv7": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P]),
-    "rpst_nearest_index_table": (_I, [_I, _I, _P]),
-    "rpst_resize_nearest": (_I, [_P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _P]),
-    "rpst_resized_mean_std_workspace_size": (_SZ, [_I, _I]),
-    "rpst_resized_mean_std": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _I, _F, _P, _SZ, _P]),
-    "rpst_ld4_fuse": (_I, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P]),
-    "rpst_maxpool2x2_ceil": (_I, [_P, _P, _I, _I, _I, _I, _P]),
-    "rpst_upsample_nearest2x": (_I, [_P, _P, _I, _I, _I, _I, _P]),
-    "rpst_add_upsample_nearest2x": (_I, [_P, _P, _P, _I, _I, _I, _I, _P]),
-    "rpst_sanet_attention_workspace_size": (_SZ, [_I, _I]),
-    "rpst_sanet_attention_workspace_size_c": (_SZ, [_I, _I, _I]),
-    "rpst_sanet_attention": (_I, [_P, _P, _P, _P, _I, _I, _I, _P, _SZ, _P]),
-    "rpst_conv_weight_flip": (_I, [_P, _P, _I, _I, _I, _P]),
-    "rpst_relu_backward": (_I, [_P, _P, _P, _I64, _P]),
-    "rpst_leaky_relu_backward": (_I, [_P, _P, _P, _I64, _F, _P]),
-    "rpst_maxpool2x2_ceil_backward": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _P]),
-    "rpst_reflect_pad_border_grad_workspace_size": (_SZ, [_I, _I, _I, _I]),
-    "rpst_reflect_pad_border_grad": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _P, _SZ, _P]),
-    "rpst_reflect_pad_border_grad_masked": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _P, _SZ,
-                                                 _P]),
-    "rpst_conv_wgrad_workspace_size": (_SZ, [_I, _I, _I, _I, _I]),
-    "rpst_conv_wgrad": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _P, _SZ, _P]),
-    "rpst_conv_wgrad_pad": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P, _SZ, _P]),
-    "rpst_conv7_wgrad_workspace_size": (_SZ, [_I, _I, _I, _I, _I]),
-    "rpst_conv7_wgrad": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P, _SZ, _P]),
-    "rpst_reflect_pad_backward": (_I, [_P, _P, _I64, _I, _I, _I, _P]),
-    "rpst_adain_backward": (_I, [_P, _P, _P, _P, _P, _P, _I, _I64, _P, _SZ, _P]),
-    "rpst_style_content_loss_grad": (_I, [_P, _P, _P, _P, _P, _I, _I64, _I, _P]),
-    "rpst_sq_diff_workspace_size": (_SZ, []),
-    "rpst_sq_diff_sum": (_I, [_P, _P, _I64, _D, _P, _P, _SZ, _P]),
-    "rpst_pad1": (_I, [_P, _P, _I64, _I, _I, _I, _P]),
-    "rpst_upsample_nearest2x_backward": (_I, [_P, _P, _I64, _I, _I, _P]),
-    "rpst_mean_variance_norm_backward": (_I, [_P, _P, _P, _P, _I64, _I64, _I, _P]),
-    "rpst_softmax_rows": (_I, [_P, _P, _I64, _I, _P]),
-    "rpst_softmax_rows_backward": (_I, [_P, _P, _P, _I64, _I, _P]),
-    "rpst_sanet_attention_backward_workspace_size": (_SZ, [_I, _I, _I]),
-    "rpst_sanet_attention_backward": (_I, [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P, _SZ,
-                                           _P]),
-    "rpst_sanet_attention_backward_chunked_workspace_size": (_SZ, [_I, _I, _I, _I]),
-    "rpst_sanet_attention_backward_chunked": (_I, [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I,
-                                                   _P, _SZ, _P]),
-    "rpst_adaptive_attention_backward_workspace_size": (_SZ, [_I, _I, _I, _I]),
-    "rpst_adaptive_attention_backward": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _F, _F,
-                                              _F, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I,
-                                              _P, _SZ, _P]),
-    "rpst_conv1x1_wgrad_workspace_size": (_SZ, [_I, _I, _I]),
-    "rpst_conv1x1_wgrad": (_I, [_P, _P, _P, _P, _I, _I, _I64, _I, _P, _SZ, _P]),
-    "rpst_u8hwc_to_f32nchw": (_I, [_P, _P, _I, _I, _I, _P]),
-    "rpst_f32nchw_to_u8_tile": (_I, [_P, _P, _I, _I, _I, _I, _I, _I, _I, _P]),
-    "rpst_png_filter_up": (_I, [_P, _P, _I, _I, _I, _P]),
-    "rpst_cosine_affinity_workspace_size": (_SZ, [_I, _I, _I]),
-    "rpst_cosine_affinity": (_I, [_P, _P, _P, _I, _I, _I, _P, _SZ, _P]),
-    "rpst_aea_clamp_workspace_size": (_SZ, [_I, _I, _I]),
-    "rpst_aea_clamp": (_I, [_P, _P, _P, _P, _P, _P, _I, _I, _F, _F, _F, _P, _P, _I, _I, _P, _SZ,
-                            _P]),
-    "rpst_adaptive_attention_workspace_size": (_SZ, [_I, _I, _I, _I]),
-    "rpst_adaptive_attention": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _F, _F, _F, _P,
-                                     _P, _P, _P, _I, _I, _I, _P, _SZ, _P]),
-    "rpst_matrix_power_workspace_size": (_SZ, [_I, _I]),
-    "rpst_matrix_power_psd_f64": (_I, [_P, _P, _I, _I, _I, _P, _P, _SZ, _P]),
-    "rpst_wct_workspace_size": (_SZ, [_I, _I, _I64]),
-    "rpst_whiten_and_color_f64": (_I, [_P, _P, _P, _I, _I64, _P, _P, _SZ, _P]),
-    "rpst_wct_fuse": (_I, [_P, _P, _P, _I, _I, _I64, _P, _P, _SZ, _P]),
-    "rpst_wct_params": (_I, [_P, _P, _P, _P, _P, _I, _I, _I64, _P, _P, _SZ, _P]),
-    "rpst_wct_status": (_I, [_P, _I, _I, _I64, _P, _P]),
-    "rpst_wct_phase_timing": (_I, [_I]),
-    "rpst_wct_phase_ms": (_I, [_P, _P]),
-    "rpst_whiten_and_color_original_f64": (_I, [_P, _P, _P, _I, _I64, _P, _SZ, _P]),
-    "rpst_whiten_and_color_status": (_I, [_P, _I, _I64, _P, _P]),
-    "rpst_conv2d_mix_workspace_size": (_SZ, [_I, _I, _I, _I, _I, _I]),
-    "rpst_conv2d_mix": (_I, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _P, _SZ,
-                             _P]),
-}
+
+class RpstError(RuntimeError):
+    pass
+
+
+def parse_header(text: str):
+    """The C ABI as rpst.h states it -> ({name: (restype, [argtypes])}, {"RPST_<NAME>": int}).
+
+    A pure function of the header's text: `#define RPST_<NAME> <integer>` lines and prototypes
+    `ret name(type name, ...);` of scalars and pointers inside the extern "C" frame. A statement
+    that is no such prototype, or a type outside _SCALARS, raises RpstError: nothing is guessed."""
+    text = re.sub(r"/\*.*?\*/|//[^\n]*", " ", text, flags=re.S)
+    constants = {m[1]: int(m[2]) for m in re.finditer(
+        r"^[ \t]*#[ \t]*define[ \t]+(RPST_\w+)[ \t]+\(?(-?\d+)\)?[ \t]*$", text, re.M)}
+    text = re.sub(r'^[ \t]*#.*|extern\s+"C"\s*\{|\btypedef\b[^;]*;|\}', "", text, flags=re.M)
+
+    def ctype(decl, name, named):
+        words = [w for w in decl.replace("*", " * ").split() if w != "const"]
+        if "*" in words:
+            return _P if named or words != ["char", "*"] else ctypes.c_char_p
+        kind = " ".join(words[:-1] if named and len(words) > 1 else words)
+        if kind not in _SCALARS:
+            raise RpstError(f"rpst.h: {name}: `{decl.strip()}` has type `{kind}`, which "
+                            "rpst/_lib.py _SCALARS does not map")
+        return _SCALARS[kind]
+
+    signatures = {}
+    for proto in filter(None, (" ".join(s.split()) for s in text.split(";"))):
+        m = re.fullmatch(r"(.+?) ?\b(\w+) ?\(([^()\[\]]*)\)", proto)
+        if not m:
+            raise RpstError(f"rpst.h: `{proto}` is not a prototype the binding can read")
+        ret, name, params = m.groups()
+        params = [] if params.strip() in ("", "void") else params.split(",")
+        signatures[name] = (ctype(ret, name, False), [ctype(p, name, True) for p in params])
+    return signatures, constants
+
+
+def _read_header():
+    try:
+        with open(HEADER_PATH) as f:
+            return parse_header(f.read())
+    except OSError as e:
+        raise RpstError(f"rpst: C ABI header not found at {HEADER_PATH} ({e})") from None
+
+
+# name -> (restype, argtypes) and RPST_<NAME> -> value: what include/rpst.h declares. Mutable:
+# a tool that loads an older library deletes the entries it lacks before load()
+SIGNATURES, CONSTANTS = _read_header()
+
+
+def constants(*names: str):
+    """The header's RPST_<name> value for each name, in order (KeyError names a missing one)."""
+    return tuple(CONSTANTS["RPST_" + n] for n in names)
+
 
 _lib = None
 _lock = threading.Lock()
 
 
-class RpstError(RuntimeError):
-    pass
+def _bind(lib, signatures) -> None:
+    """Give every declared entry point of lib its restype and argtypes."""
+    for name, (res, args) in signatures.items():
+        try:
+            fn = getattr(lib, name)
+        except AttributeError:
+            raise RpstError(f"rpst: {LIB_PATH} does not export {name}, which include/rpst.h "
+                            "declares: the library is stale, rebuild it with "
+                            "`make -C rp-style-transfer_amd/csrc`") from None
+        fn.restype = res
+        fn.argtypes = args
 
 
 def load():
@@ -158,10 +110,7 @@ def load():
                 f"rpst: HIP library not found at {LIB_PATH}; build it with "
                 "`make -C rp-style-transfer_amd/csrc` or __graft_entry__.build()")
         lib = ctypes.CDLL(LIB_PATH)
-        for name, (res, args) in SIGNATURES.items():
-            fn = getattr(lib, name)
-            fn.restype = res
-            fn.argtypes = args
+        _bind(lib, SIGNATURES)
         _lib = lib
     return _lib
 

@@ -582,7 +582,8 @@ def _transform_backward(tr, saved, g, grads):
     dw, db = conv_wgrad(z, g, c, ops.PAD_REFLECT)
     _acc(grads, c.weight, dw)
     _acc(grads, c.bias, db)
-    dz = conv_dgrad(g, plan.ConvStep(conv=c, pad=ops.PAD_REFLECT, in_op=ops.IN_NONE, relu=0))
+    dz = conv_dgrad(g, plan.ConvStep(conv=c, pad=ops.PAD_REFLECT, in_op=ops.IN_NONE,
+                                     relu=ops.ACT_NONE))
     _sanet_backward(tr.sanet4_1, sa, dz, grads)
     _sanet_backward(tr.sanet5_1, sb, _upsample_backward(dz), grads)
 

@@ -15,9 +15,17 @@ import torch
 
 from . import _lib
 
-PAD_ZERO, PAD_REFLECT = 0, 1
-IN_NONE, IN_MAXPOOL2, IN_UPSAMPLE2, IN_ADD_UPSAMPLE2, IN_ADAIN, IN_ADD_ADAIN = 0, 1, 2, 3, 4, 5
-ACT_NONE, ACT_RELU, ACT_LRELU = 0, 1, 2  # conv epilogue: none / ReLU / LeakyReLU(0.2)
+# the codes of include/rpst.h (RPST_<name>), read from it
+PAD_ZERO, PAD_REFLECT = _lib.constants("PAD_ZERO", "PAD_REFLECT")
+IN_NONE, IN_MAXPOOL2, IN_UPSAMPLE2, IN_ADD_UPSAMPLE2, IN_ADAIN, IN_ADD_ADAIN = _lib.constants(
+    "IN_NONE", "IN_MAXPOOL2", "IN_UPSAMPLE2", "IN_ADD_UPSAMPLE2", "IN_ADAIN", "IN_ADD_ADAIN")
+# conv epilogue: none / ReLU / LeakyReLU(0.2)
+ACT_NONE, ACT_RELU, ACT_LRELU = _lib.constants("ACT_NONE", "ACT_RELU", "ACT_LRELU")
+# rpst_conv2d_algorithm
+ALGO_DIRECT, ALGO_WINOGRAD, ALGO_WINOGRAD4, ALGO_NARROW = _lib.constants(
+    "CONV_DIRECT", "CONV_WINOGRAD", "CONV_WINOGRAD4", "CONV_NARROW")
+# rpst_wct_status bits
+WCT_NOCONV, WCT_TIMEOUT = _lib.constants("WCT_NOCONV", "WCT_TIMEOUT")
 
 
 def _act(relu) -> int:
@@ -367,8 +375,8 @@ def conv_out_hw(h: int, w: int, in_op: int) -> Tuple[int, int]:
     return h, w
 
 
-ALGO_DIRECT, ALGO_WINOGRAD, ALGO_WINOGRAD4, ALGO_NARROW = 0, 1, 2, 3  # rpst_conv2d_algorithm
-_ALGO_TAG = {0: "conv", 1: "wino", 2: "wino4", 3: "narrow"}
+_ALGO_TAG = {ALGO_DIRECT: "conv", ALGO_WINOGRAD: "wino", ALGO_WINOGRAD4: "wino4",
+             ALGO_NARROW: "narrow"}
 
 
 def _conv_name(ksize, cin, cout, hs, ws, n, in_op):
@@ -448,7 +456,7 @@ def pool_pass_pays(x, cout: int, ksize: int) -> bool:
     profiles/r01_bench_sanet_w4*)."""
     n, cin, h, w = _shape(x)
     return ksize == 3 and _lib.load().rpst_conv2d_algorithm(
-        cout, cin, (h + 1) // 2, (w + 1) // 2, ksize, IN_NONE) == 2
+        cout, cin, (h + 1) // 2, (w + 1) // 2, ksize, IN_NONE) == ALGO_WINOGRAD4
 
 
 def conv2d_pair(x: torch.Tensor, x2: torch.Tensor, packed: torch.Tensor,
@@ -510,7 +518,7 @@ def conv2d_pool_fuses(x: torch.Tensor, cout: int, ksize: int, in_op: int = IN_NO
         return False
     n, cin, hs, ws = _shape(x)
     return in_op in (IN_NONE, IN_ADAIN, IN_UPSAMPLE2) and _lib.load().rpst_conv2d_algorithm(
-        cout, cin, hs, ws, ksize, in_op) == 2
+        cout, cin, hs, ws, ksize, in_op) == ALGO_WINOGRAD4
 
 
 def conv2d_pool(x: torch.Tensor, packed: torch.Tensor, bias: Optional[torch.Tensor], cout: int,
@@ -960,10 +968,6 @@ def whiten_and_color(cF: torch.Tensor, sF: torch.Tensor, method: str = 'closed-f
         _lib.call("rpst_whiten_and_color_status", ws.data_ptr(), C, hw, st.data_ptr(),
                   _stream(cF))
     return out, st
-
-
-WCT_NOCONV = 1   # include/rpst.h RPST_WCT_NOCONV
-WCT_TIMEOUT = 4  # include/rpst.h RPST_WCT_TIMEOUT
 
 
 def check_wct_status(status: torch.Tensor, what: str = "wct") -> None:

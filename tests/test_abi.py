@@ -1,6 +1,7 @@
 """C-ABI checks that need no GPU: the library loads, exports every symbol the header
-declares, the ctypes table matches the header, and argument validation reports errors
-through status codes + rpst_last_error() without touching the device."""
+declares (the ctypes table is derived from the header: tests/test_abi_header.py), a stale
+library is refused by name, and argument validation reports errors through status codes +
+rpst_last_error() without touching the device."""
 import ctypes
 import os
 import re
@@ -30,8 +31,14 @@ def test_library_exports_every_header_symbol():
         assert hasattr(lib, name), f"{name} declared in rpst.h but not exported"
 
 
-def test_ctypes_table_matches_header():
-    assert sorted(_lib.SIGNATURES) == header_functions()
+def test_stale_library_is_named():
+    """A library that lacks a symbol the header declares (an old build) is refused with the
+    symbol's name and the advice to rebuild, not with a bare AttributeError."""
+    table = dict(_lib.SIGNATURES, rpst_added_since_the_build=(ctypes.c_int, [ctypes.c_int]))
+    with pytest.raises(_lib.RpstError, match="rpst_added_since_the_build.*rebuild"):
+        _lib._bind(ctypes.CDLL(_lib.LIB_PATH), table)
+    assert "rpst_added_since_the_build" not in _lib.SIGNATURES
+    _lib._bind(ctypes.CDLL(_lib.LIB_PATH), dict(_lib.SIGNATURES))
 
 
 def test_version_and_error_string():
