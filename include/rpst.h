@@ -651,7 +651,8 @@ int rpst_wct_phase_ms(float* cov_ms, float* matfun_ms);
  * Workspace: rpst_conv2d_mix_workspace_size(N, Cin, H, W, Cout, ksize). It does not depend on
  * the quarter setting but does on the precise level: at rpst_conv2d_set_precise(1) the layer
  * leaves F(4x4) and the workspace holds T x + c (N*Cin*H*W floats), which every inference
- * workspace would otherwise carry. Query it at the level the launch runs under. */
+ * workspace would otherwise carry. Query it at the level the launch runs under. ksize is 1
+ * or 3: another one sizes as 0 bytes and is refused (RPST_EINVAL) before any launch. */
 size_t rpst_conv2d_mix_workspace_size(int N, int Cin, int H, int W, int Cout, int ksize);
 int rpst_conv2d_mix(const float* input, const double* T, const double* offset,
                     const float* packed_weight, const float* bias, float* out, int N, int Cin,

@@ -1155,8 +1155,8 @@ extern "C" int rpst_conv2d_ws(const float* input, const float* aux, const float*
 // The fold does not depend on the quarter setting, and neither does its size (wino4_mix_floats
 // takes the larger weight image); at precise level 1 the layer runs F(2x2) on z.
 // fold: the per-image weights and border biases; else z = T x + c, then wct_apply_f32's
-// scratch. Known fault, kept as it was: a ksize other than 1 or 3 sizes as 0 bytes but is
-// carved like a direct layer, and rpst_conv2d_mix writes z before conv_common refuses the ksize.
+// scratch. A ksize other than 1 or 3 sizes as 0 bytes; rpst_conv2d_mix refuses it before it
+// asks for the layout.
 struct MixLayout { float *fold_ws, *z, *scratch; size_t bytes; };
 static MixLayout mix_layout(void* workspace, int N, int Cin, int H, int W, int Cout, int ksize,
                             const ConvMode& m) {
@@ -1186,6 +1186,8 @@ extern "C" int rpst_conv2d_mix(const float* input, const double* T, const double
                                rpst_stream_t stream) {
   RPST_REQUIRE(input && T && offset && packed_weight && out, "conv2d_mix: null pointer");
   RPST_REQUIRE(N > 0 && Cin > 0 && Cout > 0 && H > 0 && W > 0, "conv2d_mix: bad shape");
+  // before the layout: another ksize sizes as 0 bytes, and the fallback below writes z
+  RPST_REQUIRE(ksize == 1 || ksize == 3, "conv2d_mix: ksize must be 1 or 3, got %d", ksize);
   const ConvMode m = conv_mode();
   const MixLayout L = mix_layout(workspace, N, Cin, H, W, Cout, ksize, m);
   RPST_REQUIRE_WS(L.bytes, "conv2d_mix: workspace %zu < %zu bytes", workspace_bytes, L.bytes);

@@ -181,6 +181,21 @@ def test_conv2d_argument_errors(args, msg):
         _lib.call("rpst_conv2d", *args)
 
 
+def test_conv2d_mix_refuses_ksize_before_the_layout():
+    """rpst_conv2d_mix refuses a ksize other than 1 or 3 with conv2d's status and wording
+    before it lays out its workspace: that ksize sizes as 0 bytes, which any workspace
+    satisfies, and the layer's fallback writes z = T x + c into the workspace ahead of the
+    conv's own ksize check. Placeholder pointers: the refusal comes before any launch."""
+    lib = _lib.load()
+    assert lib.rpst_conv2d_mix_workspace_size(2, 8, 9, 13, 32, 5) == 0
+    args = (1, 1, 1, 1, None, 1, 2, 8, 9, 13, 32, 5, 0, 0, None, 0, None)
+    assert lib.rpst_conv2d_mix(*args) == -1
+    assert lib.rpst_last_error().decode() == "conv2d_mix: ksize must be 1 or 3, got 5"
+    with pytest.raises(_lib.RpstError, match="ksize must be 1 or 3, got 5"):
+        _lib.call("rpst_conv2d_mix", *args)
+    assert lib.rpst_conv2d_mix_workspace_size(2, 8, 9, 13, 32, 5) == 0
+
+
 @pytest.mark.parametrize("n1,n,msg", [(0, 4, "0 < n1 <= N"), (5, 4, "0 < n1 <= N"),
                                        (2, 4, "null second input")])
 def test_conv2d_pair_argument_errors(n1, n, msg):

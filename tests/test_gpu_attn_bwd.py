@@ -4,13 +4,17 @@ float64 torch autograd of O = H softmax(F^T G)^T, with a ragged last query chunk
 = 2048 + 352), two chunks at C = 512 (HW = 4096), HWc != HWs (1200 queries, 2100 keys) and
 one chunk (HW = 600). Tolerance rel-L2 1e-5 (fp32 vs fp64, logits of moderate spread).
 The workspace has no B x HW x HW term. The single pass (rpst_sanet_attention_backward, S and
-dP whole) is the same walk with one chunk: checked against the chunked entry bit for bit."""
+dP whole) is the same walk with one chunk: checked against the chunked entry bit for bit.
+Peaked rows (|S| to 117, the regime training runs in) over several tiles, on both entries:
+test_sanet_attention_backward_peaked_rows, bars from the CPU float32 form's own error."""
 import copy
 
 import pytest
 import torch
 
 from helpers import flat_or_live, rel_l2
+from train_glue_ref import (ATTN_GRADS, ATTN_PEAKED, attn_peaked_case, row_peak_median,
+                            row_sum_residue)
 
 pytestmark = pytest.mark.gpu
 
@@ -89,6 +93,62 @@ def test_sanet_attention_backward_single_pass(cuda, shape):
     if hw <= 2048:
         assert torch.equal(one[1], many[1]), "dG"
         assert torch.equal(one[2], many[2]), "dH"
+
+
+@pytest.mark.parametrize("case", ATTN_PEAKED)
+def test_sanet_attention_backward_peaked_rows(cuda, case):
+    """Both entries on peaked rows over several tiles, the regime training runs in (at
+    relu4_1 the logits span ~100 per row): the tests above feed moderate logits (|S| <= 10,
+    median largest probability 0.1), and the peaked rows of test_sanet_backward have at most 64
+    keys, one lane pass of the row kernels, one GEMM tile and one query chunk. The cases
+    (train_glue_ref.ATTN_PEAKED: uniform F, G scaled by 3, 2 or 1) reach |S| of 38 to 117
+    with ragged tiles and HWc != HWs, a C off the 16-byte path, one element past a tile on both
+    sides, the 2048-query seam, and C = 512 over 8 x 8 tiles. The reference is _ref_grads'
+    float64 autograd, formed once on the CPU and shared with tests/test_train_glue_cpu.py
+    (train_glue_ref.attn_peaked_case). On it the
+    median over the rows of the largest probability is >= 0.7. dF, dG, dH are finite and
+    each within max(1e-5, 3 x the CPU float32 torch form's rel-L2 against float64), a bar
+    that never passes 1e-4 (the factor 3 is _floor_bars'). Between the entries: dF bit-equal,
+    dG and dH bit-equal where HWc <= 2048. sum_j dG[c][j] ~ 0 at the chunked test's bar, 5e-5 of
+    max|dG|, the CPU float32 form's own residue printed beside it."""
+    from rpst import _lib, ops
+    B, C, hw, hws, _ = case
+    inputs, S, P, g64, f32 = attn_peaked_case(case)
+    peak = row_peak_median(P)
+    print(f"peaked rows {case}: |S| max {float(S.abs().max()):.1f}, peak median {peak:.3f}")
+    assert peak >= 0.7, peak
+    bars = {k: max(1e-5, 3.0 * f32[k]) for k in ATTN_GRADS}
+    assert all(b <= 1e-4 for b in bars.values()), bars
+    F, G, H, dO = (x.to(cuda) for x in inputs)
+    lib = _lib.load()
+    sizes = (("rpst_sanet_attention_backward",
+              lib.rpst_sanet_attention_backward_workspace_size(B, hw, hws)),
+             ("rpst_sanet_attention_backward_chunked",
+              lib.rpst_sanet_attention_backward_chunked_workspace_size(B, C, hw, hws)))
+    got = {}
+    for fn, nbytes in sizes:
+        ws = torch.empty(nbytes, device=cuda, dtype=torch.uint8)
+        got[fn] = dict(zip(ATTN_GRADS, (torch.empty_like(x) for x in (F, G, H))))
+        _lib.call(fn, F.data_ptr(), G.data_ptr(), H.data_ptr(), dO.data_ptr(),
+                  *(got[fn][k].data_ptr() for k in ATTN_GRADS), B, C, hw, hws, ws.data_ptr(),
+                  nbytes, ops._stream(F))
+    errs = {fn: {k: rel_l2(g[k], g64[k]) for k in ATTN_GRADS} for fn, g in got.items()}
+    gsums = {fn: row_sum_residue(g["dG"]) for fn, g in got.items()}
+    for fn in got:
+        for k in ATTN_GRADS:
+            print(f"{fn} {case} {k}: rel-L2 {errs[fn][k]:.3e} (bar {bars[k]:.3e}, "
+                  f"fp32 {f32[k]:.3e})")
+        print(f"{fn} {case} dG row sums: {gsums[fn]:.3e} (bar 5e-05, fp32 {f32['gsum']:.3e})")
+    for fn, g in got.items():
+        for k in ATTN_GRADS:
+            assert torch.isfinite(g[k]).all(), (fn, k)
+            assert errs[fn][k] < bars[k], (fn, k, errs[fn][k], bars[k])
+        assert gsums[fn] < 5e-5, (fn, gsums[fn])
+    one, many = got.values()
+    assert torch.equal(one["dF"], many["dF"]), "dF"
+    if hw <= 2048:
+        assert torch.equal(one["dG"], many["dG"]), "dG"
+        assert torch.equal(one["dH"], many["dH"]), "dH"
 
 
 @pytest.mark.parametrize("mode,inputs", flat_or_live([("aea", ("aea",)), ("relu", ("relu",))]))

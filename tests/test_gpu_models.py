@@ -86,17 +86,30 @@ def test_sanet_attention_vs_oracle(cuda, shape):
     assert rel_l2(out, ref) < 1e-5
 
 
-def test_sanet_attention_large_logits(cuda):
-    """Logits in the hundreds: exercises the max subtraction of the softmax."""
-    from rpst import ops
-    B, C, h, w = 1, 64, 16, 16
-    F = gen(5, (B, C, h, w), 3.0)
-    G = gen(6, (B, C, h, w), 3.0)
+@pytest.mark.parametrize("B,C,h,w,scale,smax", [
+    pytest.param(1, 64, 16, 16, 3.0, 100, id="flash-c64-hw256"),
+    # C = 40 is no flash width: S is materialised; HW = 255 is odd (|S| max 157)
+    pytest.param(1, 40, 15, 17, 4.0, 100, id="materialised-c40-hw255"),
+    # 180 keys, ragged against the 64-query block (|S| max 98)
+    pytest.param(2, 128, 9, 20, 2.5, 60, id="flash-c128-hw180"),
+    # the training channel count (|S| max 78)
+    pytest.param(1, 512, 16, 17, 1.5, 60, id="flash-c512-hw272")])
+def test_sanet_attention_large_logits(cuda, B, C, h, w, scale, smax):
+    """Logits in the hundreds: exercises the max subtraction of the softmax, on the flash path
+    and on the materialised-S path, at ragged HW. (CPU float32 torch reads 1.4e-6 to 2.2e-6
+    on these outputs.)"""
+    from rpst import _lib, ops
+    F = gen(5, (B, C, h, w), scale)
+    G = gen(6, (B, C, h, w), scale)
     H = gen(7, (B, C, h, w), 1.0)
     S = torch.bmm(F.view(B, C, -1).permute(0, 2, 1).double(), G.view(B, C, -1).double())
-    assert S.abs().max() > 100
+    assert S.abs().max() > smax
+    flash = _lib.load().rpst_sanet_attention_workspace_size_c(1, C, h * w) == 0
+    assert flash == (C != 40)  # which path the case is there for
     ref = torch.bmm(H.view(B, C, -1).double(), torch.softmax(S, -1).permute(0, 2, 1)).view(B, C, h, w)
     out = ops.sanet_attention(F.to(cuda), G.to(cuda), H.to(cuda))
+    print(f"large logits {(B, C, h, w, scale)}: |S| max {float(S.abs().max()):.1f}, "
+          f"rel-L2 {rel_l2(out, ref):.3e}")
     assert rel_l2(out, ref) < 1e-5
 
 

@@ -356,13 +356,17 @@ def _sam_model(seed, img, cuda):
     return m.to(cuda)
 
 
-@pytest.mark.parametrize("shape", [(2, 512, 8, 8, 8, 8), (1, 512, 4, 4, 4, 4), (1, 64, 9, 7, 9, 7)])
+@pytest.mark.parametrize("shape", [(2, 512, 8, 8, 8, 8), (1, 512, 4, 4, 4, 4), (1, 64, 9, 7, 9, 7),
+                                   (1, 64, 20, 23, 20, 23), (2, 128, 17, 19, 17, 19)])
 def test_sanet_backward(cuda, shape):
     """rpst.autograd._sanet_forward / _sanet_backward (1x1 convs, mean_variance_norm,
     attention: S, dP, dF, dG on rocBLAS, softmax and its backward as kernels) against
     float64 autograd of oracle.sanet on the same fp32 inputs; content c is (n, C, hc, wc),
     style s (n, C, hs, ws) (the attention kernel takes equal sizes, as SAModel has). Output
-    rel-L2 1e-5, parameter gradients 1e-4."""
+    rel-L2 1e-5, parameter gradients 1e-4. The last two shapes (HW = 460 and 323) take the
+    per-plane and per-row loops past one stride and the GEMMs past one tile, on peaked rows
+    (median largest probability 0.94 and 0.99); the oracle's own CPU float32 gradients read
+    at worst 5.5e-6 and 8.3e-6 there."""
     import network as net
     from rpst import autograd as A
     n, C, hc, wc, hs, ws = shape
@@ -388,7 +392,79 @@ def test_sanet_backward(cuda, shape):
         e = rel_l2(grads[id(p)], sd[name].grad)
         worst = max(worst, e)
         assert e < 1e-4, (name, e)
-    print(f"sanet backward {shape}: worst {worst:.3e}")
+    print(f"sanet backward {shape}: worst {worst:.3e}, "
+          f"median largest probability {_peak_median(c, s, sd, ''):.3f}")
+
+
+def _peak_median(c, s, sd, prefix):
+    """Median over the query rows of the largest softmax probability of oracle.sanet's
+    attention on (c, s), in float64."""
+    with torch.no_grad():
+        Fm = R.conv(R.mean_variance_norm(c.double()), sd, prefix + "f", "none", False).flatten(2)
+        Gm = R.conv(R.mean_variance_norm(s.double()), sd, prefix + "g", "none", False).flatten(2)
+        P = torch.softmax(torch.bmm(Fm.transpose(1, 2), Gm), -1)
+    return float(P.amax(-1).flatten().median())
+
+
+@pytest.mark.parametrize("C,hw4,hw5", [(64, (20, 24), (10, 12)), (128, (18, 22), (9, 11))])
+def test_transform_backward(cuda, C, hw4, hw5):
+    """rpst.autograd._transform_forward / _transform_backward on a Transform above 64 pixels
+    (relu4_1 planes of 480 and 396 pixels, relu5_1 of 120 and 99) against float64 autograd of
+    oracle.transform on the same fp32 inputs: the merge conv's reflect wgrad and dgrad,
+    _upsample_backward into sanet5_1, and the two SANets' parameter gradients summed through
+    _acc into one dict. Output rel-L2 1e-5; every parameter gradient within max(1e-4, 3 x the
+    oracle's own fp32 distance to float64) (_floor_bars; the fp32 floors are <= 7.3e-6 on a
+    CPU, so the bars are 1e-4); g.bias (exact gradient zero) within TOL_GBIAS of max|f.bias
+    grad| (the CPU fp32 residue is 5e-7 of it). C stops at 128: at C = 512 and 24 x 24 the
+    fp32 floor alone is 2.8e-5."""
+    import network as net
+    from rpst import autograd as A
+    tr = net.Transform(C)
+    synth_(tr, 71)
+    shape4, shape5 = (1, C) + hw4, (1, C) + hw5
+    c4 = torch.relu(gen(72, shape4, 2.0, 0.3))
+    s4 = torch.relu(gen(73, shape4, 1.5, 0.2))
+    c5 = torch.relu(gen(74, shape5, 2.0, 0.3))
+    s5 = torch.relu(gen(75, shape5, 1.5, 0.2))
+    g = gen(76, shape4)
+
+    def cpu_grads(dtype):
+        sd = {k: v.to(dtype).requires_grad_() for k, v in state_dict_of(tr).items()}
+        out = R.transform(*(x.to(dtype) for x in (c4, s4, c5, s5)), sd, "")
+        out.backward(g.to(dtype))
+        return out.detach(), sd, {k: v.grad for k, v in sd.items()}
+
+    ref, sd, g64 = cpu_grads(torch.float64)
+    _, _, g32 = cpu_grads(torch.float32)
+    bars = _floor_bars(g32, g64)
+    what = f"transform backward C{C} {hw4}"
+    print(f"{what}: median largest probability sanet4_1 "
+          f"{_peak_median(c4, s4, sd, 'sanet4_1.'):.3f}, sanet5_1 "
+          f"{_peak_median(c5, s5, sd, 'sanet5_1.'):.3f}")
+    tr = tr.to(cuda)
+    with torch.no_grad():
+        out, saved = A._transform_forward(tr, *(x.to(cuda) for x in (c4, s4, c5, s5)))
+        grads = {}
+        A._transform_backward(tr, saved, g.to(cuda), grads)
+    print(f"{what} out: rel-L2 {rel_l2(out, ref):.3e} (bar 1e-05)")
+    assert rel_l2(out, ref) < 1e-5, rel_l2(out, ref)
+    named = dict(tr.named_parameters())
+    assert sorted(named) == sorted(g64) and set(grads) == {id(p) for p in named.values()}
+    errs = {}
+    for name, p in named.items():
+        if _is_gbias(name):
+            fb = grads[id(named[name.replace(".g.", ".f.")])].abs().max()
+            fb64 = g64[name.replace(".g.", ".f.")].abs().max()
+            errs[name] = float(grads[id(p)].abs().max() / fb)
+            print(f"{what} {name}: max {errs[name]:.3e} of max|f.bias grad| (bar {TOL_GBIAS:.0e},"
+                  f" fp32 {float(g32[name].abs().max() / fb64):.3e})")
+        else:
+            errs[name] = rel_l2(grads[id(p)], g64[name])
+            print(f"{what} {name}: rel-L2 {errs[name]:.3e} (bar {bars[name]:.3e}, "
+                  f"fp32 {rel_l2(g32[name], g64[name]):.3e})")
+    for name in named:
+        bar = TOL_GBIAS if _is_gbias(name) else bars[name]
+        assert errs[name] <= bar if _is_gbias(name) else errs[name] < bar, (name, errs[name], bar)
 
 
 def test_samodel_training_gradients_match_reference(cuda, golden):
