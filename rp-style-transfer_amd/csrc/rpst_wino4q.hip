@@ -77,6 +77,16 @@ __device__ __forceinline__ void q_dma4(__amdgpu_buffer_rsrc_t r, unsigned m0, un
   asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tbuffer_load_dword %1, %2, %3 offen lds"
                :: "s"(m0), "v"(voff), "s"(r), "s"(soff) : "memory");
 }
+// the lane's index in its wave, derived where it is called (mbcnt over an opaque zero, 3 VALU):
+// the epilogue's lane coordinates kept from the kernel's start would be live across the K
+// loop, which has no VGPR to spare
+__device__ __forceinline__ int q_lane_here() {
+  int z = 0;
+#if __HIP_DEVICE_COMPILE__
+  asm volatile("" : "+v"(z));
+#endif
+  return (int)__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, (unsigned)z));
+}
 __device__ __forceinline__ void q_lds_barrier() {
   asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
   __builtin_amdgcn_s_barrier();
@@ -128,7 +138,9 @@ static_assert(10 * kQRP <= kQDMA4 * 64 && kQDMA4 * 256 <= kQCS, "16-B pieces in 
 static_assert(10 * kQPS <= kQDMA * 64 && kQDMA * 64 <= kQCS, "4-B pieces in a channel");
 static_assert(2 * kQWide >= kQDMA4 && 2 * kQSlow >= kQDMA && 8 * kQWPI >= 36, "coverage");
 static_assert(2 * kQXS <= kQWS, "the exchange fits a weight stage");
-static_assert((2 * kQWS + 4 * kQPAT) * 4 + 1024 + kQSlow * kQNTH * 4 + 9 * kQMaxCo * 4 <= 163840,
+constexpr int kQEpiB = 1024;  // epilogue context: two tile-row records + 32 row-offset vectors
+static_assert((2 * kQWS + 4 * kQPAT) * 4 + 1024 + kQSlow * kQNTH * 4 + 9 * kQMaxCo * 4 + kQEpiB <=
+                  163840,
               "LDS");
 
 // ---- weight transform + packing -------------------------------------------------------
@@ -259,72 +271,105 @@ ConvTiling wino4q_tiling(ConvArgs& a) {
 }
 
 // ---- the epilogue of one finished 4x4 tile and channel ---------------------------------
-struct QEpi {
-  int W, H, Cout, gy0, gx0, rows, n, sidx;
-  bool vec, full, bst, edge, store, pool;
-  float inv, slope;
-  unsigned voff[4];
+// What it needs besides the tile never changes over the life of a block, so it is derived
+// once, before the ring starts (q_epi_fill), into LDS: one record per tile row wr and one
+// vector of output row offsets per (wr, tn). Each channel's epilogue reads them back with LDS
+// instructions only (q_finish): kept in registers across the exchange passes the context
+// overflows the scalar registers, and re-derived from the kernel arguments per channel (the
+// form this replaces) it cost scalar loads, three integer divisions and the flag arithmetic
+// four times per co tile and wave with no MFMA in flight to hide them.
+struct QEpiRec {
+  float* oimg;       // bst: image n's output planes, obytes bytes (0: an image past skip_from)
   float* out;
-  float* oimg;
+  float2* stat;      // channel 0's statistics partial of (n, this tile row)
   unsigned obytes;
-  const float* btab;
-  float2* statp;
-  int statP;
+  unsigned hw4;      // bytes of one output plane (bst)
+  int W, H, Cout, gy0, bx0, rows, n;
+  unsigned flags;    // kQF*
+  float inv, slope;
 };
+constexpr unsigned kQFFull = 1, kQFEdge = 2, kQFBst = 4, kQFPool = 8, kQFStore = 16;
+// (a pointer read back from LDS is generic; these keep the epilogue's stores global_store)
+typedef float floatx2 __attribute__((ext_vector_type(2)));
+typedef __attribute__((address_space(1))) float gfloat;
+typedef __attribute__((address_space(1))) floatx2 gfloatx2;
+typedef __attribute__((address_space(1))) floatx4 gfloatx4;
+static_assert(2 * (sizeof(QEpiRec) + 15) / 16 * 16 + 2 * 16 * 16 <= kQEpiB, "LDS");
 
 // Block order (w4_tile; tools/ab_bench_libs.sh, profiles/r05/order_ab.log; configs[1], two
 // rounds): row tile fastest with the hardware's round-robin XCD assignment (consecutive blocks
 // on consecutive XCDs) 553.3 / 553.1 img/s; column tile fastest with consecutive logical blocks
 // on one XCD (the round-4 choice) 548.3 / 547.3; row tile fastest on one XCD 534.7; column
 // tile fastest round-robin 536.2; image-fastest orders 503-538.
-__device__ __forceinline__ QEpi q_epi_ctx(int wr, int tn) {
-  const KArgs L = late_args();
-  QEpi e;
-  e.W = L->W;
-  e.H = L->H;
-  e.Cout = L->Cout;
-  e.slope = L->relu == RPST_ACT_RELU ? 0.f : (L->relu == RPST_ACT_LRELU ? 0.2f : 1.f);
-  int btx, bty;
-  w4_tile((int)blockIdx.x / L->cosplit, L->tiles_x, L->tiles_y, btx, bty, e.n);
-  const int bx0 = btx * kQTW;
-  e.gy0 = bty * kQTH + 4 * wr;
-  e.gx0 = bx0 + 4 * tn;
-  e.vec = (e.W & 3) == 0 && e.gx0 + 3 < e.W;
-  e.rows = max(0, min(4, e.H - e.gy0));
-  const int cols = max(0, min(kQTW, e.W - bx0));
-  // (v_rcp: exact for the 256-pixel full tiles; the IEEE division's ~10-instruction sequence
-  // ran per channel)
-  e.inv = e.rows * cols > 0 ? __builtin_amdgcn_rcpf((float)(e.rows * cols)) : 0.f;
-  e.full = e.rows == 4 && bx0 + kQTW <= e.W;
-  e.edge = e.gy0 == 0 || e.gy0 + 4 >= e.H || bx0 == 0 || bx0 + kQTW >= e.W;
-  e.out = L->out;
-  const int64_t plane = (int64_t)e.H * e.W;
-  e.pool = L->pool_out != 0;
-  e.bst = !e.pool && (e.W & 3) == 0 && (int64_t)e.Cout * plane * 4 < (1LL << 31);
-  e.oimg = e.out + (int64_t)e.n * e.Cout * plane;
-  const bool keep = L->skip_from <= 0 || e.n < L->skip_from;
-  e.obytes = keep ? (unsigned)(e.Cout * plane * 4) : 0u;
-  e.store = keep;
+//
+// thread t < 32 of block (tx, ty, n) derives the context of tile (wr, tn) = (t >> 4, t & 15);
+// tn = 0 writes its tile row's record
+__device__ __forceinline__ void q_epi_fill(const ConvArgs& a, int tx, int ty, int n, int t,
+                                           QEpiRec* recs, uint4* voffs) {
+  const int wr = t >> 4, tn = t & 15;
+  const int bx0 = tx * kQTW, gy0 = ty * kQTH + 4 * wr, gx0 = bx0 + 4 * tn;
+  const int rows = max(0, min(4, a.H - gy0));
+  unsigned vo[4];
 #pragma unroll
   for (int yy = 0; yy < 4; ++yy)
-    e.voff[yy] = (yy < e.rows && e.gx0 < e.W) ? (unsigned)(((e.gy0 + yy) * e.W + e.gx0) * 4)
-                                             : 0x80000000u;
-  e.btab = L->btab;
-  e.statp = L->stat_part;
-  e.statP = L->stat_P;
-  e.sidx = (bty * L->tiles_x + btx) * 2 + wr;
-  return e;
+    vo[yy] = (yy < rows && gx0 < a.W) ? (unsigned)(((gy0 + yy) * a.W + gx0) * 4) : 0x80000000u;
+  voffs[t] = make_uint4(vo[0], vo[1], vo[2], vo[3]);
+  if (tn) return;
+  QEpiRec r;
+  r.W = a.W;
+  r.H = a.H;
+  r.Cout = a.Cout;
+  r.gy0 = gy0;
+  r.bx0 = bx0;
+  r.rows = rows;
+  r.n = n;
+  r.slope = a.relu == RPST_ACT_RELU ? 0.f : (a.relu == RPST_ACT_LRELU ? 0.2f : 1.f);
+  const int cols = max(0, min(kQTW, a.W - bx0));
+  // (v_rcp: exact for the 256-pixel full tiles)
+  r.inv = rows * cols > 0 ? __builtin_amdgcn_rcpf((float)(rows * cols)) : 0.f;
+  const int64_t plane = (int64_t)a.H * a.W;
+  const bool full = rows == 4 && bx0 + kQTW <= a.W;
+  const bool edge = gy0 == 0 || gy0 + 4 >= a.H || bx0 == 0 || bx0 + kQTW >= a.W;
+  const bool pool = a.pool_out != 0;
+  const bool bst = !pool && (a.W & 3) == 0 && (int64_t)a.Cout * plane * 4 < (1LL << 31);
+  const bool keep = a.skip_from <= 0 || n < a.skip_from;
+  r.flags = (full ? kQFFull : 0u) | (edge ? kQFEdge : 0u) | (bst ? kQFBst : 0u) |
+            (pool ? kQFPool : 0u) | (keep ? kQFStore : 0u);
+  r.out = a.out;
+  r.oimg = a.out + (int64_t)n * a.Cout * plane;
+  r.obytes = keep ? (unsigned)(a.Cout * plane * 4) : 0u;
+  r.hw4 = (unsigned)(a.H * a.W) * 4u;
+  const int sidx = (ty * a.tiles_x + tx) * 2 + wr;
+  r.stat = a.stat_part ? a.stat_part + ((int64_t)n * a.stat_P + sidx) * a.Cout : nullptr;
+  recs[wr] = r;
+}
+
+// a wave-uniform value read from LDS, moved to scalar registers (the buffer descriptor built
+// from VGPRs is otherwise re-read lane by lane in a loop around every store)
+__device__ __forceinline__ unsigned uni(unsigned v) {
+  return (unsigned)__builtin_amdgcn_readfirstlane((int)v);
+}
+__device__ __forceinline__ float* uni(float* p) {
+  const uint64_t u = (uint64_t)(uintptr_t)p;
+  return (float*)(uintptr_t)(((uint64_t)uni((unsigned)(u >> 32)) << 32) | uni((unsigned)u));
 }
 
 // bias (interior class for BTAB) already in Y; border classes, activation, statistics
-// partial, store (or 2x2 ceil-mode max pool) of channel co of this lane's tile
+// partial, store (or 2x2 ceil-mode max pool) of channel co of this lane's tile (column tn of
+// tile row r); vo = its output row offsets, cofs = co's byte offset inside the image's output
+// (co hw4, a running value of the caller's). The record's fields are read where they are
+// used: read ahead into one struct, the twenty of them sit in VGPRs beside the tile, and the
+// statistics epilogue has none to spare.
 template <bool STATS, bool BTAB, bool RELU>
-__device__ __forceinline__ void q_finish(const QEpi& e, int co, float (&Y)[16], int tn) {
-  const int gy0 = e.gy0, gx0 = e.gx0, rows = e.rows, n = e.n;
-  const bool cok = co < e.Cout;
+__device__ __forceinline__ void q_finish(const QEpiRec& r, const uint4& vo, const float* btab,
+                                         int co, unsigned cofs, float (&Y)[16], int tn) {
+  const unsigned f = r.flags;
+  const bool full = (f & kQFFull) != 0;
+  const bool cok = co < r.Cout;
   if constexpr (BTAB) {
-    if (e.edge) {
-      const float* bt = e.btab + (cok ? co : 0) * 9;  // this image's table, in LDS
+    if (f & kQFEdge) {
+      const int gy0 = r.gy0, gx0 = r.bx0 + 4 * tn, H = r.H, W = r.W;
+      const float* bt = btab + (cok ? co : 0) * 9;  // this image's table, in LDS
       float b9[9];
 #pragma unroll
       for (int i = 0; i < 9; ++i) b9[i] = cok ? bt[i] : 0.f;
@@ -334,48 +379,58 @@ __device__ __forceinline__ void q_finish(const QEpi& e, int co, float (&Y)[16], 
 #pragma unroll
       for (int yy = 0; yy < 4; ++yy) {
         const int gy = gy0 + yy;
-        const int rc = gy == 0 ? 0 : (gy >= e.H - 1 ? 2 : 1);
+        const int rc = gy == 0 ? 0 : (gy >= H - 1 ? 2 : 1);
         const float l = rc == 0 ? b9[0] : (rc == 2 ? b9[6] : b9[3]);
         const float m = rc == 0 ? b9[1] : (rc == 2 ? b9[7] : b9[4]);
-        const float r = rc == 0 ? b9[2] : (rc == 2 ? b9[8] : b9[5]);
+        const float rr = rc == 0 ? b9[2] : (rc == 2 ? b9[8] : b9[5]);
 #pragma unroll
         for (int xx = 0; xx < 4; ++xx) {
           const int gx = gx0 + xx;
-          Y[yy * 4 + xx] += gx == 0 ? l : (gx >= e.W - 1 ? r : m);
+          Y[yy * 4 + xx] += gx == 0 ? l : (gx >= W - 1 ? rr : m);
         }
       }
     }
   }
+  if constexpr (RELU) {
 #pragma unroll
-  for (int i = 0; i < 16; ++i)
-    Y[i] = __builtin_amdgcn_fmed3f(Y[i], RELU ? 0.f : e.slope * Y[i], __builtin_inff());
+    for (int i = 0; i < 16; ++i) Y[i] = __builtin_amdgcn_fmed3f(Y[i], 0.f, __builtin_inff());
+  } else {
+    const float slope = r.slope;
+#pragma unroll
+    for (int i = 0; i < 16; ++i)
+      Y[i] = __builtin_amdgcn_fmed3f(Y[i], slope * Y[i], __builtin_inff());
+  }
   float sum = 0.f;
   if constexpr (STATS) {
-    if (e.full) {
+    if (full) {
 #pragma unroll
       for (int i = 0; i < 16; ++i) sum += Y[i];
     } else {
+      const int rows = r.rows, gx0 = r.bx0 + 4 * tn, W = r.W;
 #pragma unroll
       for (int yy = 0; yy < 4; ++yy)
 #pragma unroll
-        for (int xx = 0; xx < 4; ++xx) sum += (yy < rows && gx0 + xx < e.W) ? Y[yy * 4 + xx] : 0.f;
+        for (int xx = 0; xx < 4; ++xx) sum += (yy < rows && gx0 + xx < W) ? Y[yy * 4 + xx] : 0.f;
     }
   }
-  if ((RPST_W4Q_DBG & 64) && e.statP > -7) {  // timing only: the stores never taken
-  } else if (e.bst) {
-    const auto ro = rsrc_or_zero(e.oimg, e.obytes, true);
-    const unsigned cofs = cok ? (unsigned)co * (unsigned)(e.H * e.W) * 4u : 0x7fffffffu;
+  if ((RPST_W4Q_DBG & 64) && r.H > -7) {  // timing only: the stores never taken
+  } else if (f & kQFBst) {
+    const auto ro = rsrc_or_zero(uni(r.oimg), uni(r.obytes), true);
+    const unsigned chofs = cok ? cofs : 0x7fffffffu;
+    const unsigned voff[4] = {vo.x, vo.y, vo.z, vo.w};
 #pragma unroll
     for (int yy = 0; yy < 4; ++yy) {
       const floatx4 v = {Y[yy * 4], Y[yy * 4 + 1], Y[yy * 4 + 2], Y[yy * 4 + 3]};
       __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v), ro,
-                                             (int)(e.voff[yy] + cofs), 0, 0);
+                                             (int)(voff[yy] + chofs), 0, 0);
     }
-  } else if (e.pool) {
+  } else if (f & kQFPool) {
     // max_pool2d(2, 2, ceil_mode) of the finished tile, fmaxf in maxpool2_kernel's order
-    if (cok && e.store) {
-      const int Ho = (e.H + 1) >> 1, Wo = (e.W + 1) >> 1;
-      float* o = e.out + (((int64_t)n * e.Cout + co) * Ho + (gy0 >> 1)) * Wo + (gx0 >> 1);
+    if (cok && (f & kQFStore)) {
+      const int gy0 = r.gy0, gx0 = r.bx0 + 4 * tn, rows = r.rows, H = r.H, W = r.W;
+      const int Ho = (H + 1) >> 1, Wo = (W + 1) >> 1;
+      gfloat* o = (gfloat*)r.out + (((int64_t)r.n * r.Cout + co) * Ho + (gy0 >> 1)) * Wo +
+                  (gx0 >> 1);
 #pragma unroll
       for (int py = 0; py < 2; ++py) {
         if (2 * py >= rows) continue;
@@ -383,7 +438,7 @@ __device__ __forceinline__ void q_finish(const QEpi& e, int co, float (&Y)[16], 
         float pv[2];
 #pragma unroll
         for (int px = 0; px < 2; ++px) {
-          const bool x1 = gx0 + 2 * px + 1 < e.W;
+          const bool x1 = gx0 + 2 * px + 1 < W;
           const float* t = Y + (2 * py) * 4 + 2 * px;
           float v = t[0];
           if (x1) v = fmaxf(v, t[1]);
@@ -391,44 +446,47 @@ __device__ __forceinline__ void q_finish(const QEpi& e, int co, float (&Y)[16], 
           if (x1 && y1) v = fmaxf(v, t[5]);
           pv[px] = v;
         }
-        if (gx0 + 3 < e.W && (Wo & 1) == 0) {
-          *reinterpret_cast<float2*>(o + py * Wo) = make_float2(pv[0], pv[1]);
+        if (gx0 + 3 < W && (Wo & 1) == 0) {
+          *(gfloatx2*)(o + py * Wo) = floatx2{pv[0], pv[1]};
         } else {
-          if (gx0 < e.W) o[py * Wo] = pv[0];
-          if (gx0 + 2 < e.W) o[py * Wo + 1] = pv[1];
+          if (gx0 < W) o[py * Wo] = pv[0];
+          if (gx0 + 2 < W) o[py * Wo + 1] = pv[1];
         }
       }
     }
-  } else if (cok && e.store) {
-    float* o = e.out + (((int64_t)n * e.Cout + co) * e.H + gy0) * e.W + gx0;
+  } else if (cok && (f & kQFStore)) {
+    const int gy0 = r.gy0, gx0 = r.bx0 + 4 * tn, rows = r.rows, H = r.H, W = r.W;
+    const bool vec = (W & 3) == 0 && gx0 + 3 < W;
+    gfloat* o = (gfloat*)r.out + (((int64_t)r.n * r.Cout + co) * H + gy0) * W + gx0;
 #pragma unroll
     for (int yy = 0; yy < 4; ++yy) {
       if (yy < rows) {
-        if (e.vec) {
-          *reinterpret_cast<float4*>(o + yy * e.W) =
-              make_float4(Y[yy * 4], Y[yy * 4 + 1], Y[yy * 4 + 2], Y[yy * 4 + 3]);
+        if (vec) {
+          *(gfloatx4*)(o + yy * W) =
+              floatx4{Y[yy * 4], Y[yy * 4 + 1], Y[yy * 4 + 2], Y[yy * 4 + 3]};
         } else {
 #pragma unroll
           for (int xx = 0; xx < 4; ++xx)
-            if (gx0 + xx < e.W) o[yy * e.W + xx] = Y[yy * 4 + xx];
+            if (gx0 + xx < W) o[yy * W + xx] = Y[yy * 4 + xx];
         }
       }
     }
   }
   if constexpr (STATS) {
     sum = row16_sum(sum);
-    const float mean = sum * e.inv;
+    const float mean = sum * r.inv;
     float m2 = 0.f;
-    if (e.full) {
+    if (full) {
 #pragma unroll
       for (int i = 0; i < 16; ++i) m2 = fmaf(Y[i] - mean, Y[i] - mean, m2);
     } else {
+      const int rows = r.rows, gx0 = r.bx0 + 4 * tn, W = r.W;
 #pragma unroll
       for (int yy = 0; yy < 4; ++yy)
 #pragma unroll
         for (int xx = 0; xx < 4; ++xx) {
           const float dv = Y[yy * 4 + xx] - mean;
-          m2 += (yy < rows && gx0 + xx < e.W) ? dv * dv : 0.f;
+          m2 += (yy < rows && gx0 + xx < W) ? dv * dv : 0.f;
         }
     }
     m2 = row16_sum(m2);
@@ -436,8 +494,7 @@ __device__ __forceinline__ void q_finish(const QEpi& e, int co, float (&Y)[16], 
     // partial fill whole cache lines (in [n][co][partial] order they were 8-B pieces
     // scattered over 16 planes). Statistics cost, 128->256 N64 (tools/ab_stats.py): 1.5 ms
     // of 28.4, of which the store 0.2 and the centred-square pass 0.33
-    if (tn == 0 && cok)
-      e.statp[((int64_t)n * e.statP + e.sidx) * e.Cout + co] = make_float2(mean, m2);
+    if (tn == 0 && cok) ((gfloatx2*)r.stat)[co] = floatx2{mean, m2};
   }
 }
 
@@ -465,8 +522,9 @@ __global__ __launch_bounds__(kQNTH, 1) void wino4q_mfma_kernel(ConvArgs a) {
   __shared__ float btl[BTAB ? 9 * kQMaxCo : kQMaxCo];
 
   const int wave = __builtin_amdgcn_readfirstlane((int)threadIdx.x >> 6);
-  const int lane = threadIdx.x & 63;
-  const int k = lane >> 4, tn = lane & 15, wr = wave >> 2;
+  // (lane, tid: not const -- each quarter body below derives its own copies, see there)
+  int lane = threadIdx.x & 63;
+  const int wr = wave >> 2;
 
   // block -> (co-split group, row tile, column tile, image)
   int bid = (int)blockIdx.x;
@@ -483,6 +541,10 @@ __global__ __launch_bounds__(kQNTH, 1) void wino4q_mfma_kernel(ConvArgs a) {
     const float* src = BTAB ? a.btab + (int64_t)n * nb : a.bias;
     for (int i = threadIdx.x; i < nb; i += kQNTH) btl[i] = src ? src[i] : 0.f;
   }
+  // the epilogue's context (QEpiRec, q_epi_fill), published by the prologue's barrier
+  __shared__ __attribute__((aligned(16))) QEpiRec erec[2];
+  __shared__ uint4 evoff[2 * 16];
+  if (threadIdx.x < 32) q_epi_fill(a, tx, ty, n, (int)threadIdx.x, erec, evoff);
   constexpr bool up = INOP == RPST_IN_UPSAMPLE2;
   const unsigned in_plane = up ? (unsigned)(a.Hs * a.Ws) : (unsigned)(a.H * a.W);
   const unsigned oob = a.Cin * in_plane * 4u;  // a padding position's (out-of-range) offset
@@ -513,7 +575,7 @@ __global__ __launch_bounds__(kQNTH, 1) void wino4q_mfma_kernel(ConvArgs a) {
   const bool fixL = wide && w4a && !zp && x0 == 0;
   const bool fixR = wide && w4a && !zp && x0 + kQTW == a.W;
   unsigned poff[kQSlow];
-  const int tid = threadIdx.x;
+  int tid = threadIdx.x;
   if (wide) {
 #pragma unroll
     for (int i = 0; i < kQWide; ++i) {
@@ -620,8 +682,7 @@ __global__ __launch_bounds__(kQNTH, 1) void wino4q_mfma_kernel(ConvArgs a) {
   // take channel l / 10, row l % 10 of the stage
   auto fix_halo = [&](float* stg) {
     if ((wave == 0 && fixL) || (wave == 1 && fixR)) {
-      int l = lane;
-      asm volatile("" : "+v"(l));
+      const int l = q_lane_here();
       if (l < 40) {
         const int ch = l / 10, row = l - 10 * ch;
         float* rp = stg + ch * kQCS + row * kQPS;
@@ -654,6 +715,11 @@ __global__ __launch_bounds__(kQNTH, 1) void wino4q_mfma_kernel(ConvArgs a) {
 
   auto body = [&](auto Qc) {
     constexpr int Q = decltype(Qc)::value, QR = Q >> 1, QC = Q & 1;
+    // (the lane's coordinates per quarter body, the DMA issue's included: shared, they stay
+    // live across the other quarters' bodies and spill)
+    lane = q_lane_here();
+    tid = wave * 64 + lane;
+    const int k = lane >> 4, tn = lane & 15;
     floatx4 acc[9][4];
 #pragma unroll
     for (int p = 0; p < 9; ++p)
@@ -794,7 +860,10 @@ __global__ __launch_bounds__(kQNTH, 1) void wino4q_mfma_kernel(ConvArgs a) {
                    "+v"(acc[6][2]), "+v"(acc[6][3]), "+v"(acc[7][0]), "+v"(acc[7][1]),
                    "+v"(acc[7][2]), "+v"(acc[7][3]), "+v"(acc[8][0]), "+v"(acc[8][1]),
                    "+v"(acc[8][2]), "+v"(acc[8][3]));
-      const int co0 = ctile * kQCo + 16 * Q + 4 * k;
+      const int el = q_lane_here(), ek = el >> 4, etn = el & 15;
+      const int co0 = ctile * kQCo + 16 * Q + 4 * ek;
+      unsigned cofs = (unsigned)co0 * erec[wr].hw4;  // + one plane per finished channel
+      asm volatile("" : "+v"(cofs));  // (opaque: else each channel's offset is a multiply again)
       // 6 passes (accumulator element pair rp, position row pt): each wave writes its 3
       // positions of row pt of the other quarters' blocks (elements 2 rp, 2 rp + 1) into ws1
       // and, after a barrier, reads the other quarters' positions of its own block. After pass pt it holds transformed rows
@@ -812,7 +881,7 @@ __global__ __launch_bounds__(kQNTH, 1) void wino4q_mfma_kernel(ConvArgs a) {
             const int slot = (Q - dq - 1) & 3;
 #pragma unroll
             for (int j = 0; j < 3; ++j)
-              *reinterpret_cast<float2*>(xb + (((dq * 3 + slot) * 3 + j) * 64 + lane) * 2) =
+              *reinterpret_cast<float2*>(xb + (((dq * 3 + slot) * 3 + j) * 64 + el) * 2) =
                   make_float2(acc[3 * pt + j][dq][2 * rp], acc[3 * pt + j][dq][2 * rp + 1]);
           }
           if (!(DBG & 4)) q_lds_barrier();
@@ -827,7 +896,7 @@ __global__ __launch_bounds__(kQNTH, 1) void wino4q_mfma_kernel(ConvArgs a) {
                 v = make_float2(acc[3 * pt + j][src][2 * rp], acc[3 * pt + j][src][2 * rp + 1]);
               } else {
                 v = *reinterpret_cast<const float2*>(
-                    xb + (((Q * 3 + ((s - Q - 1) & 3)) * 3 + j) * 64 + lane) * 2);
+                    xb + (((Q * 3 + ((s - Q - 1) & 3)) * 3 + j) * 64 + el) * 2);
               }
               m[0][s >> 1][3 * (s & 1) + j] = v.x;
               m[1][s >> 1][3 * (s & 1) + j] = v.y;
@@ -843,14 +912,10 @@ __global__ __launch_bounds__(kQNTH, 1) void wino4q_mfma_kernel(ConvArgs a) {
 #pragma unroll
         for (int e2 = 0; e2 < 2; ++e2) {
           const int r = 2 * rp + e2;
-          // the epilogue context is re-derived per channel from the kernel arguments: kept
-          // across the exchange passes it overflows the scalar registers
-          QEpi e = q_epi_ctx(wr, tn);
-          e.btab = btl;
           float bias = 0.f;
           {
             const int co = co0 + r;
-            if (co < e.Cout) bias = BTAB ? btl[co * 9 + 4] : btl[co];
+            if (co < erec[wr].Cout) bias = BTAB ? btl[co * 9 + 4] : btl[co];
           }
 #pragma unroll
           for (int x = 0; x < 4; ++x) P[e2][1][x] += bias;
@@ -864,7 +929,8 @@ __global__ __launch_bounds__(kQNTH, 1) void wino4q_mfma_kernel(ConvArgs a) {
 #pragma unroll
             for (int yy = 0; yy < 4; ++yy) Y[yy * 4 + x] = y[yy];
           }
-          q_finish<STATS, BTAB, RELU>(e, co0 + r, Y, tn);
+          q_finish<STATS, BTAB, RELU>(erec[wr], evoff[wr * 16 + etn], btl, co0 + r, cofs, Y, etn);
+          cofs += erec[wr].hw4;
         }
       }
 #pragma unroll
