@@ -48,8 +48,8 @@ def golden_config(g, i):
                   bool(g[f"net{i}_use_mask"]))
 
 
-def _d(a):
-    return torch.as_tensor(np.asarray(a) if not torch.is_tensor(a) else a).double()
+def _d(a, dtype=torch.float64):
+    return torch.as_tensor(np.asarray(a) if not torch.is_tensor(a) else a).to(dtype)
 
 
 def conv_pad(x, w, b, pad_mode="reflect"):
@@ -60,10 +60,10 @@ def conv_pad(x, w, b, pad_mode="reflect"):
     return F.conv2d(x, w, b)
 
 
-def rp64(sd):
-    """The rp_enc* / rp_dec* entries of a state_dict as float64 tensors (the frozen VGG is not
-    part of inference)."""
-    return {k: _d(v) for k, v in sd.items() if k.startswith("rp_")}
+def rp64(sd, dtype=torch.float64):
+    """The rp_enc* / rp_dec* entries of a state_dict as float64 tensors (or of `dtype`; the
+    frozen VGG is not part of inference)."""
+    return {k: _d(v, dtype) for k, v in sd.items() if k.startswith("rp_")}
 
 
 def block(x, sd, prefix, pad_mode="reflect"):

@@ -151,3 +151,299 @@ def blocks_mask(h, w, labels, seed, dot=None):
         lab, y, x, hh, ww = dot
         m[y:y + hh, x:x + ww] = lab
     return m
+
+
+def bands_mask(h, w, rows, labels):
+    """Horizontal bands (h, w): heights cycle through `rows`, labels through `labels`, the last
+    band cut at the map's edge."""
+    m = np.empty((h, w), dtype=np.uint8)
+    y = k = 0
+    while y < h:
+        m[y:y + rows[k % len(rows)]] = labels[k % len(labels)]
+        y += rows[k % len(rows)]
+        k += 1
+    return m
+
+
+def speckle_mask(h, w, labels, seed):
+    """Independent draws per pixel from `labels`; a 4-pixel word (of the flattened map) that
+    came out uniform has its second pixel moved to the next label, so every word is mixed."""
+    k = np.random.default_rng(seed).integers(0, len(labels), size=h * w)
+    n4 = (h * w) // 4
+    words = k[:4 * n4].reshape(n4, 4)
+    flat = (words == words[:, :1]).all(axis=1)
+    words[flat, 1] = (words[flat, 1] + 1) % len(labels)
+    return np.asarray(labels, dtype=np.uint8)[k].reshape(h, w)
+
+
+MIXED_STAMP = 77  # the label mixed_mask stamps on exactly 10 pixels
+
+
+def mixed_mask(h, w, rows, seed, column=66):
+    """Bands of heights `rows` over the labels 0, 90, 255, 180; right of `column` (no multiple
+    of 4, so words straddle it) the label is 30 more (255 becomes 140); the third band is
+    speckle of 0 / 90 / 255; a 2 x 5 rectangle holds MIXED_STAMP: 10 pixels, not valid."""
+    assert column % 4 and w > column + 8 and len(rows) >= 3 and h > sum(rows[:3])
+    m = bands_mask(h, w, rows, [0, 90, 255, 180])
+    right = m[:, column:]
+    m[:, column:] = np.where(right == 255, 140, right + 30)
+    y0 = rows[0] + rows[1]
+    m[y0:y0 + rows[2]] = speckle_mask(rows[2], w, [0, 90, 255], seed)
+    m[3:5, 7:12] = MIXED_STAMP
+    return m
+
+
+# ---- which paths of the statistics kernel a label map reaches -----------------------------
+# The constants of rp-style-transfer_amd/csrc/rpst_masked.hip, restated: keep them equal.
+SEG_THREADS = 256     # kSegThreads: lanes that walk a slice together
+SEG_WAVE = 64         # kWave
+MAX_SPLITS = 16       # kMaxSplits
+APPLY_ELEMS = 16384   # kApplyElems: elements per apply workgroup
+PLAN_THREADS = 1024   # kPlanThreads: lanes of the histogram
+
+
+def masked_splits(C):
+    """masked_splits of rpst_masked.hip: workgroups per plane."""
+    return min(max(-(-512 // C), 1), MAX_SPLITS)
+
+
+def plane_slices(HW, C):
+    """-> (unit, [(lo, hi)] per split): the slices plane_label_sums walks, in units of `unit`
+    elements: 4 (one float4 / one 32-bit label word) when HW % 4 == 0, else 1."""
+    unit = 4 if HW % 4 == 0 else 1
+    n, splits = HW // unit, masked_splits(C)
+    per = -(-n // splits)
+    return unit, [(min(s * per, n), min(s * per + per, n)) for s in range(splits)]
+
+
+def run_path_census(seg, C, detail=False):
+    """Counts of the wave-steps of plane_label_sums (rpst_masked.hip) over one label map
+    (h, w) with C channels, by kind. A pure-numpy mirror of the kernel's slicing, whose
+    constants it restates (SEG_THREADS, SEG_WAVE, MAX_SPLITS, masked_splits: a change there
+    has to be made here): splits = masked_splits(C), slice s = units [s per, s per + per) with
+    per = ceil(n / splits), walked in steps of 256 lanes, a unit being one 4-pixel word when
+    HW % 4 == 0 and one pixel otherwise; a wave of 64 lanes takes the register path in a step
+    when each of its active lanes reads a word that holds its current label four times (never
+    in a slice's first step, the lanes having no label yet; never in pixel units).
+      register          wave-steps on the register path (with an active lane)
+      element_later     wave-steps on the element path after a slice's first step
+      reg_to_elem       element wave-steps that follow a register one: the run a lane carried
+                        in registers across steps is handed over at a label change
+      elem_to_reg       register wave-steps that follow an element one
+      mixed_words       words (active, HW % 4 == 0) that hold more than one label
+      partial_waves     wave-steps with some but not all 64 lanes active
+      max_steps         the largest number of steps of a slice
+      apply_chunks      workgroups per plane of masked_apply_kernel
+      histogram_steps   iterations of the plan's histogram loop
+    With detail, also 'transitions': (split, step, wave) of every reg_to_elem wave-step."""
+    flat = np.asarray(seg, dtype=np.uint8).reshape(-1)
+    HW = flat.size
+    unit, slices = plane_slices(HW, C)
+    words = flat.reshape(-1, unit).astype(np.int64)
+    out = dict(register=0, element_later=0, reg_to_elem=0, elem_to_reg=0, mixed_words=0,
+               partial_waves=0, max_steps=0)
+    transitions = []
+    waves = SEG_THREADS // SEG_WAVE
+    for split, (lo, hi) in enumerate(slices):
+        label = np.full(SEG_THREADS, -1, dtype=np.int64)
+        was_register = [None] * waves
+        steps = -(-(hi - lo) // SEG_THREADS)
+        out["max_steps"] = max(out["max_steps"], steps)
+        for step in range(steps):
+            i = lo + step * SEG_THREADS + np.arange(SEG_THREADS)
+            active = i < hi
+            w = words[np.minimum(i, hi - 1)]
+            same = ~active | ((label >= 0) & (w == label[:, None]).all(axis=1))
+            if unit == 1:
+                same = ~active
+            out["mixed_words"] += int((active & (w != w[:, :1]).any(axis=1)).sum())
+            for k in range(waves):
+                ln = slice(k * SEG_WAVE, (k + 1) * SEG_WAVE)
+                n_act = int(active[ln].sum())
+                if n_act == 0:
+                    continue
+                out["partial_waves"] += n_act < SEG_WAVE
+                register = bool(same[ln].all())
+                if register:
+                    out["register"] += 1
+                    out["elem_to_reg"] += was_register[k] is False
+                else:
+                    out["element_later"] += step > 0
+                    if was_register[k]:
+                        out["reg_to_elem"] += 1
+                        transitions.append((split, step, k))
+                    upd = np.arange(SEG_THREADS)[ln][active[ln]]
+                    label[upd] = w[upd, -1]
+                was_register[k] = register
+    out = {k: int(v) for k, v in out.items()}
+    out["apply_chunks"] = -(-HW // APPLY_ELEMS)
+    out["histogram_steps"] = -(-(HW // unit) // PLAN_THREADS)
+    if detail:
+        out["transitions"] = transitions
+    return out
+
+
+def carried_run_elements(seg, C, split, step, wave):
+    """The pixels (flat indices) of the run that the first lane of `wave` to change its label
+    in `step` of slice `split` carried there in registers: the lane's pixels of the earlier
+    steps back to its last change, and those of this step's word in front of the change."""
+    flat = np.asarray(seg, dtype=np.uint8).reshape(-1)
+    unit, slices = plane_slices(flat.size, C)
+    lo, hi = slices[split]
+    for lane in range(wave * SEG_WAVE, (wave + 1) * SEG_WAVE):
+        units = lo + np.arange(step + 1) * SEG_THREADS + lane
+        if units[-1] >= hi:
+            continue
+        px = (units[:, None] * unit + np.arange(unit)).reshape(-1)
+        labs = flat[px]
+        before = labs[unit * step - 1]
+        if (labs[unit * step:] == before).all():
+            continue
+        a = unit * step
+        while a > 0 and labs[a - 1] == before:
+            a -= 1
+        b = unit * step
+        while labs[b] == before:
+            b += 1
+        return px[a:b]
+    raise AssertionError("no lane of that wave changes its label in that step")
+
+
+def kernel_form_params(content, style, c_seg, s_seg, c_drop=None):
+    """masked_params as the kernels form it, in float64: per label the sums of d = x - x[0]
+    and of d d over the plane, mean = x[0] + t1 / n, var = (t2 - t1 t1 / n) / (n - 1), n the
+    label's pixel count. c_drop: flat indices of content pixels left out of the sums (n stays
+    the count), for planting a walk that misses them."""
+    content = np.asarray(content, dtype=np.float64)
+    style = np.asarray(style, dtype=np.float64)
+    C = content.shape[0]
+    counts = label_counts(c_seg, s_seg)
+    rows = np.tile(np.array([0.0, -1.0, 1.0, 0.0]), (C, 256, 1))
+
+    def stats(x, seg, lab, drop):
+        d = x.reshape(C, -1) - x.reshape(C, -1)[:, :1]
+        m = np.asarray(seg).reshape(-1) == lab
+        n = int(m.sum())
+        if drop is not None:
+            m = m.copy()
+            m[drop] = False
+        t1, t2 = d[:, m].sum(axis=1), (d[:, m] ** 2).sum(axis=1)
+        var = (t2 - t1 * t1 / n) / (n - 1)
+        return x.reshape(C, -1)[:, 0] + t1 / n, np.sqrt(np.maximum(var, 0.0) + EPS)
+
+    for lab in np.nonzero(counts[:, 2])[0]:
+        mc, sc = stats(content, c_seg, lab, c_drop)
+        ms, ss = stats(style, s_seg, lab, None)
+        rows[:, lab] = np.stack([mc, sc, ss, ms], axis=1)
+    return rows, counts
+
+
+def apply_rows(content, c_seg, rows):
+    """The apply step alone, float64: content (C, h, w) through the parameter rows
+    (C, 256, 4); a row with std_c < 0 is pass-through."""
+    content = np.asarray(content, dtype=np.float64)
+    C = content.shape[0]
+    lab = np.asarray(c_seg).reshape(-1)
+    r = rows[:, lab]  # (C, HW, 4)
+    x = content.reshape(C, -1)
+    out = np.where(r[..., 1] < 0, x, (x - r[..., 0]) / r[..., 1] * r[..., 2] + r[..., 3])
+    return out.reshape(content.shape)
+
+
+def row_errors(got, rows, counts):
+    """Per valid (channel, label) row of (C, 256, 4) parameters: |mean - ref| over
+    (|ref mean| + ref std) and |std - ref| over ref std, the worst of the content pair and the
+    style pair -> (worst mean figure, worst std figure)."""
+    v = counts[:, 2].astype(bool)
+    got, rows = np.asarray(got, dtype=np.float64)[:, v], rows[:, v]
+    em = max(float((np.abs(got[..., m] - rows[..., m]) /
+                    (np.abs(rows[..., m]) + rows[..., s])).max()) for m, s in ((0, 1), (3, 2)))
+    es = max(float((np.abs(got[..., s] - rows[..., s]) / rows[..., s]).max()) for s in (1, 2))
+    return em, es
+
+
+# ---- the inputs of the loop-stride tests (test_gpu_masked.py, test_masked_cpu.py) ----------
+def labelled_feature(seed, shape, segs):
+    """helpers.gen(seed, shape) scaled and shifted per label and per channel, so that the
+    labels' statistics differ by more than their spread: value = u (0.4 + 0.2 (l % 4)) +
+    ((37 l) % 13 - 6) + 0.25 (c % 5), u uniform in [-1, 1), l the pixel's label in segs
+    (N, h, w). Every plane's first element, which the kernels subtract from the others before
+    they sum, lies 20.5 above that: no pixel's shifted value is small (at least 7.5), so a
+    pixel left out of a sum moves its label's variance whatever its label. fp32 torch
+    (N, C, h, w)."""
+    from helpers import gen
+    lab = torch.from_numpy(np.asarray(segs).astype(np.int64))[:, None]
+    c = torch.arange(shape[1]).view(1, -1, 1, 1)
+    x = gen(seed, shape) * (0.4 + 0.2 * (lab % 4)) + ((37 * lab) % 13 - 6) + 0.25 * (c % 5)
+    x[:, :, 0, 0] += 20.5
+    return x.float()
+
+
+# case -> (content shape, style (h, w), maps); the maps are (content, style) per image
+STRIDE_SHAPES = {
+    "a-bands": ((1, 2, 256, 160), (256, 160)),
+    "a-speckle": ((1, 2, 256, 160), (256, 160)),
+    "a-mixed": ((1, 2, 256, 160), (256, 160)),
+    "b": ((1, 512, 48, 64), (48, 64)),
+    "c": ((2, 8, 136, 128), (136, 128)),
+    "d": ((1, 64, 96, 128), (80, 100)),
+    "e": ((1, 8, 131, 133), (131, 133)),
+}
+_STRIDE_CASES = {}
+
+
+def stride_maps(name):
+    """-> (c_segs (N, h, w), s_segs (N, hs, ws)) of a STRIDE_SHAPES case."""
+    (n, _, h, w), (hs, ws) = STRIDE_SHAPES[name]
+    if name == "a-bands":
+        maps = [(bands_mask(h, w, [37, 50, 21], [0, 60, 255, 120]),
+                 bands_mask(hs, ws, [29, 44], [120, 255, 0, 60]))]
+    elif name == "a-speckle":
+        maps = [(speckle_mask(h, w, [0, 60, 255], 5), speckle_mask(hs, ws, [255, 60, 0, 9], 6))]
+    elif name == "a-mixed":
+        maps = [(mixed_mask(h, w, [37, 50, 21, 40], 7), mixed_mask(hs, ws, [50, 31, 44, 21], 8))]
+    elif name == "b":
+        maps = [(bands_mask(h, w, [24], [3, 200]), bands_mask(hs, ws, [10, 14], [200, 3]))]
+    elif name == "c":
+        maps = [(bands_mask(h, w, [30, 17, 41], [0, 60, 255]),
+                 bands_mask(hs, ws, [25, 40], [255, 0, 60])),
+                (bands_mask(h, w, [19, 52], [7, 60, 130, 255]),
+                 bands_mask(hs, ws, [33, 20, 11], [130, 7, 255, 60]))]
+    elif name == "d":
+        maps = [(bands_mask(h, w, [21, 30, 13], [0, 60, 255]),
+                 bands_mask(hs, ws, [17, 26], [60, 255, 0]))]
+    elif name == "e":
+        maps = [(bands_mask(h, w, [23, 40, 9], [0, 60, 255]),
+                 bands_mask(hs, ws, [31, 18], [255, 0, 60]))]
+    else:
+        raise KeyError(name)
+    assert len(maps) == n
+    return np.stack([m[0] for m in maps]), np.stack([m[1] for m in maps])
+
+
+def stride_case(name):
+    """The inputs and the float64 reference of a STRIDE_SHAPES case, formed once and shared
+    (read only): content, style, skip (fp32 torch), c_segs, s_segs (uint8 numpy), rows
+    (N, C, 256, 4), counts (N, 256, 3), out (N, C, h, w) float64, census of image 0's content
+    and style maps."""
+    import types
+    if name in _STRIDE_CASES:
+        return _STRIDE_CASES[name]
+    from helpers import gen
+    shape, ssize = STRIDE_SHAPES[name]
+    c_segs, s_segs = stride_maps(name)
+    seed = 100 + 10 * sorted(STRIDE_SHAPES).index(name)
+    content = labelled_feature(seed, shape, c_segs)
+    style = labelled_feature(seed + 1, (*shape[:2], *ssize), s_segs) * 0.7 + 0.5
+    skip = gen(seed + 2, shape)
+    per = [masked_params(content[n].numpy(), style[n].numpy(), c_segs[n], s_segs[n])
+           for n in range(shape[0])]
+    rows, counts = np.stack([p[0] for p in per]), np.stack([p[1] for p in per])
+    out = np.stack([apply_rows(content[n].numpy(), c_segs[n], rows[n])
+                    for n in range(shape[0])])
+    case = types.SimpleNamespace(
+        name=name, content=content, style=style, skip=skip, c_segs=c_segs, s_segs=s_segs,
+        rows=rows, counts=counts, out=out, census=run_path_census(c_segs[0], shape[1]),
+        style_census=run_path_census(s_segs[0], shape[1]))
+    _STRIDE_CASES[name] = case
+    return case

@@ -43,8 +43,15 @@ def test_adain_golden(cuda, golden):
         assert rel_l2(out, ref) < TOL_STATS, i
 
 
+# Past one apply chunk on the scalar path, and planes whose statistics end the 4-deep unrolled
+# loop with a ragged remainder: (65, 67) is odd (HW = 4355: two scalar apply chunks of 4096);
+# (68, 64) has HW / 4 = 1088 (one unrolled pass of 1024, then a remainder only lanes 0-63
+# take); (75, 64) has HW / 4 = 1200 (remainder on lanes 0-175).
+RAGGED_SHAPES = [(2, 3, 65, 67), (2, 3, 68, 64), (1, 2, 75, 64)]
+
+
 @pytest.mark.parametrize("shape", [(1, 1, 1, 2), (2, 3, 5, 7), (4, 64, 33, 17), (2, 256, 64, 64),
-                                   (1, 8, 512, 512)])
+                                   (1, 8, 512, 512)] + RAGGED_SHAPES)
 def test_adain_vs_oracle(cuda, shape):
     import network as net
     c = gen(1, shape, 3.0, 1.0)
@@ -62,6 +69,31 @@ def test_adain_large_offset_variance(cuda):
     ref_s = (xd.var(dim=2) + 1e-5).sqrt()
     assert rel_l2(s.reshape(2, 4), ref_s) < 1e-6
     assert rel_l2(m.reshape(2, 4), xd.mean(dim=2)) < 1e-7
+
+
+@pytest.mark.parametrize("shape", RAGGED_SHAPES)
+def test_stats_ragged_planes_vs_float64(cuda, shape):
+    """mean_variance_norm against float64 at TOL_STATS, and calc_mean_std at
+    test_adain_large_offset_variance's bars on inputs with offset 1000, on the planes of
+    RAGGED_SHAPES; every apply chunk of 4096 elements is held by itself as well."""
+    from rpst import ops
+    n, c = shape[:2]
+    x = gen(5, shape, 3.0, 1.0)
+    xd = x.double().reshape(n, c, -1)
+    ref = (xd - xd.mean(dim=2, keepdim=True)) / (xd.var(dim=2, keepdim=True) + 1e-5).sqrt()
+    got = ops.mean_variance_norm(x.to(cuda)).cpu().double().reshape(n, c, -1)
+    err = rel_l2(got, ref)
+    per = [rel_l2(got[..., o:o + 4096], ref[..., o:o + 4096]) for o in range(0, xd.shape[2], 4096)]
+    print(f"mean_variance_norm {shape}: rel-L2 {err:.3e}, per chunk "
+          + " ".join(f"{e:.3e}" for e in per))
+    assert err < TOL_STATS and len(per) == 2 and max(per) < TOL_STATS
+    x = gen(6, shape, 1.0, 1000.0)
+    m, s = ops.calc_mean_std(x.to(cuda))
+    xd = x.double().reshape(n, c, -1)
+    es = rel_l2(s.reshape(n, c), (xd.var(dim=2) + 1e-5).sqrt())
+    em = rel_l2(m.reshape(n, c), xd.mean(dim=2))
+    print(f"calc_mean_std {shape} offset 1000: mean {em:.3e} std {es:.3e}")
+    assert es < 1e-6 and em < 1e-7
 
 
 def test_mean_variance_norm(cuda, golden):

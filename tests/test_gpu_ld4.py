@@ -17,7 +17,8 @@ import torch.nn.functional as F
 import ld4_ref as L4
 import ld_ref as L
 from helpers import (TOL_NET, TOL_NET_MAXABS, TOL_STATS, check_pipeline, dataset_tree, dev, gen,
-                     golden_net, mask_kw, max_abs_ratio, rel_l2, traced_launches, unfused)
+                     golden_net, mask_kw, max_abs_ratio, rel_l2, synth_, traced_launches,
+                     unfused)
 
 pytestmark = pytest.mark.gpu
 
@@ -36,6 +37,13 @@ RESIZE_CASES = [
     ((1, 4, 4, 6), (32, 48)),
     ((1, 4, 6, 10), (6, 10)),
     ((1, 2, 3, 130), (5, 259)),
+    # past one chunk of 4096 destination elements (write_plane_chunk's chunk > 0) and one
+    # stride of 256 source quads (resized_stats_kernel):
+    ((2, 5, 33, 34), (65, 67)),    # 4355 = 2 chunks, odd: the planes' heads cycle 0-3; the
+                                   # source's 1122 = 2 strides and a 2-element tail
+    ((1, 3, 23, 29), (65, 67)),    # non-integer ratios on both axes
+    ((1, 2, 40, 52), (91, 93)),    # 8463 = 3 chunks; the source's 2080 = 3 strides
+    ((1, 4, 64, 64), (128, 128)),  # 4 full chunks, aligned, exactly 2 x
 ]
 RESIZE_IDS = [f"{s[0]}->{s[1]}" for s in RESIZE_CASES]
 
@@ -100,29 +108,20 @@ def test_resized_mean_std_survives_a_large_mean(cuda):
 
 
 def _fuse_case(cuda, ca, hd, size, csize, n=2):
-    """ld4_fuse's operands with the content half inside a [content; style] batch of 2n."""
+    """ld4_fuse on ld4_ref.fuse_inputs -> (y, the kernel's output, the float64 reference)."""
     from rpst import ops
-    fine = gen(51, (2 * n, hd, *size), 1.5, 0.3)
-    coarse = gen(52, (2 * n, hd, *csize), 2.0, -0.2)
-    y = gen(53, (n, ca, *size), 1.0, 0.1) if ca else None
-    stats = [gen(54 + k, (4, n, hd), 0.5, 1.25) for k in range(2)]  # distinct per image, std > 0
+    y, fine, coarse, stats = L4.fuse_inputs(ca, hd, size, csize, n)
     params = [ops.adain_params(*(t.to(cuda) for t in (s[0], s[1], s[2], s[3]))) for s in stats]
     got = ops.ld4_fuse(None if y is None else y.to(cuda), fine.to(cuda), coarse.to(cuda),
                        params[0], params[1], n=n)
-
-    def affine(v, s):  # adain_params(mean_c, std_c, mean_s, std_s)
-        mc, sc, ms, ss = (s[k].double().view(n, hd, 1, 1) for k in range(4))
-        return (v.double() - mc) / sc * ss + ms
-
-    want = torch.cat([affine(fine[:n], stats[0]),
-                      affine(F.interpolate(coarse[:n], size), stats[1])], dim=1)
-    return y, got, want
+    return y, got, L4.fuse_want(fine, coarse, stats, size, n)
 
 
 @pytest.mark.parametrize("ca", [0, 4, 3])
 @pytest.mark.parametrize("hd", [4, 5])
 @pytest.mark.parametrize("size,csize", [((17, 33), (9, 17)), ((24, 40), (12, 20)),
-                                        ((32, 48), (1, 2))])
+                                        ((32, 48), (1, 2)), ((65, 67), (33, 34)),
+                                        ((91, 93), (23, 29)), ((128, 128), (64, 64))])
 def test_ld4_fuse_vs_float64(cuda, ca, hd, size, csize):
     y, got, want = _fuse_case(cuda, ca, hd, size, csize)
     assert tuple(got.shape) == (2, ca + 2 * hd, *size) and got.dtype == torch.float32
@@ -132,6 +131,17 @@ def test_ld4_fuse_vs_float64(cuda, ca, hd, size, csize):
     assert err < TOL_STATS, (ca, hd, size, csize, err)
     for k in range(2):  # per image too: image 1 does not ride on image 0's statistics
         assert rel_l2(got[k, ca:], want[k]) < TOL_STATS
+    # and per destination chunk of 4096 elements of each plane: one wrong chunk of one plane
+    # is not diluted by the rest
+    hw = size[0] * size[1]
+    g, w = got[:, ca:].cpu().double().reshape(-1, hw), want.reshape(-1, hw)
+    worst = max(float((g[:, o:o + L4.CHUNK] - w[:, o:o + L4.CHUNK]).norm(dim=1)
+                      .div(w[:, o:o + L4.CHUNK].norm(dim=1)).max())
+                for o in range(0, hw, L4.CHUNK))
+    if hw > L4.CHUNK:
+        print(f"ld4_fuse {ca}+2x{hd} {csize}->{size}: rel-L2 {err:.3e}, worst chunk of a plane "
+              f"{worst:.3e}")
+    assert worst < TOL_STATS, (ca, hd, size, csize, worst)
 
 
 def test_ld4_fuse_argument_checks(cuda):
@@ -201,6 +211,27 @@ def test_ld4_encoder_levels_match_reference(cuda, golden, i):
         err, bar = rel_l2(lv, ref), max(1e-5, 3 * floor)
         print(f"ld4 case {i} level {k}: rel-L2 {err:.3e} bar max(1e-5, 3 x {floor:.2e})")
         assert err < bar, (i, k, err, bar)
+
+
+def test_ld4_test_at_72x88_vs_float64(cuda):
+    """test() at a size whose planes need two chunks (72 x 88 = 6336 elements; the coarse
+    sources 36 x 44 = 1584 and 18 x 22 = 396 elements: two strides of the statistics loop and
+    one), against the float64 restatement on the same weights: TOL_NET / TOL_NET_MAXABS, and
+    held as the levels are, to max(1e-5, 3 x the fp32 restatement's own distance to float64)."""
+    import network as net
+    m = net.LDMSAdaINRPNet4(L4.config(4, 3, 0, 3), copy.deepcopy(net.vgg))
+    synth_(m, 96)
+    sd = m.state_dict()
+    c, s = gen(61, (1, 3, 72, 88), 0.5, 0.5), gen(62, (1, 3, 72, 88), 0.5, 0.5)
+    ref = L4.test(c, s, sd, 3)
+    floor = rel_l2(L4.test(c, s, sd, 3, dtype=torch.float32), ref)
+    assert ref.dtype == torch.float64 and floor < 3e-6
+    m = m.to(cuda)
+    y = m.test(c.to(cuda), s.to(cuda))
+    err, mx, bar = rel_l2(y, ref), max_abs_ratio(y, ref), max(1e-5, 3 * floor)
+    print(f"ld4 72x88: rel-L2 {err:.3e} max-abs ratio {mx:.3e} bar max(1e-5, 3 x {floor:.2e})")
+    assert err < TOL_NET and mx < TOL_NET_MAXABS
+    assert err < bar, (err, bar)
 
 
 def test_ld4_batch_of_two_equals_single_images(cuda, golden):

@@ -10,7 +10,8 @@ import torch
 
 import masked_ref as M
 from helpers import (SOURCE_CONFIG, TOL_STATS, check_net, check_pipeline, dataset_tree, dev,
-                     golden_net, mask_kw, multiscale_config, rel_l2, synth_, unfused)
+                     golden_net, mask_kw, multiscale_config, rel_l2, state_dict_of, synth_,
+                     unfused)
 
 pytestmark = pytest.mark.gpu
 
@@ -260,3 +261,134 @@ def test_pipeline_with_masks_matches_direct_test(cuda, tmp_path):
     m.config["use_mask"] = False
     for c, s, ref in items:
         assert not np.array_equal(to_uint8(m.test(c, s))[0].cpu().numpy(), ref)
+
+
+# ---- past one loop stride and one apply chunk ---------------------------------------------
+# The shapes above keep every per-plane loop of rpst_masked.hip at one iteration. These are the
+# smallest at which they repeat (masked_ref.STRIDE_SHAPES); masked_ref.run_path_census, a
+# mirror of the statistics kernel's slicing, says which of its paths each label map reaches,
+# and the conditions asserted on it are conditions on the inputs.
+STRIDE_CASES = list(M.STRIDE_SHAPES)
+
+
+def test_stride_cases_reach_every_path():
+    cen = {name: M.stride_case(name).census for name in STRIDE_CASES}
+    for name, c in cen.items():
+        print(f"census {name}: {c}  style: {M.stride_case(name).style_census}")
+    for kind in ("register", "element_later", "reg_to_elem", "elem_to_reg", "mixed_words",
+                 "partial_waves"):
+        assert any(cen[n][kind] > 0 for n in STRIDE_CASES if n != "e"), kind
+    a = cen["a-bands"]
+    assert a["register"] >= 10 and a["reg_to_elem"] >= 1 and a["elem_to_reg"] >= 1
+    assert a["max_steps"] == 3 and a["apply_chunks"] == 3 and a["histogram_steps"] == 10
+    assert cen["a-speckle"]["register"] == 0
+    assert cen["a-speckle"]["mixed_words"] == 256 * 160 // 4  # every word
+    assert cen["a-mixed"]["mixed_words"] > 0
+    mixed = M.stride_case("a-mixed")
+    assert tuple(mixed.counts[0, M.MIXED_STAMP]) == (10, 10, 0)
+    assert mixed.counts[0, 0, 2] == 1 and mixed.counts[0, 255, 2] == 1
+    assert cen["b"]["max_steps"] == 3 and cen["b"]["partial_waves"] == 0
+    assert cen["b"]["reg_to_elem"] >= 1
+    assert cen["c"]["partial_waves"] > 0 and cen["c"]["max_steps"] == 2
+    assert cen["c"]["apply_chunks"] == 2
+    c = M.stride_case("c")
+    assert not np.array_equal(c.c_segs[0], c.c_segs[1])
+    assert not np.array_equal(c.s_segs[0], c.s_segs[1])
+    d = M.stride_case("d")
+    assert d.style.shape[2:] != d.content.shape[2:]
+    assert d.style_census["max_steps"] != cen["d"]["max_steps"]
+    e = cen["e"]
+    assert e["max_steps"] >= 2 and e["register"] == 0 and e["apply_chunks"] == 2
+    assert (131 * 133) % 4
+
+
+def _chunks(a, size):
+    """(N, C, h, w) -> the planes flattened and cut at multiples of `size`."""
+    flat = torch.as_tensor(a).reshape(a.shape[0], a.shape[1], -1)
+    return [flat[..., o:o + size] for o in range(0, flat.shape[-1], size)]
+
+
+@pytest.mark.parametrize("name", STRIDE_CASES)
+def test_masked_kernels_past_one_stride(cuda, name):
+    from rpst import ops
+    case = M.stride_case(name)
+    c, s, skip = case.content.to(cuda), case.style.to(cuda), case.skip.to(cuda)
+    cseg, sseg = dev(case.c_segs, cuda), dev(case.s_segs, cuda)
+    N = c.shape[0]
+    # plan: counts and validity flags, exactly
+    plan = ops.segment_plan(cseg, sseg)
+    assert np.array_equal(plan.cpu().numpy()[:, :, :3], case.counts), name
+    # parameters: pooled, then row by row (a pooled norm over hundreds of rows hides one label)
+    got = ops.masked_adain_params(c, s, cseg, sseg).cpu().numpy()
+    valid = case.counts[:, None, :, 2].astype(bool) & np.ones(case.rows.shape[:3], bool)
+    err = rel_l2(got[valid], case.rows[valid])
+    em, es = (max(v) for v in zip(*(M.row_errors(got[n], case.rows[n], case.counts[n])
+                                    for n in range(N))))
+    print(f"params {name}: rel-L2 {err:.3e} over {int(valid.sum())} rows, worst row mean "
+          f"{em:.3e} std {es:.3e}")
+    assert err < TOL_STATS, (name, err)
+    assert em <= TOL_STATS and es <= TOL_STATS, (name, em, es)
+    assert valid.any() and np.array_equal(got[~valid], case.rows[~valid]), name
+    # output: pooled, then every apply chunk of 16384 elements by itself
+    out = ops.masked_adain(c, s, cseg, sseg)
+    err = rel_l2(out, case.out)
+    per = [rel_l2(g, r) for g, r in zip(_chunks(out.cpu(), M.APPLY_ELEMS),
+                                        _chunks(case.out, M.APPLY_ELEMS))]
+    print(f"masked_adain {name}: rel-L2 {err:.3e}, per chunk "
+          + " ".join(f"{e:.3e}" for e in per))
+    assert err < TOL_STATS, (name, err)
+    assert len(per) == case.census["apply_chunks"] and max(per) < TOL_STATS, (name, per)
+    keep = np.stack([~case.counts[n][:, 2].astype(bool)[case.c_segs[n]] for n in range(N)])
+    keep = torch.from_numpy(keep).to(cuda)[:, None].expand_as(c)
+    assert torch.equal(out[keep], c[keep]), name
+    if name == "a-mixed":
+        assert int(keep[0, 0].sum()) == 10
+    assert not torch.equal(out[~keep], c[~keep]), name
+    assert torch.equal(out, ops.masked_adain(c, s, cseg, sseg)), name
+    assert torch.equal(ops.masked_adain(c, s, cseg, sseg, skip=skip, plan=plan), skip + out)
+    buf = torch.empty_like(c)
+    assert ops.masked_adain(c, s, cseg, sseg, plan=plan, out=buf) is buf
+    assert torch.equal(buf, out)
+    if N > 1:  # each image alone is its slice of the batch, bit for bit
+        for n in range(N):
+            one = ops.masked_adain(c[n:n + 1], s[n:n + 1], cseg[n:n + 1], sseg[n:n + 1])
+            assert torch.equal(out[n:n + 1], one), (name, n)
+
+
+def test_single_label_agrees_with_calc_mean_std_with_carried_runs(cuda):
+    """test_single_label_agrees_with_calc_mean_std where the runs are carried in registers
+    across steps: one label over (256, 160), 3 steps a slice, all but the first on the
+    register path."""
+    from rpst import ops
+    shape, lab = (1, 2, 256, 160), 60
+    seg = np.full((1, 256, 160), lab, np.uint8)
+    cen = M.run_path_census(seg[0], shape[1])
+    # 16 slices x (4 waves in the second step + the 2 active ones in the third)
+    assert cen["register"] == 96 and cen["element_later"] == 0 and cen["max_steps"] == 3
+    c = M.labelled_feature(171, shape, seg).to(cuda)
+    s = (M.labelled_feature(172, shape, seg) * 0.7 + 0.5).to(cuda)
+    p = ops.masked_adain_params(c, s, dev(seg, cuda), dev(seg, cuda))[:, :, lab].cpu().numpy()
+    cm, cs = (t.cpu().numpy().reshape(p.shape[:2]) for t in ops.calc_mean_std(c))
+    sm, ss = (t.cpu().numpy().reshape(p.shape[:2]) for t in ops.calc_mean_std(s))
+    for got, ref in ((p[..., 0], cm), (p[..., 1], cs), (p[..., 2], ss), (p[..., 3], sm)):
+        assert (np.abs(got - ref) <= np.spacing(np.abs(ref))).all()
+
+
+def test_multiscale_masked_at_136x128_vs_float64(cuda):
+    """One plan over every level of MultiScaleAdaINRPNet.test at a size where each level's
+    kernels repeat (case c's maps: 2 statistics steps with a partly active wave, 2 apply
+    chunks), against the float64 restatement on the same state dict."""
+    import network as net
+    case = M.stride_case("c")
+    m = net.MultiScaleAdaINRPNet(dict(multiscale_config(8, 5, 0), use_mask=True),
+                                 copy.deepcopy(net.vgg))
+    synth_(m, 33)
+    sd = {k: v.double() for k, v in state_dict_of(m).items()}
+    from helpers import gen
+    c, s = gen(181, (2, 3, 136, 128), 0.5, 0.5), gen(182, (2, 3, 136, 128), 0.5, 0.5)
+    ref = M.multiscale_test(c.double(), s.double(), sd, 5, case.c_segs, case.s_segs)
+    assert ref.dtype == torch.float64
+    m = m.to(cuda)
+    y = m.test(c.to(cuda), s.to(cuda), c_mask_path=dev(case.c_segs, cuda),
+               s_mask_path=dev(case.s_segs, cuda))
+    check_net(y, ref, "multiscale masked 136x128 vs float64")

@@ -10,7 +10,8 @@ import torch
 import torch.nn.functional as F
 
 import ld4_ref as L4
-from helpers import golden_net, rel_l2
+import ld_ref as L
+from helpers import TOL_STATS, gen, golden_net, rel_l2
 
 
 def _model(g, i):
@@ -233,3 +234,105 @@ def test_abi_argument_errors():
     import ctypes
     buf = (ctypes.c_int * 4)()
     assert lib.rpst_nearest_index_table(0, 4, ctypes.addressof(buf)) == -1 and "bad sizes" in err()
+
+
+# ---- the multi-chunk inputs tell a wrong walk from a right one -------------------------------
+# float64 on the very inputs of tests/test_gpu_ld4.py's multi-chunk cases: each slip that those
+# cases aim at, planted in ld4_ref's restatement of the kernels' walk, has to miss the bar it
+# is meant to trip by a factor of TEETH (and to change bits, where the test asks for bit
+# equality). The measured ratios: profiles/loop_strides/teeth.txt.
+TEETH = 10.0
+MULTI_RESIZE = [((2, 5, 33, 34), (65, 67)), ((1, 3, 23, 29), (65, 67)),
+                ((1, 2, 40, 52), (91, 93)), ((1, 4, 64, 64), (128, 128))]
+MULTI_FUSE = [((65, 67), (33, 34)), ((91, 93), (23, 29)), ((128, 128), (64, 64))]
+
+
+def test_walk_restated_covers_every_element():
+    """Without a slip write_planes is the identity, whatever the planes' heads; an odd plane
+    size cycles the heads through 0, 3, 2, 1."""
+    for hw, planes in ((4355, 10), (8463, 5), (16384, 3), (7, 4), (2, 3)):
+        val = np.arange(1, planes * hw + 1, dtype=np.float64).reshape(planes, hw)
+        for first in (0, 1):
+            assert np.array_equal(L4.write_planes(val, first), val)
+    assert [(-p * 4355) % 4 for p in range(4)] == [0, 1, 2, 3]
+    assert L4.CHUNK == 4096 and 4355 > L4.CHUNK and 8463 > 2 * L4.CHUNK
+
+
+def _plane_chunk_ratio(got, want):
+    """The worst rel-L2 over (plane, chunk of 4096 elements) / TOL_STATS."""
+    worst = 0.0
+    for o in range(0, want.shape[1], L4.CHUNK):
+        g, w = got[:, o:o + L4.CHUNK], want[:, o:o + L4.CHUNK]
+        worst = max(worst, float((np.linalg.norm(g - w, axis=1) / np.linalg.norm(w, axis=1)).max()))
+    return worst / TOL_STATS
+
+
+def _slip_applies(slip, hw, planes):
+    heads = {(-p * hw) % 4 for p in range(planes)}
+    if slip == "no_head":
+        return heads != {0}
+    if slip == "no_tail":
+        return any((hw - h) % 4 for h in heads)
+    return hw > L4.CHUNK
+
+
+@pytest.mark.parametrize("slip", ["chunk_base", "no_head", "no_tail"])
+@pytest.mark.parametrize("shape,size", MULTI_RESIZE)
+def test_teeth_resize_walk(shape, size, slip):
+    """resize_nearest, alone and into the upper channel slice of a tensor twice as wide: the
+    planted walk changes bits (the test asks for equality with F.interpolate)."""
+    n, c = shape[:2]
+    hw = size[0] * size[1]
+    want = F.interpolate(gen(41, shape, 2.0, 0.5), size).double().numpy()
+    for first, planes in ((0, want.reshape(-1, hw)), (c, want[0].reshape(-1, hw))):
+        if not _slip_applies(slip, hw, first + len(planes)):
+            assert slip != "chunk_base" and hw % 4 == 0  # aligned planes have no ragged ends
+            continue
+        got = L4.write_planes(planes, first, slip)
+        assert not np.array_equal(got, planes)
+        ratio = rel_l2(got, planes) / TOL_STATS
+        print(f"teeth resize {shape}->{size} {slip} (first plane {first}): bits differ, "
+              f"rel-L2 {ratio:.0f}x TOL_STATS")
+        assert ratio >= TEETH
+
+
+@pytest.mark.parametrize("slip", ["chunk_base", "no_head", "no_tail"])
+@pytest.mark.parametrize("ca,hd", [(0, 4), (4, 5), (3, 5), (3, 4)])
+@pytest.mark.parametrize("size,csize", MULTI_FUSE)
+def test_teeth_fuse_walk(size, csize, ca, hd, slip):
+    """ld4_fuse's output planes (y's, the fine half's, the gathered half's) written by the
+    planted walk: the per-chunk bar of test_ld4_fuse_vs_float64 is missed."""
+    n, hw = 2, size[0] * size[1]
+    y, fine, coarse, stats = L4.fuse_inputs(ca, hd, size, csize, n)
+    want = L4.fuse_want(fine, coarse, stats, size, n)
+    full = want if y is None else torch.cat([y.double(), want], dim=1)
+    planes = full.numpy().reshape(-1, hw)
+    if not _slip_applies(slip, hw, len(planes)):
+        assert slip != "chunk_base" and hw % 4 == 0
+        return
+    got = L4.write_planes(planes, 0, slip).reshape(n, ca + 2 * hd, hw)
+    ratio = _plane_chunk_ratio(got[:, ca:].reshape(-1, hw), want.numpy().reshape(-1, hw))
+    print(f"teeth fuse {ca}+2x{hd} {csize}->{size} {slip}: chunk bar missed by {ratio:.0f}x")
+    assert ratio >= TEETH
+
+
+@pytest.mark.parametrize("shape,size", MULTI_RESIZE)
+def test_teeth_resized_statistics(shape, size):
+    """resized_mean_std: the restated weighted sums are the statistics of the resized map
+    (1e-11), and stopping after one stride of 256 quads, or skipping the 0-3 tail elements,
+    misses TOL_STATS."""
+    x = gen(42, shape, 2.0, 0.5)
+    rm, rs = L.mean_std(F.interpolate(x, size).double())
+    m, s = L4.resized_stats(x, size)
+    assert rel_l2(m, rm) < 1e-11 and rel_l2(s, rs) < 1e-11
+    hw = shape[2] * shape[3]
+    # ((23, 29) is there for its ratios: 166 quads, one stride, and a 3-element tail)
+    assert hw // 4 > L4.STRIDE_QUADS or shape == (1, 3, 23, 29)
+    slips = (["one_stride"] if hw // 4 > L4.STRIDE_QUADS else []) + (["no_tail"] if hw % 4 else [])
+    for slip in slips:
+        m, s = L4.resized_stats(x, size, slip)
+        ratio = max(rel_l2(m, rm), rel_l2(s, rs)) / TOL_STATS
+        print(f"teeth resized_mean_std {shape}->{size} {slip}: TOL_STATS missed by {ratio:.0f}x")
+        assert ratio >= TEETH
+    if shape == (2, 5, 33, 34):
+        assert slips == ["one_stride", "no_tail"] and hw % 4 == 2
