@@ -361,6 +361,21 @@ int rpst_sanet_attention(const float* F, const float* G, const float* H, float* 
                          int C, int HW, void* workspace, size_t workspace_bytes,
                          rpst_stream_t stream);
 
+/* The same with a style of another size (SANet.forward reads G's own size, sanet.py:86-94):
+ * F and O are (B, C, HWq), G and H are (B, C, HWk); S = F^T G is HWq x HWk, the row softmax
+ * runs over the HWk keys, O = H S^T. rpst_sanet_attention is the HWq = HWk call of this entry
+ * (one body, the same bits).
+ * Flash path: C in {64, 128, 256, 512} and HWk % 4 == 0 (16-byte key rows for the LDS DMA).
+ * HWq needs no alignment (F and O are scalar accesses), so an odd HWq runs flash-style too.
+ * Each operand's own (C, HW) plane must stay under 2^31 bytes for the flash path. Every other
+ * shape materialises S: B*HWq*HWk floats plus 2*B*HWq of row statistics.
+ * Workspace: rpst_sanet_attention_qk_workspace_size_c(B, C, HWq, HWk) (0 on the flash path).
+ * RPST_EINVAL for a count < 1, RPST_EWORKSPACE for a short workspace, before any launch. */
+size_t rpst_sanet_attention_qk_workspace_size_c(int B, int C, int HWq, int HWk);
+int rpst_sanet_attention_qk(const float* F, const float* G, const float* H, float* O, int B,
+                            int C, int HWq, int HWk, void* workspace, size_t workspace_bytes,
+                            rpst_stream_t stream);
+
 /* ---- f3: AdaptiveSANet  network/sanet.py:12-18, 26-71, 100-138 ----
  * cal_affinity_matrix(c, s) (sanet.py:12-18): out[b] = normalize(c[b])^T normalize(s[b]),
  * normalize = x / max(||x||_2 over channels, 1e-12). c, s (B, C, HW) -> out (B, HW, HW).
@@ -636,6 +651,29 @@ int rpst_wct_status(const void* workspace, int n, int C, int64_t HW, int* status
                     rpst_stream_t stream);
 int rpst_whiten_and_color_status(const void* workspace, int C, int64_t HW, int* status,
                                  rpst_stream_t stream);
+
+/* ---- a9 with a style of another size (fuse flattens cf and sf independently, wct_rp.py:
+ * 157-166; whiten_and_color divides each covariance by its own pixel count - 1, :89-94).
+ * content and out: (n, C, HWc) fp32; style: (n, C, HWs) fp32. Per image:
+ *   mu_c, Cc = (cF - mu_c)(cF - mu_c)^T / (HWc - 1) + I   over the content's HWc pixels
+ *   mu_s, Cs = (sF - mu_s)(sF - mu_s)^T / (HWs - 1)       over the style's HWs pixels
+ *   T, the offset c = mu_s - T mu_c and out = T (cF - mu_c) + mu_s over the HWc pixels.
+ * The covariance's split-K is a function of each side's own pixel count, so an image's bits
+ * do not depend on its batch. means, T, offset, residual and status are as in the one-count
+ * entries (means: 2n x C, content rows first). rpst_wct_workspace_size, rpst_wct_fuse,
+ * rpst_wct_params and rpst_wct_status are the HWc = HWs calls of these (one body, the same
+ * bits). The fp64 entries (rpst_whiten_and_color_f64 / _original_f64) stay one-count.
+ * Workspace: rpst_wct_workspace_size_cs(n, C, HWc, HWs). RPST_EINVAL for a count < 2,
+ * RPST_EWORKSPACE for a short workspace, before any launch. */
+size_t rpst_wct_workspace_size_cs(int n, int C, int64_t HWc, int64_t HWs);
+int rpst_wct_fuse_cs(const float* content, const float* style, float* out, int n, int C,
+                     int64_t HWc, int64_t HWs, double* residual, void* workspace,
+                     size_t workspace_bytes, rpst_stream_t stream);
+int rpst_wct_params_cs(const float* content, const float* style, const float* means, double* T,
+                       double* offset, int n, int C, int64_t HWc, int64_t HWs, double* residual,
+                       void* workspace, size_t workspace_bytes, rpst_stream_t stream);
+int rpst_wct_status_cs(const void* workspace, int n, int C, int64_t HWc, int64_t HWs,
+                       int* status, rpst_stream_t stream);
 
 /* Measurement (bench.py): while armed (rpst_wct_phase_timing(1); returns the previous
  * setting), rpst_wct_params / rpst_wct_fuse record HIP events around their covariance phase

@@ -23,9 +23,9 @@
 namespace rpst {
 
 // flash-style forward attention (rpst_flash.hip)
-bool sanet_flash_ok(int C, int HW);
-int sanet_flash(const float* F, const float* G, const float* H, float* O, int B, int C, int HW,
-                hipStream_t st);
+bool sanet_flash_ok(int C, int HWq, int HWk);
+int sanet_flash(const float* F, const float* G, const float* H, float* O, int B, int C, int HWq,
+                int HWk, hipStream_t st);
 int adaptive_flash_stats(const float* F, const float* G, int B, int C, int HW, float* rm,
                          float* rinv, hipStream_t st);
 int adaptive_flash_apply(const float* F, const float* G, const float* H, float* O, int B, int C,
@@ -822,44 +822,58 @@ static int logits_rowstats(Mat Fq, int n, Mat G, float* S, float* rmax, float* r
 
 using namespace rpst;
 
-// the logits and their two softmax row vectors (the two-GEMM path; the flash path takes none)
+// the logits (B x HWq x HWk) and their two softmax row vectors (the two-GEMM path; the flash
+// path takes none)
 struct SanetLayout { float *S, *rmax, *rinv; size_t bytes; };
-static SanetLayout sanet_layout(void* workspace, int B, int HW) {
+static SanetLayout sanet_layout(void* workspace, int B, int HWq, int HWk) {
   Carver c(workspace);
-  if (B <= 0 || HW <= 0) return {};
-  const size_t rows = (size_t)B * HW;
-  float *S = c.take(rows * HW), *rmax = c.take(rows), *rinv = c.take(rows);
+  if (B <= 0 || HWq <= 0 || HWk <= 0) return {};
+  const size_t rows = (size_t)B * HWq;
+  float *S = c.take(rows * HWk), *rmax = c.take(rows), *rinv = c.take(rows);
   return {S, rmax, rinv, c.bytes};
 }
 
 extern "C" size_t rpst_sanet_attention_workspace_size(int B, int HW) {
-  return sanet_layout(nullptr, B, HW).bytes;
+  return sanet_layout(nullptr, B, HW, HW).bytes;
+}
+
+extern "C" size_t rpst_sanet_attention_qk_workspace_size_c(int B, int C, int HWq, int HWk) {
+  if (B <= 0 || C <= 0 || HWq <= 0 || HWk <= 0) return 0;
+  return sanet_flash_ok(C, HWq, HWk) ? 0 : sanet_layout(nullptr, B, HWq, HWk).bytes;
 }
 
 extern "C" size_t rpst_sanet_attention_workspace_size_c(int B, int C, int HW) {
-  if (B <= 0 || C <= 0 || HW <= 0) return 0;
-  return sanet_flash_ok(C, HW) ? 0 : rpst_sanet_attention_workspace_size(B, HW);
+  return rpst_sanet_attention_qk_workspace_size_c(B, C, HW, HW);
 }
 
-extern "C" int rpst_sanet_attention(const float* F, const float* G, const float* H, float* O,
-                                    int B, int C, int HW, void* workspace,
-                                    size_t workspace_bytes, rpst_stream_t stream) {
+extern "C" int rpst_sanet_attention_qk(const float* F, const float* G, const float* H, float* O,
+                                       int B, int C, int HWq, int HWk, void* workspace,
+                                       size_t workspace_bytes, rpst_stream_t stream) {
   RPST_REQUIRE(F && G && H && O, "sanet_attention: null pointer");
-  RPST_REQUIRE(B > 0 && C > 0 && HW > 0, "sanet_attention: bad shape B=%d C=%d HW=%d", B, C, HW);
+  RPST_REQUIRE(B > 0 && C > 0 && HWq > 0 && HWk > 0,
+               "sanet_attention: bad shape B=%d C=%d HW=%d/%d", B, C, HWq, HWk);
   RPST_REQUIRE(B <= 65535, "sanet_attention: batch too large");
-  if (sanet_flash_ok(C, HW)) return sanet_flash(F, G, H, O, B, C, HW, as_stream(stream));
-  const SanetLayout L = sanet_layout(workspace, B, HW);
+  if (sanet_flash_ok(C, HWq, HWk))
+    return sanet_flash(F, G, H, O, B, C, HWq, HWk, as_stream(stream));
+  const SanetLayout L = sanet_layout(workspace, B, HWq, HWk);
   RPST_REQUIRE_WS(L.bytes, "sanet_attention: workspace %zu < %zu bytes", workspace_bytes, L.bytes);
   hipStream_t st = as_stream(stream);
-  const int64_t fhw = (int64_t)C * HW;
-  if (int e = logits_rowstats({F, HW, fhw}, HW, {G, HW, fhw}, L.S, L.rmax, L.rinv, B, C,
+  const int64_t fq = (int64_t)C * HWq, fk = (int64_t)C * HWk;
+  if (int e = logits_rowstats({F, HWq, fq}, HWq, {G, HWk, fk}, L.S, L.rmax, L.rinv, B, C,
                               "gemm_f32_kernel(S=F^T G)", st))
     return e;
   // O[b][c][i] = (1/l_i) sum_j H[b][c][j] exp(S[b][i][j] - m_i)
-  launch_gemm<LAY_RK, LAY_RK, BX_EXP>({.A = {H, HW, fhw}, .B = {L.S, HW, (int64_t)HW * HW},
-                                       .C = {O, HW, fhw}, .M = C, .N = HW, .K = HW,
-                                       .rv = {.m = L.rmax}, .sV = HW, .colscale = L.rinv}, B, st);
+  launch_gemm<LAY_RK, LAY_RK, BX_EXP>({.A = {H, HWk, fk}, .B = {L.S, HWk, (int64_t)HWq * HWk},
+                                       .C = {O, HWq, fq}, .M = C, .N = HWq, .K = HWk,
+                                       .rv = {.m = L.rmax}, .sV = HWq, .colscale = L.rinv}, B, st);
   return launch_status("gemm_f32_kernel(O=H P^T)");
+}
+
+// the style at the content's size: the HWq = HWk call
+extern "C" int rpst_sanet_attention(const float* F, const float* G, const float* H, float* O,
+                                    int B, int C, int HW, void* workspace,
+                                    size_t workspace_bytes, rpst_stream_t stream) {
+  return rpst_sanet_attention_qk(F, G, H, O, B, C, HW, HW, workspace, workspace_bytes, stream);
 }
 
 // the column-normalised content and style features
@@ -966,7 +980,7 @@ static AdaptiveLayout adaptive_layout(void* workspace, int B, int C, int HW, int
   if (B <= 0 || C <= 0 || HW <= 0 || hidden <= 0) return L;
   const size_t rows = (size_t)B * HW, t = clamp_t_floats(B, C, HW, hidden);
   // whichever of T and S is larger; on the flash path (sanet_flash_ok) S is never formed
-  L.S = c.take(sanet_flash_ok(C, HW) ? t : std::max(rows * HW, t));
+  L.S = c.take(sanet_flash_ok(C, HW, HW) ? t : std::max(rows * HW, t));
   L.Z = c.take(rows * hidden);
   L.cn = c.take(rows * C);
   L.sn = c.take(rows * C);
@@ -1006,7 +1020,7 @@ extern "C" int rpst_adaptive_attention(const float* F, const float* G, const flo
                                     clamp, B, C, HW, st))
     return e;
   const Mat Fm{F, HW, (int64_t)C * HW}, Gm{G, HW, (int64_t)C * HW}, Hm{H, HW, (int64_t)C * HW};
-  if (sanet_flash_ok(C, HW)) {
+  if (sanet_flash_ok(C, HW, HW)) {
     // 2. pass 1: softmax row statistics of S = F^T G, S never written (rpst_flash.hip)
     if (int e = adaptive_flash_stats(F, G, B, C, HW, rmax, rinv, st)) return e;
     // the maps the caller keeps: S formed in its own (B, HW, HW) buffer and transformed in

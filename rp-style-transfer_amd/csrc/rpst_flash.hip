@@ -26,9 +26,11 @@ namespace rpst {
 // never leaves the registers. G and H tiles (C x 16 fp32 each) stream into a double-buffered
 // LDS ring by LDS-DMA one key block ahead (one barrier per key block); the H tile is stored
 // with its 16-B segments XOR-swizzled by (c / 4) % 4 so that the ds_read_b128 of 16 lanes
-// reading 16 channel rows is conflict-free. No 1/sqrt(d) (sanet.py:90-91). Keys past HW are
-// masked to -inf; queries past HW are not stored. HW % 4 == 0 (16-B rows) and C in
-// {64, 128, 256, 512}; other shapes take the two-GEMM path below.
+// reading 16 channel rows is conflict-free. No 1/sqrt(d) (sanet.py:90-91). F and O are
+// (B, C, HWq), G and H (B, C, HWk): the style may have another size than the content. Keys
+// past HWk are masked to -inf; queries past HWq are not stored. HWk % 4 == 0 (16-B key rows
+// for the DMA; F and O are scalar accesses, so HWq needs no alignment) and C in
+// {64, 128, 256, 512}; other shapes take the two-GEMM path (rpst_attn.hip).
 constexpr int kFBM = 64, kFBN = 16;
 // timing-only builds (results wrong; tools/build_variants.sh rpst_flash.hip "x:-DRPST_FLDBG=n"):
 // 1 no softmax (P = S), 2 no DMA waits / barriers, 4 no DMA, 8 no O update
@@ -104,8 +106,9 @@ template <int C, int AM>
 __global__ __launch_bounds__(256, 1) void sanet_flash_kernel(const float* __restrict__ F,
                                                              const float* __restrict__ G,
                                                              const float* __restrict__ H,
-                                                             float* __restrict__ O, int HW,
-                                                             int qblocks, AttnRows rows) {
+                                                             float* __restrict__ O, int HWq,
+                                                             int HWk, int qblocks,
+                                                             AttnRows rows) {
   constexpr int NQ = C / 4;            // Q registers per lane
   constexpr int NMB = C / 16;          // O accumulators (16 channel rows each)
   constexpr int TILE = C * kFBN;       // floats per G / H tile
@@ -122,19 +125,21 @@ __global__ __launch_bounds__(256, 1) void sanet_flash_kernel(const float* __rest
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int g = lane >> 4, lq = lane & 15;
   const int q = qb * kFBM + wave * 16 + lq;  // this lane's query
-  const int64_t plane = (int64_t)C * HW;
-  const float* Fb = F + b * plane;
-  const unsigned bytes = (unsigned)(plane * 4);
-  const auto rG = __builtin_amdgcn_make_buffer_rsrc((void*)(G + b * plane), (short)0, (int)bytes, 0x00020000);
-  const auto rH = __builtin_amdgcn_make_buffer_rsrc((void*)(H + b * plane), (short)0, (int)bytes, 0x00020000);
+  // F / O planes are C x HWq, G / H planes C x HWk; the descriptors bound G and H by their own
+  // plane
+  const int64_t qplane = (int64_t)C * HWq, kplane = (int64_t)C * HWk;
+  const float* Fb = F + b * qplane;
+  const unsigned bytes = (unsigned)(kplane * 4);
+  const auto rG = __builtin_amdgcn_make_buffer_rsrc((void*)(G + b * kplane), (short)0, (int)bytes, 0x00020000);
+  const auto rH = __builtin_amdgcn_make_buffer_rsrc((void*)(H + b * kplane), (short)0, (int)bytes, 0x00020000);
   // DMA piece j of a tile: lane -> (channel row 16 j + lane / 4, 16-B segment lane % 4). The
   // whole offset goes in voffset (not the piece's uniform row offset in soffset): the buffer
-  // range check covers voffset only, and with HW % 16 != 0 the last key block of the last
+  // range check covers voffset only, and with HWk % 16 != 0 the last key block of the last
   // channel row runs past the image plane -- those keys must read as 0, not as whatever
   // follows the tensor (a non-finite H there would turn 0 * H into NaN in O)
   const int prow = lane >> 2, pseg = lane & 3;
-  const unsigned voffG = (unsigned)(prow * HW + 4 * pseg) * 4u;
-  const unsigned voffH = (unsigned)(prow * HW + 4 * (pseg ^ ((lane >> 4) & 3))) * 4u;
+  const unsigned voffG = (unsigned)(prow * HWk + 4 * pseg) * 4u;
+  const unsigned voffH = (unsigned)(prow * HWk + 4 * (pseg ^ ((lane >> 4) & 3))) * 4u;
   // one DMA piece (jj < PPW: G piece jj, else H piece jj - PPW) of key block k0 / 16; a
   // step's 2 PPW pieces are spread one per MFMA group (scores: NQ / SG = 2 PPW groups) so each
   // issue hides in an MFMA gap instead of stalling a clustered run of them
@@ -144,10 +149,10 @@ __global__ __launch_bounds__(256, 1) void sanet_flash_kernel(const float* __rest
     const int j = wave * PPW + (isg ? jj : jj - PPW);
     if (isg) {
       if (k0g >= 0)
-        __builtin_amdgcn_raw_ptr_buffer_load_lds(rG, (attn_lds_ptr_t)(gs + 256 * j), 16, (int)(voffG + (unsigned)(16 * j * HW + k0g) * 4u), 0,
+        __builtin_amdgcn_raw_ptr_buffer_load_lds(rG, (attn_lds_ptr_t)(gs + 256 * j), 16, (int)(voffG + (unsigned)(16 * j * HWk + k0g) * 4u), 0,
                                                  0, 0);
     } else if (k0h >= 0) {
-      __builtin_amdgcn_raw_ptr_buffer_load_lds(rH, (attn_lds_ptr_t)(hs + 256 * j), 16, (int)(voffH + (unsigned)(16 * j * HW + k0h) * 4u), 0,
+      __builtin_amdgcn_raw_ptr_buffer_load_lds(rH, (attn_lds_ptr_t)(hs + 256 * j), 16, (int)(voffH + (unsigned)(16 * j * HWk + k0h) * 4u), 0,
                                                0, 0);
     }
   };
@@ -158,16 +163,16 @@ __global__ __launch_bounds__(256, 1) void sanet_flash_kernel(const float* __rest
 #pragma unroll
     for (int jj = 0; jj < PPW; ++jj) {
       const int j = wave * PPW + jj;
-      __builtin_amdgcn_raw_ptr_buffer_load_lds(rG, (attn_lds_ptr_t)(gs + 256 * j), 16, (int)(voffG + (unsigned)(16 * j * HW + k0) * 4u), 0,
+      __builtin_amdgcn_raw_ptr_buffer_load_lds(rG, (attn_lds_ptr_t)(gs + 256 * j), 16, (int)(voffG + (unsigned)(16 * j * HWk + k0) * 4u), 0,
                                                0, 0);
     }
   };
-  const int nk = (HW + kFBN - 1) / kFBN;
+  const int nk = (HWk + kFBN - 1) / kFBN;
   issue_g(0, Gs0);
 
   float qv[NQ];
 #pragma unroll
-  for (int s = 0; s < NQ; ++s) qv[s] = q < HW ? Fb[(int64_t)(4 * s + g) * HW + q] : 0.f;
+  for (int s = 0; s < NQ; ++s) qv[s] = q < HWq ? Fb[(int64_t)(4 * s + g) * HWq + q] : 0.f;
   // Q lives in AGPRs (the MFMA reads its B operand from there): the arch VGPRs hold the O
   // accumulator (rescaled by the VALU) and the LDS operands read ahead of their MFMAs
 #pragma unroll
@@ -179,8 +184,8 @@ __global__ __launch_bounds__(256, 1) void sanet_flash_kernel(const float* __rest
   // pass 2: this lane's query's row statistics and clamp, exp2 arguments pre-scaled
   float a_mL = 0.f, a_inv = 0.f, a_c = 0.f, a_m2L = 0.f;
   if constexpr (AM >= AM_AEA) {
-    if (q < HW) {
-      const int64_t r = (int64_t)b * HW + q;
+    if (q < HWq) {
+      const int64_t r = (int64_t)b * HWq + q;
       a_mL = rows.m[r] * kLog2e;
       a_inv = rows.inv[r];
       a_c = rows.c[r];
@@ -238,7 +243,7 @@ __global__ __launch_bounds__(256, 1) void sanet_flash_kernel(const float* __rest
         } else {
           v = __builtin_amdgcn_exp2f(fmaf(fmaxf(P - a_c, 0.f), kLog2e, -a_m2L));
         }
-        p[r] = kbase + r < HW ? v : 0.f;  // keys past HW weigh nothing
+        p[r] = kbase + r < HWk ? v : 0.f;  // keys past HWk weigh nothing
         if constexpr (AM == AM_AEAR) l_run += p[r];
       }
       return;
@@ -246,7 +251,7 @@ __global__ __launch_bounds__(256, 1) void sanet_flash_kernel(const float* __rest
     float sv[4], mx = -INFINITY;
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
-      sv[r] = kbase + r < HW ? sc[r] : -INFINITY;
+      sv[r] = kbase + r < HWk ? sc[r] : -INFINITY;
       mx = fmaxf(mx, sv[r]);
     }
     const float m_new = fmaxf(m_run, rows4_max(mx));
@@ -323,19 +328,19 @@ __global__ __launch_bounds__(256, 1) void sanet_flash_kernel(const float* __rest
   // the row sum over the four lane groups holding a query's keys; O / l
   if constexpr (AM != AM_AEA) l_run = rows4_sum(l_run);
   if constexpr (AM == AM_STATS) {
-    if (q < HW && g == 0) {
-      rows.out_m[(int64_t)b * HW + q] = m_run;
-      rows.out_inv[(int64_t)b * HW + q] = 1.f / l_run;
+    if (q < HWq && g == 0) {
+      rows.out_m[(int64_t)b * HWq + q] = m_run;
+      rows.out_inv[(int64_t)b * HWq + q] = 1.f / l_run;
     }
     return;
   }
-  if (q < HW) {
+  if (q < HWq) {
     const float inv = AM == AM_AEA ? 1.f : 1.f / l_run;
-    float* Ob = O + b * plane + q;
+    float* Ob = O + b * qplane + q;
 #pragma unroll
     for (int mb = 0; mb < NMB; ++mb)
 #pragma unroll
-      for (int r = 0; r < 4; ++r) Ob[(int64_t)(16 * mb + 4 * g + r) * HW] = acc[mb][r] * inv;
+      for (int r = 0; r < 4; ++r) Ob[(int64_t)(16 * mb + 4 * g + r) * HWq] = acc[mb][r] * inv;
   }
 }
 
@@ -348,42 +353,45 @@ static bool sanet_flash_on() {
   }();
   return on;
 }
-bool sanet_flash_ok(int C, int HW) {
-  return sanet_flash_on() && (C == 64 || C == 128 || C == 256 || C == 512) && HW % 4 == 0 &&
-         (int64_t)C * HW * 4 < (1LL << 31);
+// HWq: the F / O pixel count (no alignment asked: scalar accesses), HWk: the G / H one (16-B
+// rows for the DMA). Each operand's own plane stays under 2^31 bytes (32-bit byte offsets).
+bool sanet_flash_ok(int C, int HWq, int HWk) {
+  return sanet_flash_on() && (C == 64 || C == 128 || C == 256 || C == 512) && HWk % 4 == 0 &&
+         (int64_t)C * HWq * 4 < (1LL << 31) && (int64_t)C * HWk * 4 < (1LL << 31);
 }
 
 // One workgroup per (image, 64 queries) of sanet_flash_kernel<C, AM>.
 template <int AM>
 static int flash_launch(const float* F, const float* G, const float* H, float* O, int B, int C,
-                        int HW, const AttnRows& rows, hipStream_t st) {
-  const int qblocks = (HW + kFBM - 1) / kFBM;
+                        int HWq, int HWk, const AttnRows& rows, hipStream_t st) {
+  const int qblocks = (HWq + kFBM - 1) / kFBM;
   const int64_t nb = (int64_t)B * qblocks;
   RPST_REQUIRE(nb <= 0x7fffffffLL, "%s: grid too large",
                AM == AM_SOFTMAX ? "sanet_attention" : "adaptive_attention");
   const unsigned grid = (unsigned)nb;
   switch (C) {
-    case 64: sanet_flash_kernel<64, AM><<<grid, 256, 0, st>>>(F, G, H, O, HW, qblocks, rows); break;
-    case 128: sanet_flash_kernel<128, AM><<<grid, 256, 0, st>>>(F, G, H, O, HW, qblocks, rows); break;
-    case 256: sanet_flash_kernel<256, AM><<<grid, 256, 0, st>>>(F, G, H, O, HW, qblocks, rows); break;
-    default: sanet_flash_kernel<512, AM><<<grid, 256, 0, st>>>(F, G, H, O, HW, qblocks, rows); break;
+    case 64: sanet_flash_kernel<64, AM><<<grid, 256, 0, st>>>(F, G, H, O, HWq, HWk, qblocks, rows); break;
+    case 128: sanet_flash_kernel<128, AM><<<grid, 256, 0, st>>>(F, G, H, O, HWq, HWk, qblocks, rows); break;
+    case 256: sanet_flash_kernel<256, AM><<<grid, 256, 0, st>>>(F, G, H, O, HWq, HWk, qblocks, rows); break;
+    default: sanet_flash_kernel<512, AM><<<grid, 256, 0, st>>>(F, G, H, O, HWq, HWk, qblocks, rows); break;
   }
   return launch_status(AM == AM_SOFTMAX ? "sanet_flash_kernel"
                        : AM == AM_STATS ? "sanet_flash_kernel(stats)"
                                         : "sanet_flash_kernel(adaptive)");
 }
 
-int sanet_flash(const float* F, const float* G, const float* H, float* O, int B, int C, int HW,
-                hipStream_t st) {
-  return flash_launch<AM_SOFTMAX>(F, G, H, O, B, C, HW, {}, st);
+int sanet_flash(const float* F, const float* G, const float* H, float* O, int B, int C, int HWq,
+                int HWk, hipStream_t st) {
+  return flash_launch<AM_SOFTMAX>(F, G, H, O, B, C, HWq, HWk, {}, st);
 }
 
 // AdaptiveSANet attention without S (sanet.py:100-124): pass 1 writes each query's softmax
 // statistics (rm, rinv: B x HW each), pass 2 recomputes S per key block and accumulates
 // O = H Q^T with the clamp applied in registers. mode 0 = AEAModule, 1 = AEALReluModule.
+// Square only (HWq = HWk = HW): f_psi's width is tied to the image size.
 int adaptive_flash_stats(const float* F, const float* G, int B, int C, int HW, float* rm,
                          float* rinv, hipStream_t st) {
-  return flash_launch<AM_STATS>(F, G, nullptr, nullptr, B, C, HW, {.out_m = rm, .out_inv = rinv},
+  return flash_launch<AM_STATS>(F, G, nullptr, nullptr, B, C, HW, HW, {.out_m = rm, .out_inv = rinv},
                                 st);
 }
 
@@ -391,8 +399,8 @@ int adaptive_flash_apply(const float* F, const float* G, const float* H, float* 
                          int HW, const float* rm, const float* rinv, const float* clamp, int mode,
                          float scale, hipStream_t st) {
   const AttnRows rows{.m = rm, .inv = rinv, .c = clamp, .scale = scale};
-  return mode == 0 ? flash_launch<AM_AEA>(F, G, H, O, B, C, HW, rows, st)
-                   : flash_launch<AM_AEAR>(F, G, H, O, B, C, HW, rows, st);
+  return mode == 0 ? flash_launch<AM_AEA>(F, G, H, O, B, C, HW, HW, rows, st)
+                   : flash_launch<AM_AEAR>(F, G, H, O, B, C, HW, HW, rows, st);
 }
 
 }  // namespace rpst

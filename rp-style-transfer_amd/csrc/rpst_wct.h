@@ -8,16 +8,16 @@
 namespace rpst {
 
 // ---- covariance of fp32 features, C <= 256 (cov_syrk_kernel + cov_finish_kernel) ----------
-// For z < n: Cc_z = (cF_z - mu)(cF_z - mu)^T / (HW - 1) + I, for z >= n: Cs = (sF - mu)(..)^T /
-// (HW - 1), mu the fp64 row means (wct_rp.py:85-94). The features are centred on the fp32
+// For z < n: Cc_z = (cF_z - mu)(cF_z - mu)^T / (HWc - 1) + I, for z >= n: Cs = (sF - mu)(..)^T /
+// (HWs - 1), mu the fp64 row means (wct_rp.py:85-94); cF is (n, C, HWc), sF (n, C, HWs). The features are centred on the fp32
 // means `mu32` (2n x C, content rows then style rows) while staged; the fp64 mean follows from
 // the row sums of the centred rows, delta = sum(x - mu32) / HW, and the product is corrected by
 // -HW delta delta^T, so mu64 = mu32 + delta and the covariance are those of the exact fp64
 // centring. Outputs Cc, Cs (n x C x C, symmetric) and mu64 (2n x C).
 bool cov_v2_supported(int C);
-size_t cov_v2_work_doubles(int n, int C, int64_t HW);
-int cov_v2(const float* cF, const float* sF, const float* mu32, int n, int C, int64_t HW,
-           double* Cc, double* Cs, double* mu64, double* work, hipStream_t st);
+size_t cov_v2_work_doubles(int n, int C, int64_t HWc, int64_t HWs);
+int cov_v2(const float* cF, const float* sF, const float* mu32, int n, int C, int64_t HWc,
+           int64_t HWs, double* Cc, double* Cs, double* mu64, double* work, hipStream_t st);
 
 // ---- persistent matrix functions (one launch; groups of workgroups per matrix) -------------
 // WCT: T_b = Ic Mid Ic with Sc, Ic = (Cc_b + 1e-4 I)^(+-1/2), Mid = (Sc Cs_b Sc + 1e-4 I)^(1/2)

@@ -1,7 +1,9 @@
 // Closed-form WCT (Lu et al.) in fp64 on gfx950 — network/wct_rp.py:7-40, 82-114, 157-166.
 //
-// Per image (cF, sF: C x HW features, read as fp32 and widened to fp64 in registers,
-// exactly like the reference's `.double()`):
+// Per image (cF: C x HWc and sF: C x HWs features, read as fp32 and widened to fp64 in
+// registers, exactly like the reference's `.double()`; each side's n below is its own pixel
+// count, and the style may have another size than the content: fuse flattens them
+// independently, wct_rp.py:157-166):
 //   mu_c, mu_s                       row means (fp64)                      wct_rp.py:85,92
 //   Cc = (cF-mu)(cF-mu)^T/(n-1) + I  fp64 MFMA "SYRK": only upper-triangular tiles,
 //   Cs = (sF-mu)(sF-mu)^T/(n-1)      split-K partials + fixed-order reduce  wct_rp.py:89,94
@@ -414,12 +416,15 @@ int wct_apply_f32(const double* T, const double* c, const float* x, float* z, in
   return wct_transform_f32(T, nullptr, c, x, z, n, C, HW, scratch, st);
 }
 
-// Row means in fp64 of `rows` rows of length L (one workgroup per row).
+// Row means in fp64 (one workgroup per row): rows0 rows of length L0 from x0, then the rows
+// of length L1 from x1.
 template <typename T>
 __global__ __launch_bounds__(256) void rowmean_kernel(const T* __restrict__ x0,
                                                       const T* __restrict__ x1, int rows0,
-                                                      int64_t L, double* __restrict__ mean) {
+                                                      int64_t L0, int64_t L1,
+                                                      double* __restrict__ mean) {
   const int r = blockIdx.x;
+  const int64_t L = r < rows0 ? L0 : L1;
   const T* x = (r < rows0 ? x0 + (int64_t)r * L : x1 + (int64_t)(r - rows0) * L);
   double s = 0.0;
   constexpr int V = 16 / sizeof(T);
@@ -520,32 +525,36 @@ static int pick_ksplit(int64_t K) {
   return s < 1 ? 1 : (s > 128 ? 128 : (int)s);
 }
 
-// The workspace of every entry point: a function of (n, C, HW, feature type) alone.
+// The workspace of every entry point: a function of (n, C, HWc, HWs, feature type) alone.
 struct WctLayout {
-  int n, C, ksplit, BT, tiles, symtiles;
+  int n, C, ksplit_c, ksplit_s, BT, tiles, symtiles;  // ksplit_*: cov_tiled's, per side
   bool v2;  // fp32 features with C <= 256: cov_syrk_kernel (rpst_wct_mat.hip)
-  int64_t HW;
+  int64_t HWc, HWs;  // pixels of a content / a style image
   // offsets in doubles
   size_t mu_c, mu_s, mu32, part, cc, cs, tm, off, tf, mf, orig;
   size_t total;
 };
 
-static WctLayout wct_layout(int n, int C, int64_t HW, bool f32) {
+static WctLayout wct_layout(int n, int C, int64_t HWc, int64_t HWs, bool f32) {
   WctLayout L{};
   L.n = n;
   L.C = C;
-  L.HW = HW;
+  L.HWc = HWc;
+  L.HWs = HWs;
   L.v2 = f32 && cov_v2_supported(C);
   L.BT = C >= 128 ? 128 : 64;
   L.tiles = (C + L.BT - 1) / L.BT;
   L.symtiles = L.tiles * (L.tiles + 1) / 2;
-  L.ksplit = pick_ksplit(HW);
+  L.ksplit_c = pick_ksplit(HWc);
+  L.ksplit_s = pick_ksplit(HWs);
   const size_t cc = (size_t)C * C * n;
   size_t o = 0;
   L.mu_c = o; o += (size_t)n * C;
   L.mu_s = o; o += (size_t)n * C;  // mu_s follows mu_c: one (2n x C) array
   L.mu32 = o; o += ((size_t)2 * n * C + 1) / 2;  // fp32 centring means (v2 without `means`)
-  L.part = o; o += L.v2 ? cov_v2_work_doubles(n, C, HW) : (size_t)2 * n * L.ksplit * C * C;
+  L.part = o;
+  o += L.v2 ? cov_v2_work_doubles(n, C, HWc, HWs)
+            : (size_t)n * (L.ksplit_c + L.ksplit_s) * C * C;
   L.cc = o; o += cc;
   L.cs = o; o += cc;
   L.tm = o; o += cc;
@@ -582,17 +591,19 @@ static int cov_tiled(const void* cF, const void* sF, const WctLayout& L, double*
                      hipStream_t st) {
   const int n = L.n, C = L.C;
   double* part = ws + L.part;
-  const size_t half = (size_t)n * L.ksplit * C * C;
+  const size_t cpart = (size_t)n * L.ksplit_c * C * C;  // the content partials; the style's follow
   for (int which = 0; which < 2; ++which) {
     const void* X = which == 0 ? cF : sF;
-    G64Args g = g64(X, X, part + which * half, C, C, (int)L.HW, (int)L.HW, (int)L.HW, C);
+    const int HW = (int)(which == 0 ? L.HWc : L.HWs);
+    const int ksplit = which == 0 ? L.ksplit_c : L.ksplit_s;
+    G64Args g = g64(X, X, part + which * cpart, C, C, HW, HW, HW, C);
     g.sB = g.sA;  // B_NK: X again
     g.amean = g.bmean = ws + (which == 0 ? L.mu_c : L.mu_s);
     g.sMean = C;
-    g.ksplit = L.ksplit;
+    g.ksplit = ksplit;
     g.sym = 1;
     g.tiles_n = L.tiles;
-    dim3 grid(L.symtiles, 1, n * L.ksplit);
+    dim3 grid(L.symtiles, 1, n * ksplit);
     if (L.BT == 128)
       gemm64<128, SRC, SRC, B_NK, OUT_PARTIAL>(g, grid, st);
     else
@@ -601,9 +612,10 @@ static int cov_tiled(const void* cF, const void* sF, const WctLayout& L, double*
   }
   const int64_t nel = (int64_t)n * C * C;
   const unsigned rb = (unsigned)((nel + 255) / 256);
-  const double scale = 1.0 / (double)(L.HW - 1);
-  cov_reduce_kernel<<<rb, 256, 0, st>>>(part, ws + L.cc, C, L.ksplit, L.BT, scale, 1.0, n);
-  cov_reduce_kernel<<<rb, 256, 0, st>>>(part + half, ws + L.cs, C, L.ksplit, L.BT, scale, 0.0, n);
+  cov_reduce_kernel<<<rb, 256, 0, st>>>(part, ws + L.cc, C, L.ksplit_c, L.BT,
+                                        1.0 / (double)(L.HWc - 1), 1.0, n);
+  cov_reduce_kernel<<<rb, 256, 0, st>>>(part + cpart, ws + L.cs, C, L.ksplit_s, L.BT,
+                                        1.0 / (double)(L.HWs - 1), 0.0, n);
   return launch_status("cov_reduce_kernel");
 }
 
@@ -619,7 +631,8 @@ static int wct_moments(const void* cF, const void* sF, const float* means, const
   double* mu = ws + L.mu_c;
   if (!means) {
     rowmean_kernel<F><<<2 * n * C, 256, 0, st>>>(static_cast<const F*>(cF),
-                                                static_cast<const F*>(sF), n * C, L.HW, mu);
+                                                static_cast<const F*>(sF), n * C, L.HWc, L.HWs,
+                                                mu);
     if (int e = launch_status("rowmean_kernel")) return e;
   }
   if (L.v2) {
@@ -631,8 +644,8 @@ static int wct_moments(const void* cF, const void* sF, const float* means, const
       if (int e = convert(mu, m32, cnt, st)) return e;
       mu32 = m32;
     }
-    return cov_v2(static_cast<const float*>(cF), static_cast<const float*>(sF), mu32, n, C, L.HW,
-                  ws + L.cc, ws + L.cs, mu, ws + L.part, st);
+    return cov_v2(static_cast<const float*>(cF), static_cast<const float*>(sF), mu32, n, C, L.HWc,
+                  L.HWs, ws + L.cc, ws + L.cs, mu, ws + L.part, st);
   }
   if (means)
     if (int e = convert(means, mu, cnt, st)) return e;
@@ -690,8 +703,9 @@ static int wct_original(const WctLayout& L, double* ws, double* T, hipStream_t s
   return launch_status("gemm_f64_kernel(original T)");
 }
 
-// out = T (cF - mu_c) + mu_s with T in L.tm and the means in the workspace; fp32 features ->
-// fp32 out on the fp32 MFMA (RPST_WCT_T_F64=1: the fp64 product), fp64 -> fp64
+// out = T (cF - mu_c) + mu_s over the content's HWc pixels, with T in L.tm and the means in the
+// workspace; fp32 features -> fp32 out on the fp32 MFMA (RPST_WCT_T_F64=1: the fp64 product),
+// fp64 -> fp64
 template <int SRC>
 static int wct_transform(const void* cF, void* out, const WctLayout& L, double* ws,
                          hipStream_t st) {
@@ -699,13 +713,13 @@ static int wct_transform(const void* cF, void* out, const WctLayout& L, double* 
   double *mu_c = ws + L.mu_c, *mu_s = ws + L.mu_s, *Tm = ws + L.tm;
   if (SRC == SRC_F32C && !env_int("RPST_WCT_T_F64", 0))
     return wct_transform_f32(Tm, mu_c, mu_s, static_cast<const float*>(cF),
-                             static_cast<float*>(out), n, C, L.HW,
+                             static_cast<float*>(out), n, C, L.HWc,
                              reinterpret_cast<float*>(ws + L.tf), st);
-  G64Args g = g64(Tm, cF, out, C, (int)L.HW, C, C, (int)L.HW, (int)L.HW);
+  G64Args g = g64(Tm, cF, out, C, (int)L.HWc, C, C, (int)L.HWc, (int)L.HWc);
   g.bmean = mu_c;
   g.bias = mu_s;
   g.sMean = C;
-  dim3 grid((unsigned)((L.HW + 63) / 64), (C + 63) / 64, n);
+  dim3 grid((unsigned)((L.HWc + 63) / 64), (C + 63) / 64, n);
   gemm64<64, SRC_F64, SRC, B_KN, SRC == SRC_F32C ? OUT_F32_BIAS : OUT_F64_BIAS>(g, grid, st);
   return launch_status("gemm_f64_kernel(transform)");
 }
@@ -730,22 +744,26 @@ struct EntryLimits {
   bool detail;
 };
 
-// Null pointers, then the shape, then the workspace against need(n, C, HW) (need null: the
-// entry takes no workspace size); nothing is launched before these pass.
-static int check_entry(const char* name, bool pointers, int n, int C, int64_t HW,
-                       const EntryLimits& lim, size_t (*need)(int, int, int64_t),
+// Null pointers, then the shape (HWc pixels per content image, HWs per style image; an entry
+// with one count passes it twice), then the workspace against need(n, C, HWc, HWs) (need null:
+// the entry takes no workspace size); nothing is launched before these pass.
+static int check_entry(const char* name, bool pointers, int n, int C, int64_t HWc, int64_t HWs,
+                       const EntryLimits& lim, size_t (*need)(int, int, int64_t, int64_t),
                        const void* workspace, size_t workspace_bytes) {
   RPST_REQUIRE(pointers, "%s: null pointer", name);
-  const bool positive = n > 0 && C > 0 && HW > 1;
-  const bool fits = n <= lim.max_n && C <= lim.max_C && HW <= lim.max_HW;
+  const bool positive = n > 0 && C > 0 && HWc > 1 && HWs > 1;
+  const bool fits = n <= lim.max_n && C <= lim.max_C && HWc <= lim.max_HW && HWs <= lim.max_HW;
   if (lim.detail) {
-    RPST_REQUIRE(positive, "%s: bad shape n=%d C=%d HW=%lld", name, n, C, (long long)HW);
+    if (HWc == HWs)
+      RPST_REQUIRE(positive, "%s: bad shape n=%d C=%d HW=%lld", name, n, C, (long long)HWc);
+    RPST_REQUIRE(positive, "%s: bad shape n=%d C=%d HW=%lld/%lld", name, n, C, (long long)HWc,
+                 (long long)HWs);
     RPST_REQUIRE(fits, "%s: shape too large", name);
   } else {
     RPST_REQUIRE(positive && fits, "%s: bad shape", name);
   }
   if (!need) return RPST_OK;
-  const size_t bytes = need(n, C, HW);
+  const size_t bytes = need(n, C, HWc, HWs);
   if (workspace && workspace_bytes >= bytes) return RPST_OK;
   if (lim.detail) set_error("%s: workspace %zu < %zu bytes", name, workspace_bytes, bytes);
   else set_error("%s: workspace too small", name);
@@ -754,17 +772,17 @@ static int check_entry(const char* name, bool pointers, int n, int C, int64_t HW
 
 // the per-image status words of the last closed-form call on `workspace` (laid out for fp32
 // or fp64 features) copied to `status`
-static int copy_status(const char* name, const void* workspace, int n, int C, int64_t HW, bool f32,
-                       int* status, rpst_stream_t stream) {
-  if (int e = check_entry(name, workspace && status, n, C, HW, {INT_MAX, 1024, INT64_MAX, false},
-                          nullptr, nullptr, 0))
+static int copy_status(const char* name, const void* workspace, int n, int C, int64_t HWc,
+                       int64_t HWs, bool f32, int* status, rpst_stream_t stream) {
+  if (int e = check_entry(name, workspace && status, n, C, HWc, HWs,
+                          {INT_MAX, 1024, INT64_MAX, false}, nullptr, nullptr, 0))
     return e;
-  const WctLayout L = wct_layout(n, C, HW, f32);
+  const WctLayout L = wct_layout(n, C, HWc, HWs, f32);
   double* ws = static_cast<double*>(const_cast<void*>(workspace));
   return matfun_wct_status(ws + L.mf, n, C, status, as_stream(stream));
 }
 
-static size_t matrix_power_need(int batch, int n, int64_t) {
+static size_t matrix_power_need(int batch, int n, int64_t, int64_t) {
   return rpst_matrix_power_workspace_size(n, batch);
 }
 
@@ -772,21 +790,26 @@ static size_t matrix_power_need(int batch, int n, int64_t) {
 
 using namespace rpst;
 
-extern "C" size_t rpst_wct_workspace_size(int n, int C, int64_t HW) {
-  if (n <= 0 || C <= 0 || HW <= 1) return 0;
+extern "C" size_t rpst_wct_workspace_size_cs(int n, int C, int64_t HWc, int64_t HWs) {
+  if (n <= 0 || C <= 0 || HWc <= 1 || HWs <= 1) return 0;
   // the larger of the fp32-feature and fp64-feature layouts (one size for every entry point)
-  const size_t a = wct_layout(n, C, HW, true).total, b = wct_layout(n, C, HW, false).total;
+  const size_t a = wct_layout(n, C, HWc, HWs, true).total,
+               b = wct_layout(n, C, HWc, HWs, false).total;
   return (a > b ? a : b) * sizeof(double);
 }
 
-extern "C" int rpst_wct_fuse(const float* content, const float* style, float* out, int n, int C,
-                             int64_t HW, double* residual, void* workspace,
-                             size_t workspace_bytes, rpst_stream_t stream) {
-  if (int e = check_entry("wct_fuse", content && style && out, n, C, HW,
-                          {32767, 1024, 0x7fffffffLL, true}, rpst_wct_workspace_size, workspace,
-                          workspace_bytes))
+extern "C" size_t rpst_wct_workspace_size(int n, int C, int64_t HW) {
+  return rpst_wct_workspace_size_cs(n, C, HW, HW);
+}
+
+extern "C" int rpst_wct_fuse_cs(const float* content, const float* style, float* out, int n,
+                                int C, int64_t HWc, int64_t HWs, double* residual,
+                                void* workspace, size_t workspace_bytes, rpst_stream_t stream) {
+  if (int e = check_entry("wct_fuse", content && style && out, n, C, HWc, HWs,
+                          {32767, 1024, 0x7fffffffLL, true}, rpst_wct_workspace_size_cs,
+                          workspace, workspace_bytes))
     return e;
-  const WctLayout L = wct_layout(n, C, HW, true);
+  const WctLayout L = wct_layout(n, C, HWc, HWs, true);
   double* ws = static_cast<double*>(workspace);
   hipStream_t st = as_stream(stream);
   if (int e = wct_closed_form<SRC_F32C>(content, style, nullptr, L, ws, ws + L.tm, ws + L.off,
@@ -795,28 +818,43 @@ extern "C" int rpst_wct_fuse(const float* content, const float* style, float* ou
   return wct_transform<SRC_F32C>(content, out, L, ws, st);
 }
 
+extern "C" int rpst_wct_fuse(const float* content, const float* style, float* out, int n, int C,
+                             int64_t HW, double* residual, void* workspace,
+                             size_t workspace_bytes, rpst_stream_t stream) {
+  return rpst_wct_fuse_cs(content, style, out, n, C, HW, HW, residual, workspace,
+                          workspace_bytes, stream);
+}
+
+extern "C" int rpst_wct_params_cs(const float* content, const float* style, const float* means,
+                                  double* T, double* offset, int n, int C, int64_t HWc,
+                                  int64_t HWs, double* residual, void* workspace,
+                                  size_t workspace_bytes, rpst_stream_t stream) {
+  if (int e = check_entry("wct_params", content && style && T && offset, n, C, HWc, HWs,
+                          {65535, INT_MAX, 0x7fffffffLL, true}, rpst_wct_workspace_size_cs,
+                          workspace, workspace_bytes))
+    return e;
+  RPST_REQUIRE(C <= 1024, "wct_params: C=%d > 1024", C);
+  return wct_closed_form<SRC_F32C>(content, style, means, wct_layout(n, C, HWc, HWs, true),
+                                   static_cast<double*>(workspace), T, offset, residual,
+                                   as_stream(stream));
+}
+
 extern "C" int rpst_wct_params(const float* content, const float* style, const float* means,
                                double* T, double* offset, int n, int C, int64_t HW,
                                double* residual, void* workspace, size_t workspace_bytes,
                                rpst_stream_t stream) {
-  if (int e = check_entry("wct_params", content && style && T && offset, n, C, HW,
-                          {65535, INT_MAX, 0x7fffffffLL, true}, rpst_wct_workspace_size,
-                          workspace, workspace_bytes))
-    return e;
-  RPST_REQUIRE(C <= 1024, "wct_params: C=%d > 1024", C);
-  return wct_closed_form<SRC_F32C>(content, style, means, wct_layout(n, C, HW, true),
-                                   static_cast<double*>(workspace), T, offset, residual,
-                                   as_stream(stream));
+  return rpst_wct_params_cs(content, style, means, T, offset, n, C, HW, HW, residual, workspace,
+                            workspace_bytes, stream);
 }
 
 extern "C" int rpst_whiten_and_color_f64(const double* cF, const double* sF, double* out, int C,
                                          int64_t HW, double* residual, void* workspace,
                                          size_t workspace_bytes, rpst_stream_t stream) {
-  if (int e = check_entry("whiten_and_color", cF && sF && out, 1, C, HW,
-                          {1, 1024, 0x7fffffffLL, false}, rpst_wct_workspace_size, workspace,
+  if (int e = check_entry("whiten_and_color", cF && sF && out, 1, C, HW, HW,
+                          {1, 1024, 0x7fffffffLL, false}, rpst_wct_workspace_size_cs, workspace,
                           workspace_bytes))
     return e;
-  const WctLayout L = wct_layout(1, C, HW, false);
+  const WctLayout L = wct_layout(1, C, HW, HW, false);
   double* ws = static_cast<double*>(workspace);
   hipStream_t st = as_stream(stream);
   if (int e = wct_closed_form<SRC_F64C>(cF, sF, nullptr, L, ws, ws + L.tm, ws + L.off, residual,
@@ -828,11 +866,11 @@ extern "C" int rpst_whiten_and_color_f64(const double* cF, const double* sF, dou
 extern "C" int rpst_whiten_and_color_original_f64(const double* cF, const double* sF,
                                                   double* out, int C, int64_t HW, void* workspace,
                                                   size_t workspace_bytes, rpst_stream_t stream) {
-  if (int e = check_entry("whiten_and_color(original)", cF && sF && out, 1, C, HW,
-                          {1, 1024, 0x7fffffffLL, false}, rpst_wct_workspace_size, workspace,
+  if (int e = check_entry("whiten_and_color(original)", cF && sF && out, 1, C, HW, HW,
+                          {1, 1024, 0x7fffffffLL, false}, rpst_wct_workspace_size_cs, workspace,
                           workspace_bytes))
     return e;
-  const WctLayout L = wct_layout(1, C, HW, false);
+  const WctLayout L = wct_layout(1, C, HW, HW, false);
   double* ws = static_cast<double*>(workspace);
   hipStream_t st = as_stream(stream);
   if (int e = wct_moments<SRC_F64C>(cF, sF, nullptr, L, ws, st)) return e;
@@ -841,14 +879,19 @@ extern "C" int rpst_whiten_and_color_original_f64(const double* cF, const double
 }
 
 // rpst_wct_fuse / rpst_wct_params lay the workspace out for fp32 features
+extern "C" int rpst_wct_status_cs(const void* workspace, int n, int C, int64_t HWc, int64_t HWs,
+                                  int* status, rpst_stream_t stream) {
+  return copy_status("wct_status", workspace, n, C, HWc, HWs, true, status, stream);
+}
+
 extern "C" int rpst_wct_status(const void* workspace, int n, int C, int64_t HW, int* status,
                                rpst_stream_t stream) {
-  return copy_status("wct_status", workspace, n, C, HW, true, status, stream);
+  return rpst_wct_status_cs(workspace, n, C, HW, HW, status, stream);
 }
 
 extern "C" int rpst_whiten_and_color_status(const void* workspace, int C, int64_t HW, int* status,
                                             rpst_stream_t stream) {
-  return copy_status("whiten_and_color_status", workspace, 1, C, HW, false, status, stream);
+  return copy_status("whiten_and_color_status", workspace, 1, C, HW, HW, false, status, stream);
 }
 
 extern "C" int rpst_wct_phase_timing(int on) {
@@ -878,7 +921,7 @@ extern "C" size_t rpst_matrix_power_workspace_size(int n, int batch) {
 extern "C" int rpst_matrix_power_psd_f64(const double* A, double* out, int n, int batch,
                                          int inverse, double* residual, void* workspace,
                                          size_t workspace_bytes, rpst_stream_t stream) {
-  if (int e = check_entry("matrix_power", A && out, batch, n, 2, {65535, 1024, 2, false},
+  if (int e = check_entry("matrix_power", A && out, batch, n, 2, 2, {65535, 1024, 2, false},
                           matrix_power_need, workspace, workspace_bytes))
     return e;
   return matfun_power(A, out, n, batch, inverse, residual, static_cast<double*>(workspace),

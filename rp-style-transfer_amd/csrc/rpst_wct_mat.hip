@@ -10,7 +10,9 @@
 //    X). The 128x128-tile SYRK of rpst_wct.hip staged the rows of each diagonal tile twice
 //    and computed 3/4 of the square; here the executed blocks are (NB+1)/(2 NB) of it and each
 //    staged element feeds NB+1 ... 2 NB blocks. K splits are a function of HW only (bitwise
-//    batch invariance), partials are combined in fixed order by cov_finish_kernel.
+//    batch invariance), partials are combined in fixed order by cov_finish_kernel. A style of
+//    another pixel count than the content runs the two sides as two launches, each with the
+//    splits of its own HW.
 // 2. matfun_kernel: the Newton-Schulz square roots, the products Sc Cs Sc and Ic Mid Ic and the
 //    offset mu_s - T mu_c for every image in one launch. A group of P workgroups (one 64x64
 //    output tile each) works on one matrix at a time; the phases of a matrix are separated by a
@@ -321,13 +323,14 @@ __global__ __launch_bounds__(1024, 1) void cov_syrk16_kernel(CovArgs a) {
 // Cc / Cs / mu64 from the partials: S = sum of the partials of the (r, c) block (upper
 // triangle; the lower one mirrors it), delta_r = (row sum of x - mu32) / HW,
 // cov = (S - HW delta_r delta_c) / (HW - 1) (+ I for the content matrices, wct_rp.py:89).
+// nz matrices of HW pixels each, the first nc of them content ones (Cc), the rest style (Cs).
 __global__ void cov_finish_kernel(const double* __restrict__ part, const double* __restrict__ rsum,
                                   const float* __restrict__ mu32, double* __restrict__ Cc,
-                                  double* __restrict__ Cs, double* __restrict__ mu64, int n, int C,
-                                  int NB, int PS, int ksplit, int64_t HW) {
+                                  double* __restrict__ Cs, double* __restrict__ mu64, int nz,
+                                  int nc, int C, int NB, int PS, int ksplit, int64_t HW) {
   const int64_t cc = (int64_t)C * C;
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= 2 * n * cc) return;
+  if (i >= nz * cc) return;
   const int z = (int)(i / cc);
   const int rem = (int)(i - (int64_t)z * cc);
   const int r = rem / C, c = rem - r * C;
@@ -348,23 +351,23 @@ __global__ void cov_finish_kernel(const double* __restrict__ part, const double*
   }
   const double dr = sr / (double)HW, dc = sc / (double)HW;
   const double cov = (s - (double)HW * dr * dc) / (double)(HW - 1);
-  if (z < n) Cc[(int64_t)z * cc + rem] = cov + (r == c ? 1.0 : 0.0);
-  else Cs[(int64_t)(z - n) * cc + rem] = cov;
+  if (z < nc) Cc[(int64_t)z * cc + rem] = cov + (r == c ? 1.0 : 0.0);
+  else Cs[(int64_t)(z - nc) * cc + rem] = cov;
   if (c == 0) mu64[(int64_t)z * C + r] = (double)mu32[(int64_t)z * C + r] + dr;
 }
 
 bool cov_v2_supported(int C) { return C >= 1 && C <= 256; }
 
-// The work area of cov_v2, stated once. k per split: HW / 8 rounded up to whole 32-deep
-// stages (512^2: 32768), so every shape fills 8 x 2n workgroups (C = 128 at 256^2 ran 2
-// splits, C = 256 at 128^2 one); a function of HW only, so an image's bits never depend on
-// its batch.
+// The work area of one cov_side launch set over nz matrices of HW pixels, stated once. k per
+// split: HW / 8 rounded up to whole 32-deep stages (512^2: 32768), so every shape fills
+// 8 x nz workgroups (C = 128 at 256^2 ran 2 splits, C = 256 at 128^2 one); a function of HW
+// only, so an image's bits never depend on its batch.
 struct CovLayout {
   int NB, nblk, kper, ksplit, PS;  // PS: partials per matrix (K splits x k groups)
   size_t rsum, total;              // doubles: the partials at 0, the row sums after them
 };
 
-static CovLayout cov_layout(int n, int C, int64_t HW) {
+static CovLayout cov_layout(int nz, int C, int64_t HW) {
   CovLayout L{};
   L.NB = cov_nb(C);
   L.nblk = L.NB * (L.NB + 1) / 2;
@@ -372,48 +375,65 @@ static CovLayout cov_layout(int n, int C, int64_t HW) {
   L.kper = (int)((k + kCovBK - 1) / kCovBK * kCovBK);
   L.ksplit = (int)((HW + L.kper - 1) / L.kper);
   L.PS = L.ksplit * cov_kg(L.NB);
-  L.rsum = (size_t)2 * n * L.PS * L.nblk * 256;
-  L.total = L.rsum + (size_t)2 * n * L.ksplit * C;
+  L.rsum = (size_t)nz * L.PS * L.nblk * 256;
+  L.total = L.rsum + (size_t)nz * L.ksplit * C;
   return L;
 }
 
-size_t cov_v2_work_doubles(int n, int C, int64_t HW) { return cov_layout(n, C, HW).total; }
+// equal pixel counts: one area over the 2n matrices; else the content side's, then the style's
+size_t cov_v2_work_doubles(int n, int C, int64_t HWc, int64_t HWs) {
+  if (HWc == HWs) return cov_layout(2 * n, C, HWc).total;
+  return cov_layout(n, C, HWc).total + cov_layout(n, C, HWs).total;
+}
 
 template <bool VEC>
-static void cov_launch(int NB, const CovArgs& a, hipStream_t st) {
-  const dim3 grid(a.ksplit, 2 * a.n);
+static void cov_launch(int NB, const CovArgs& a, int nz, hipStream_t st) {
+  const dim3 grid(a.ksplit, nz);
   if (NB == 4) cov_syrk_kernel<4, VEC><<<grid, 512, 0, st>>>(a);
   else if (NB == 8) cov_syrk_kernel<8, VEC><<<grid, 512, 0, st>>>(a);
   else cov_syrk16_kernel<VEC><<<grid, 1024, 0, st>>>(a);
 }
 
-int cov_v2(const float* cF, const float* sF, const float* mu32, int n, int C, int64_t HW,
-           double* Cc, double* Cs, double* mu64, double* work, hipStream_t st) {
-  if (!cov_v2_supported(C) || HW < 2 || 2 * n > 65535) {
-    set_error("cov_v2: unsupported shape n=%d C=%d HW=%lld", n, C, (long long)HW);
-    return RPST_EINVAL;
-  }
-  const CovLayout L = cov_layout(n, C, HW);
+// The SYRK and its finish over nz matrices of HW pixels: the first nc read X0 and give Cc, the
+// other nz - nc read X1 and give Cs. mu32 / mu64: this launch set's nz x C rows.
+static int cov_side(const float* X0, const float* X1, const float* mu32, int nz, int nc, int C,
+                    int64_t HW, double* Cc, double* Cs, double* mu64, double* work,
+                    hipStream_t st) {
+  const CovLayout L = cov_layout(nz, C, HW);
   CovArgs a{};
-  a.X0 = cF;
-  a.X1 = sF;
+  a.X0 = X0;
+  a.X1 = X1;
   a.mu32 = mu32;
-  a.n = n;
+  a.n = nc;
   a.C = C;
   a.HW = HW;
   a.ksplit = L.ksplit;
   a.kper = L.kper;
   a.part = work;
   a.rsum = work + L.rsum;
-  const bool vec = HW % 4 == 0 && (reinterpret_cast<uintptr_t>(cF) & 15) == 0 &&
-                   (reinterpret_cast<uintptr_t>(sF) & 15) == 0;
-  if (vec) cov_launch<true>(L.NB, a, st);
-  else cov_launch<false>(L.NB, a, st);
+  auto al = [](const float* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; };
+  const bool vec = HW % 4 == 0 && (nc == 0 || al(X0)) && (nc == nz || al(X1));
+  if (vec) cov_launch<true>(L.NB, a, nz, st);
+  else cov_launch<false>(L.NB, a, nz, st);
   if (int e = launch_status("cov_syrk_kernel")) return e;
-  const int64_t tot = (int64_t)2 * n * C * C;
+  const int64_t tot = (int64_t)nz * C * C;
   cov_finish_kernel<<<(unsigned)((tot + 255) / 256), 256, 0, st>>>(
-      a.part, a.rsum, mu32, Cc, Cs, mu64, n, C, L.NB, L.PS, a.ksplit, HW);
+      a.part, a.rsum, mu32, Cc, Cs, mu64, nz, nc, C, L.NB, L.PS, a.ksplit, HW);
   return launch_status("cov_finish_kernel");
+}
+
+int cov_v2(const float* cF, const float* sF, const float* mu32, int n, int C, int64_t HWc,
+           int64_t HWs, double* Cc, double* Cs, double* mu64, double* work, hipStream_t st) {
+  if (!cov_v2_supported(C) || HWc < 2 || HWs < 2 || 2 * n > 65535) {
+    set_error("cov_v2: unsupported shape n=%d C=%d HW=%lld/%lld", n, C, (long long)HWc,
+              (long long)HWs);
+    return RPST_EINVAL;
+  }
+  if (HWc == HWs) return cov_side(cF, sF, mu32, 2 * n, n, C, HWc, Cc, Cs, mu64, work, st);
+  const size_t nC = (size_t)n * C;
+  if (int e = cov_side(cF, nullptr, mu32, n, n, C, HWc, Cc, nullptr, mu64, work, st)) return e;
+  return cov_side(nullptr, sF, mu32 + nC, n, 0, C, HWs, nullptr, Cs, mu64 + nC,
+                  work + cov_layout(n, C, HWc).total, st);
 }
 
 // ======================= 2. persistent matrix functions ===================================

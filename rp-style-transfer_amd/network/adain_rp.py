@@ -46,7 +46,11 @@ def adain_rp_fused(encoder, decoder, content, style):
 
 
 def encode_both(encoder, content, style):
-    """Run a shared encoder over content and style in one pass of 2N images."""
+    """Run a shared encoder over content and style in one pass of 2N images; a style of
+    another size than the content takes a pass of its own (the reference encodes the two
+    separately, adain_rp.py / wct_rp.py test())."""
+    if content.shape != style.shape:
+        return encoder(content), encoder(style)
     n = content.shape[0]
     feats = encoder(torch.cat([content, style], dim=0))
     return feats[:n], feats[n:]

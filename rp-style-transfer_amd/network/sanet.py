@@ -7,6 +7,8 @@
                          B operand is staged, then out_conv with the residual fused
   Transform.forward   sanet.py:148-149 -> merge_conv reads a + up2(b) in its loader
   SAModel.test        sanet.py:238-246 -> VGG relu1_1..5_1 over [style; content] once
+                         (a style of another size than the content: one pass each; the
+                         attention takes HWc queries and HWs keys)
   AdaptiveSANet       sanet.py:100-138: cosine affinity GEMM, the
                       AEA clamp MLP as a GEMM with a LeakyReLU epilogue + head kernel, and
                       the clamped attention formed while S is staged into the last GEMM
@@ -85,6 +87,7 @@ class SANet(nn.Module):
         self.out_conv = nn.Conv2d(in_planes, in_planes, (1, 1))
 
     def forward(self, content, style):
+        """content (B,C,h,w), style (B,C,h',w') of any size -> (B,C,h,w)."""
         F = plan.conv(self.f, mean_variance_norm(content))
         G = plan.conv(self.g, mean_variance_norm(style))
         H = plan.conv(self.h, style)
@@ -221,9 +224,13 @@ class SAModel(nn.Module):
         self.eval()
         with torch.no_grad():
             n = content.shape[0]
-            feats = _encode_pair_intermediate(self, style, content)
-            s4, c4 = feats[3][:n], feats[3][n:]
-            s5, c5 = feats[4][:n], feats[4][n:]
+            if content.shape == style.shape:
+                feats = _encode_pair_intermediate(self, style, content)
+                s4, c4 = feats[3][:n], feats[3][n:]
+                s5, c5 = feats[4][:n], feats[4][n:]
+            else:  # a style of another size: one encoder pass each (sanet.py:240-242)
+                _, _, _, s4, s5 = self.encode_with_intermediate(style)
+                _, _, _, c4, c5 = self.encode_with_intermediate(content)
             fusion = self.transform(c4, s4, c5, s5)
             stylized = self.decoder(fusion)
             self.train()

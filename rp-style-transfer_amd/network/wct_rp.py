@@ -51,11 +51,18 @@ def wct_rp_fused(encoder, decoder, content, style, model=None):
     (fp64), and the decoder's first conv reads T_n x + c_n through per-image folded weights
     (rpst_conv2d_mix), so the fused feature T (cF - mu_c) + mu_s is never written."""
     n = content.shape[0]
-    assert content.size() == style.size()
-    feats, mean, _ = plan.run(plan.of(encoder), content, x2=style, stats_last=True)
-    T, c, res, st = ops.wct_params(feats[:n], feats[n:], means=mean.reshape(2 * n, -1),
-                                   status=True)
-    out = plan.run(plan.of(decoder), feats[:n], first_mix=(T, c))
+    if content.shape == style.shape:
+        feats, mean, _ = plan.run(plan.of(encoder), content, x2=style, stats_last=True)
+        cf, sf, means = feats[:n], feats[n:], mean.reshape(2 * n, -1)
+    else:
+        # a style of another size: one encoder pass each, each side's row means from its own
+        # epilogue (content rows first)
+        ops._pair_shapes("WCTRPNet.test", content, style)
+        cf, mc, _ = plan.run(plan.of(encoder), content, stats_last=True)
+        sf, ms, _ = plan.run(plan.of(encoder), style, stats_last=True)
+        means = torch.cat([mc.reshape(n, -1), ms.reshape(n, -1)], dim=0)
+    T, c, res, st = ops.wct_params(cf, sf, means=means, status=True)
+    out = plan.run(plan.of(decoder), cf, first_mix=(T, c))
     # st: per-image status on the device: an image whose iteration did not converge
     # (non-finite features), or whose persistent launch timed out, has NaN T and c, so its
     # output is NaN; checked after this call's launches are queued (_status)
@@ -107,7 +114,13 @@ class WCTRPNet(BaseNet):
 
     def whiten_and_color(self, cF, sF, method='closed-form'):
         """cF, sF: (C, HW) fp64 device tensors -> (C, HW) fp64; method 'closed-form' (Lu et
-        al., wct_rp.py:102-111) or 'original' (Li et al., :96-101)."""
+        al., wct_rp.py:102-111) or 'original' (Li et al., :96-101). The fp64 entry takes one
+        pixel count: matrices of different widths raise ValueError (fuse() and test() take a
+        style of another size)."""
+        if cF.dim() != 2 or sF.dim() != 2 or cF.shape != sF.shape:
+            raise ValueError(f"WCTRPNet.whiten_and_color: cF {tuple(cF.shape)} and sF "
+                             f"{tuple(sF.shape)} must be (C, HW) matrices of one shape; a style "
+                             "of another size goes through fuse()")
         out, st = ops.whiten_and_color(cF, sF, method=method, status=True)
         _status(self, st, "WCTRPNet.whiten_and_color")
         return out
@@ -156,7 +169,8 @@ class WCTRPNet(BaseNet):
                     'decoder': self.rp_decoder.state_dict()}, save_path)
 
     def fuse(self, content_feats, style_feats):
-        """Per-image closed-form WCT, all images of the batch in one set of launches."""
+        """Per-image closed-form WCT, all images of the batch in one set of launches; the
+        style features may have another spatial size than the content's."""
         out, st = ops.wct_fuse(content_feats, style_feats, status=True)
         _status(self, st, "WCTRPNet.fuse")
         return out

@@ -480,9 +480,19 @@ def adain_rp_losses(model, content: torch.Tensor, style: torch.Tensor):
                    list(model.rp_shared_encoder.parameters()) + list(model.rp_decoder.parameters()))
 
 
+def _same_size(what: str, content: torch.Tensor, style: torch.Tensor) -> None:
+    """The training steps run content and style as one batch: a style of another size is an
+    inference feature (test()), refused here at entry."""
+    if content.shape != style.shape:
+        raise ValueError(f"rpst.autograd.{what}: content {tuple(content.shape)} and style "
+                         f"{tuple(style.shape)} must have one shape (a style of another size is "
+                         "supported by test() only)")
+
+
 def wct_rp_losses(model, content: torch.Tensor, style: torch.Tensor):
     """WCTRPNet.forward with autograd: the loss dict and total_loss, differentiable w.r.t.
     the RP decoder parameters (the only ones the reference's graph reaches)."""
+    _same_size("wct_rp_losses", content, style)
     return _losses(_WCTRPStep, model, content, style, list(model.rp_decoder.parameters()))
 
 
@@ -702,6 +712,7 @@ def samodel_losses(model, content: torch.Tensor, style: torch.Tensor):
     differentiable w.r.t. the transform and decoder parameters. AdaptiveSAModel.forward
     (sanet.py:347-382: the same losses around an AdaptiveTransform) runs through the same
     step, its AdaptiveSANets (and their f_psi MLPs) on rpst_adaptive_attention_backward."""
+    _same_size("samodel_losses", content, style)
     return _losses(_SAModelStep, model, content, style,
                    list(model.transform.parameters()) + list(model.decoder.parameters()),
                    extra=('l_identity1', 'l_identity2'))

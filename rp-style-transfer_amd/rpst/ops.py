@@ -810,26 +810,40 @@ def conv_algorithm(cout: int, cin: int, hs: int, ws: int, ksize: int, in_op: int
 SANET_WS_CAP = 8 << 30
 
 
+def _pair_shapes(what: str, content: torch.Tensor, style: torch.Tensor) -> None:
+    """content (n, C, h, w) and style (n, C, h', w'): the batch and the channels are shared,
+    the spatial size is each one's own. ValueError names both shapes."""
+    if content.dim() != 4 or style.dim() != 4 or content.shape[:2] != style.shape[:2]:
+        raise ValueError(f"rpst: {what}: content {tuple(content.shape)} and style "
+                         f"{tuple(style.shape)} must be 4-d and share their batch and channels "
+                         "(only the spatial size may differ)")
+
+
 def sanet_attention(F: torch.Tensor, G: torch.Tensor, H: torch.Tensor) -> torch.Tensor:
-    """SANet core (sanet.py:86-94): O = H softmax(F^T G)^T per image, (B,C,h,w)."""
-    assert F.dim() == 4 and F.shape == G.shape == H.shape
+    """SANet core (sanet.py:86-94): O = H softmax(F^T G)^T per image. F (B,C,h,w) comes from
+    the content, G and H (B,C,h',w') from the style, whose size may differ; O is F-shaped."""
+    if G.shape != H.shape:
+        raise ValueError(f"rpst: sanet_attention: G {tuple(G.shape)} and H {tuple(H.shape)} "
+                         "must have one shape")
+    _pair_shapes("sanet_attention", F, G)
     _check(F, G, H)
     F, G, H = _c(F), _c(G), _c(H)
     B, C, h, w = F.shape
-    hw = h * w
+    hw, hwk = h * w, G.shape[2] * G.shape[3]
     out = torch.empty_like(F)
     lib = _lib.load()
     # flash path (S never written): no workspace, the whole batch in one launch
-    per_img = lib.rpst_sanet_attention_workspace_size_c(1, C, hw)
+    per_img = lib.rpst_sanet_attention_qk_workspace_size_c(1, C, hw, hwk)
     chunk = B if per_img == 0 else max(1, min(B, SANET_WS_CAP // per_img))
-    ws_bytes = lib.rpst_sanet_attention_workspace_size_c(chunk, C, hw)
+    ws_bytes = lib.rpst_sanet_attention_qk_workspace_size_c(chunk, C, hw, hwk)
     ws = _lib.scratch(ws_bytes, F)
+    name = f"HW{hw}" if hw == hwk else f"HW{hw}x{hwk}"
     for b0 in range(0, B, chunk):
         nb = min(chunk, B - b0)
-        with _traced(f"sanet_attention C{C} HW{hw} N{nb}", 4.0 * nb * hw * hw * C, 0.0):
-            _lib.call("rpst_sanet_attention", F[b0].data_ptr(), G[b0].data_ptr(),
-                      H[b0].data_ptr(), out[b0].data_ptr(), nb, C, hw, ws.data_ptr(), ws_bytes,
-                      _stream(F))
+        with _traced(f"sanet_attention C{C} {name} N{nb}", 4.0 * nb * hw * hwk * C, 0.0):
+            _lib.call("rpst_sanet_attention_qk", F[b0].data_ptr(), G[b0].data_ptr(),
+                      H[b0].data_ptr(), out[b0].data_ptr(), nb, C, hw, hwk, ws.data_ptr(),
+                      ws_bytes, _stream(F))
     return out
 
 
@@ -1016,29 +1030,37 @@ class WCTStatusWatch:
         check_wct_status(host, what)
 
 
-def _wct_status(ws: torch.Tensor, n: int, C: int, hw: int, dev) -> torch.Tensor:
+def _wct_status(ws: torch.Tensor, n: int, C: int, hwc: int, hws: int, dev) -> torch.Tensor:
     st = torch.empty(n, device=dev, dtype=torch.int32)
-    _lib.call("rpst_wct_status", ws.data_ptr(), n, C, hw, st.data_ptr(), _stream(st))
+    _lib.call("rpst_wct_status_cs", ws.data_ptr(), n, C, hwc, hws, st.data_ptr(), _stream(st))
     return st
 
 
+def _px(hwc: int, hws: int) -> str:  # trace name of a WCT launch's pixel counts
+    return f"{hwc}px" if hwc == hws else f"{hwc}x{hws}px"
+
+
 def wct_fuse(content: torch.Tensor, style: torch.Tensor, status: bool = False):
-    """WCTRPNet.fuse (wct_rp.py:157-166): (n,C,h,w) fp32 -> fp32, fp64 internals. The matrix
-    functions iterate on the device (no host synchronisation); an image whose Newton-Schulz
-    iteration cannot converge (non-finite features) or whose persistent launch timed out comes
-    out NaN. status=True also returns the (n,) int32 per-image status (rpst_wct_status)."""
-    assert content.dim() == 4 and content.shape == style.shape
+    """WCTRPNet.fuse (wct_rp.py:157-166): content (n,C,h,w), style (n,C,h',w') fp32 -> fp32 of
+    the content's shape, fp64 internals; the style may have another size (each side is
+    flattened on its own). The matrix functions iterate on the device (no host
+    synchronisation); an image whose Newton-Schulz iteration cannot converge (non-finite
+    features) or whose persistent launch timed out comes out NaN. status=True also returns the
+    (n,) int32 per-image status (rpst_wct_status)."""
+    _pair_shapes("wct_fuse", content, style)
     _check(content, style)
     content, style = _c(content), _c(style)
     n, C, h, w = content.shape
+    hwc, hws = h * w, style.shape[2] * style.shape[3]
     out = torch.empty_like(content)
     res = torch.empty(2 * n, device=content.device, dtype=torch.float64)
-    ws, nbytes = _lib.workspace("wct", content, n, C, h * w)
-    with _traced(f"wct_fuse C{C} {h * w}px N{n}", 6.0 * n * C * C * h * w, 0.0):
-        _lib.call("rpst_wct_fuse", content.data_ptr(), style.data_ptr(), out.data_ptr(), n, C,
-                  h * w, res.data_ptr(), ws.data_ptr(), nbytes, _stream(content))
+    nbytes = _lib.load().rpst_wct_workspace_size_cs(n, C, hwc, hws)
+    ws = _lib.scratch(nbytes, content)
+    with _traced(f"wct_fuse C{C} {_px(hwc, hws)} N{n}", 2.0 * n * C * C * (2 * hwc + hws), 0.0):
+        _lib.call("rpst_wct_fuse_cs", content.data_ptr(), style.data_ptr(), out.data_ptr(), n, C,
+                  hwc, hws, res.data_ptr(), ws.data_ptr(), nbytes, _stream(content))
     if status:
-        return out, _wct_status(ws, n, C, h * w, content.device)
+        return out, _wct_status(ws, n, C, hwc, hws, content.device)
     return out
 
 
@@ -1047,24 +1069,30 @@ def wct_params(content: torch.Tensor, style: torch.Tensor, means: Optional[torch
     """The closed-form WCT matrices of every image without the product (wct_rp.py:85-109):
     returns (T (n,C,C) fp64, offset c = mu_s - T mu_c (n,C) fp64, residual (2n,) fp64), plus
     the (n,) int32 status with status=True (rpst_wct_status: 0 valid; NaN T / c otherwise).
+    content (n,C,h,w) and style (n,C,h',w') share n and C only.
     means: optional (2n, C) fp32 row means, content rows first (the encoder epilogue's)."""
-    assert content.dim() == 4 and content.shape == style.shape
+    _pair_shapes("wct_params", content, style)
     _check(content, style, means)
     content, style = _c(content), _c(style)
     n, C, h, w = content.shape
+    hwc, hws = h * w, style.shape[2] * style.shape[3]
     if means is not None:
         means = _c(means)
-        assert means.numel() == 2 * n * C
+        if means.numel() != 2 * n * C:
+            raise ValueError(f"rpst: wct_params: means {tuple(means.shape)} is not (2n, C) = "
+                             f"({2 * n}, {C})")
     T = torch.empty((n, C, C), device=content.device, dtype=torch.float64)
     c = torch.empty((n, C), device=content.device, dtype=torch.float64)
     res = torch.empty(2 * n, device=content.device, dtype=torch.float64)
-    ws, nbytes = _lib.workspace("wct", content, n, C, h * w)
-    with _traced(f"wct_params C{C} {h * w}px N{n}", 2.0 * n * C * (C + 1) * h * w, 0.0):
-        _lib.call("rpst_wct_params", content.data_ptr(), style.data_ptr(), _ptr(means),
-                  T.data_ptr(), c.data_ptr(), n, C, h * w, res.data_ptr(), ws.data_ptr(), nbytes,
-                  _stream(content))
+    nbytes = _lib.load().rpst_wct_workspace_size_cs(n, C, hwc, hws)
+    ws = _lib.scratch(nbytes, content)
+    with _traced(f"wct_params C{C} {_px(hwc, hws)} N{n}", n * C * (C + 1) * (hwc + hws) * 1.0,
+                 0.0):
+        _lib.call("rpst_wct_params_cs", content.data_ptr(), style.data_ptr(), _ptr(means),
+                  T.data_ptr(), c.data_ptr(), n, C, hwc, hws, res.data_ptr(), ws.data_ptr(),
+                  nbytes, _stream(content))
     if status:
-        return T, c, res, _wct_status(ws, n, C, h * w, content.device)
+        return T, c, res, _wct_status(ws, n, C, hwc, hws, content.device)
     return T, c, res
 
 
