@@ -257,6 +257,43 @@ int rpst_conv7(const float* input, const float* input2, const float* packed_weig
                int pad_mode, int act, int out_channel_offset, int out_channels_total,
                rpst_stream_t stream);
 
+/* ---- bf16: opt-in reduced-precision 3x3 conv (stride 1, pad 1) on the bf16 MFMA ----
+ * A second precision for inference, chosen per call: no thread switch, no environment
+ * variable, and nothing above changes with it. Activations stay fp32 in memory (input and
+ * output). The tile loader forms the fp32 input value (under RPST_IN_ADAIN the affine of
+ * rpst_conv2d first) and rounds it once, to nearest even, to bf16; the weights are rounded the
+ * same way once, by rpst_conv2d_bf16_pack. Products of two bf16 values are exact in fp32;
+ * accumulation is fp32 in a fixed K order without atomics; bias, activation and statistics are
+ * fp32 / fp64 as for rpst_conv2d_stats. Image n's output bits do not depend on the batch.
+ * Runs: ksize 3, Cin a multiple of 16 in [16, 256], Cout >= 16, pad_mode RPST_PAD_ZERO /
+ * RPST_PAD_REFLECT (H, W >= 2), in_op RPST_IN_NONE / RPST_IN_ADAIN, act RPST_ACT_*, any
+ * H, W >= 1 with one image's input below 2 GiB. Everything else: RPST_EINVAL.
+ *   rpst_conv2d_bf16_supports (host only): 1 for a layer rpst_conv2d_bf16 runs AND runs faster
+ *     than rpst_conv2d's fp32 kernel (measured at 512^2: Cout >= 64; the rule and its numbers
+ *     stand beside the function), else 0. The plans lower a conv to bf16 only where it says 1.
+ *   packed: the bf16 image [Cin/16][9 taps][Cout_pad][16] of fp32 (Cout,Cin,3,3) weights,
+ *     rpst_conv2d_bf16_packed_size bytes (0 for an unsupported layer); Cout_pad as rpst_conv7.
+ *   input2 (may be NULL): images n >= n1 are read from it, as rpst_conv2d_pair (RPST_IN_NONE
+ *     only; n1 is ignored without it). aux: the AdaIN parameters of rpst_conv2d, non-NULL
+ *     exactly under RPST_IN_ADAIN. bias may be NULL.
+ *   mean / std_out (both or neither; may be NULL): calc_mean_std of `out` from the epilogue
+ *     as rpst_conv2d_stats returns it; then store_n in [1, N] and images n >= store_n are not
+ *     written, only reduced (rpst_conv2d_stats_store), and the workspace holds
+ *     rpst_conv2d_bf16_workspace_size bytes. Without statistics store_n is N (or 0) and the
+ *     workspace is unused.
+ *   rpst_conv2d_bf16_grid_threads: total threads of the launch, for profilers. */
+int rpst_conv2d_bf16_supports(int Cout, int Cin, int ksize, int pad_mode, int in_op);
+size_t rpst_conv2d_bf16_packed_size(int Cout, int Cin);
+int rpst_conv2d_bf16_pack(const float* weight, void* packed, int Cout, int Cin,
+                          rpst_stream_t stream);
+size_t rpst_conv2d_bf16_workspace_size(int N, int Cin, int H, int W, int Cout);
+int rpst_conv2d_bf16(const float* input, const float* input2, int n1, const float* aux,
+                     const void* packed, const float* bias, float* out, int N, int Cin, int H,
+                     int W, int Cout, int pad_mode, int in_op, int act, float* mean,
+                     float* std_out, float eps, int store_n, void* workspace,
+                     size_t workspace_bytes, rpst_stream_t stream);
+int64_t rpst_conv2d_bf16_grid_threads(int N, int Cin, int H, int W, int Cout);
+
 /* ---- LDMSAdaINRPNet4 (`network: ld_adain4`, adain_rp.py:711-819): coarse pyramid + concat ----
  * Nearest rule of F.interpolate(x, size) in its default mode, per axis:
  *   src = min((int)floorf(dst * ((float)in / (float)out)), in - 1), the product in fp32.

@@ -69,6 +69,11 @@ struct ConvTiling {
   bool stat_t;
 };
 
+// Merge the [n][co][partial] (mean, M2) partials of a statistics epilogue (P per plane, laid
+// out by t.stat_*) into calc_mean_std, in fp64 (stat_merge_kernel, rpst_conv.hip).
+int conv_stat_merge(const float2* part, float* mean, float* std_out, int N, int Cout, int P,
+                    int tiles_x, const ConvTiling& t, int H, int W, float eps, hipStream_t st);
+
 // image n's input planes (block-uniform n)
 __device__ __forceinline__ const float* conv_in_img(const ConvArgs& a, int n, int64_t per) {
   return (a.in2_from > 0 && n >= a.in2_from) ? a.in2 + (int64_t)(n - a.in2_from) * per

@@ -1239,6 +1239,17 @@ extern "C" size_t rpst_conv2d_stats_workspace_size(int N, int Cin, int Hs, int W
          fold_bytes(N, Cin, Hs, Ws, Cout, ksize, in_op, m);
 }
 
+namespace rpst {
+// (declared in rpst_conv.h: rpst_conv_bf16.hip's statistics epilogue ends in the same merge)
+int conv_stat_merge(const float2* part, float* mean, float* std_out, int N, int Cout, int P,
+                    int tiles_x, const ConvTiling& t, int H, int W, float eps, hipStream_t st) {
+  const int planes = N * Cout;
+  stat_merge_kernel<<<(planes + 3) / 4, 256, 0, st>>>(part, mean, std_out, planes, P, tiles_x,
+                                                      t.stat_wn, t.stat_nt, t.stat_tw, H, W, eps);
+  return launch_status("stat_merge_kernel");
+}
+}  // namespace rpst
+
 // the partials a statistics launch left in r.stat_part -> calc_mean_std
 static int stat_merge(const ConvReq& r, const ConvArgs& a, const ConvPlan& p, float* mean,
                       float* std_out, float eps) {
@@ -1249,11 +1260,8 @@ static int stat_merge(const ConvReq& r, const ConvArgs& a, const ConvPlan& p, fl
         a.H, a.W, eps);
     return launch_status("stat_merge_t_kernel");
   }
-  const int planes = r.N * r.Cout;
-  stat_merge_kernel<<<(planes + 3) / 4, 256, 0, r.st>>>(part, mean, std_out, planes, a.stat_P,
-                                                        a.tiles_x, p.t.stat_wn, p.t.stat_nt,
-                                                        p.t.stat_tw, a.H, a.W, eps);
-  return launch_status("stat_merge_kernel");
+  return conv_stat_merge(part, mean, std_out, r.N, r.Cout, a.stat_P, a.tiles_x, p.t, a.H, a.W,
+                         eps, r.st);
 }
 
 static int conv2d_stats_impl(ConvReq r, float* mean, float* std_out, float eps, void* workspace,

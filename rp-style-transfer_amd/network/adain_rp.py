@@ -17,6 +17,7 @@ from rpst import ops, plan
 from rpst.plan import KernelSequential
 
 from .base import (BaseNet, Conv2dBlock, SourceNet, StackType,  # noqa: F401 (star exports)
+                   config_precision,
                    adaptive_instance_normalization, build_decrease_depth_rp_blocks,
                    build_increase_depth_rp_blocks, calc_mean_std, masked_adain_batch, mse,
                    rp_constant_conv_blocks, segment_maps,
@@ -30,19 +31,22 @@ FUSED_ADAIN = os.environ.get("RPST_FUSE_ADAIN", "1") != "0"
 STORE_ALL = os.environ.get("RPST_ADAIN_STORE_ALL", "0") == "1"
 
 
-def adain_rp_fused(encoder, decoder, content, style):
+def adain_rp_fused(encoder, decoder, content, style, precision="fp32"):
     """enc -> AdaIN -> dec with AdaIN fused into its neighbours (adain_rp.py:94-101):
     the encoder's last conv emits calc_mean_std of its output from its epilogue, and the
     decoder's first conv applies ((c - mu_c)/sigma_c)*sigma_s + mu_s while loading its
     input tile, so the AdaIN feature is never written to HBM. The style half of the encoder
     output is consumed only through its statistics: that conv writes the content half alone
-    (store_n = n; adain_rp.py:94-101 reads style_feat only via calc_mean_std)."""
+    (store_n = n; adain_rp.py:94-101 reads style_feat only via calc_mean_std).
+    precision "bf16": both plans send the conv steps ops.conv2d_bf16_supports accepts to the
+    bf16 kernel (plan.lower)."""
     n = content.shape[0]
     assert content.size() == style.size()
     feats, mean, std = plan.run(plan.of(encoder), content, x2=style, stats_last=True,
-                                store_n=None if STORE_ALL else n)
+                                store_n=None if STORE_ALL else n, precision=precision)
     aux = ops.adain_params(mean[:n], std[:n], mean[n:], std[n:])
-    return plan.run(plan.of(decoder), feats[:n], first_aux=aux, first_in_op=ops.IN_ADAIN)
+    return plan.run(plan.of(decoder), feats[:n], first_aux=aux, first_in_op=ops.IN_ADAIN,
+                    precision=precision)
 
 
 def encode_both(encoder, content, style):
@@ -61,6 +65,10 @@ class AdaINRPNet(BaseNet):
         super().__init__()
         enc_layers = list(vgg_encoder.children())
         self.config = config
+        # test() alone reads it (adain_rp_fused); forward() and training stay fp32. The
+        # subclasses have no bf16 path: they raise here
+        self.precision = config_precision(config, type(self).__name__,
+                                          bf16_ok=type(self) is AdaINRPNet)
         self.enc_1 = KernelSequential(*enc_layers[:4])    # input -> relu1_1
         self.enc_2 = KernelSequential(*enc_layers[4:11])  # relu1_1 -> relu2_1
         self.enc_3 = KernelSequential(*enc_layers[11:18])  # relu2_1 -> relu3_1
@@ -103,7 +111,11 @@ class AdaINRPNet(BaseNet):
     def test(self, content, style, iterations=0, bid=0, c_mask_path=None, s_mask_path=None):
         with torch.no_grad():
             if type(self).fuse is AdaINRPNet.fuse and FUSED_ADAIN:
-                return adain_rp_fused(self.rp_shared_encoder, self.rp_decoder, content, style)
+                return adain_rp_fused(self.rp_shared_encoder, self.rp_decoder, content, style,
+                                      self.precision)
+            if self.precision != "fp32":
+                raise NotImplementedError("AdaINRPNet: precision 'bf16' runs on the fused "
+                                          "test() path only (RPST_FUSE_ADAIN=0 disables it)")
             content_feat, style_feat = encode_both(self.rp_shared_encoder, content, style)
             fusion_feat = self.fuse(content_feat, style_feat)
             return self.rp_decoder(fusion_feat)

@@ -218,6 +218,20 @@ def adaptive_instance_normalization(content_feat, style_feat):
     return ops.adaptive_instance_normalization(content_feat, style_feat)
 
 
+def config_precision(config, owner, bf16_ok=False) -> str:
+    """The model's `precision` key: "fp32" (the default, and what every model computes in)
+    or "bf16", the opt-in reduced-precision inference of AdaINRPNet.test() (rpst_conv2d_bf16).
+    Any other value is a ValueError; "bf16" on a model without that path a
+    NotImplementedError at construction, never a silent fp32 run."""
+    precision = config.get("precision", "fp32")
+    if precision not in ("fp32", "bf16"):
+        raise ValueError(f"{owner}: precision must be 'fp32' or 'bf16', got {precision!r}")
+    if precision == "bf16" and not bf16_ok:
+        raise NotImplementedError(
+            f"{owner}: precision 'bf16' is implemented for AdaINRPNet.test() only")
+    return precision
+
+
 class BaseNet(nn.Module):
     """Abstract model API of the reference (base.py:533-559)."""
 
@@ -313,6 +327,7 @@ class SourceNet(BaseNet):
         super(BaseNet, self).__init__()
         enc_layers = list(vgg_encoder.children())
         self.config = config
+        config_precision(config, type(self).__name__)
         self.begin = 0
         self.enc_1 = KernelSequential(*enc_layers[:4])  # input -> relu1_1
         self.enc_2 = KernelSequential(*enc_layers[4:11])  # relu1_1 -> relu2_1

@@ -23,7 +23,7 @@ import torch.nn as nn
 from rpst import ops, plan
 from rpst.plan import KernelSequential
 
-from .base import BaseNet, _make_decoder, calc_mean_std, mse
+from .base import BaseNet, _make_decoder, calc_mean_std, config_precision, mse
 
 
 def mean_variance_norm(feat):
@@ -186,6 +186,7 @@ class SAModel(nn.Module):
     def __init__(self, config, encoder, start_iter, img_size):
         super().__init__()
         self.config = config
+        config_precision(config, type(self).__name__)
         enc_layers = list(encoder.children())[:44]
         self.enc_1 = KernelSequential(*enc_layers[:4])      # input -> relu1_1
         self.enc_2 = KernelSequential(*enc_layers[4:11])    # relu1_1 -> relu2_1
@@ -282,6 +283,7 @@ class AdaptiveSAModel(BaseNet):
     def __init__(self, config, encoder, start_iter, img_size):
         super().__init__()
         self.config = config
+        config_precision(config, type(self).__name__)
         enc_layers = list(encoder.children())[:44]
         self.enc_1 = KernelSequential(*enc_layers[:4])
         self.enc_2 = KernelSequential(*enc_layers[4:11])

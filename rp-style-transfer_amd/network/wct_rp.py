@@ -20,7 +20,7 @@ from rpst.plan import KernelSequential
 
 from .adain_rp import AdaINRPNet, encode_both  # noqa: F401 (re-export, wct_rp.py:3)
 from .base import (BaseNet, build_decrease_depth_rp_blocks, build_increase_depth_rp_blocks,
-                   calc_mean_std, mse)
+                   calc_mean_std, config_precision, mse)
 
 
 # RPST_FUSE_WCT=0 disables the fused path (A/B measurements, debugging)
@@ -88,6 +88,7 @@ class WCTRPNet(BaseNet):
         super().__init__()
         enc_layers = list(vgg_encoder.children())
         self.config = config
+        config_precision(config, type(self).__name__)
         self.enc_1 = KernelSequential(*enc_layers[:4])
         self.enc_2 = KernelSequential(*enc_layers[4:11])
         self.enc_3 = KernelSequential(*enc_layers[11:18])

@@ -594,6 +594,69 @@ def conv2d_stats(x: torch.Tensor, packed: torch.Tensor, bias: Optional[torch.Ten
     return out, mean, std
 
 
+# ---- opt-in bf16 inference: the 3x3 conv on the bf16 MFMA (rpst_conv2d_bf16) --------------
+def conv2d_bf16_supports(cout: int, cin: int, ksize: int = 3, pad: int = PAD_ZERO,
+                         in_op: int = IN_NONE) -> bool:
+    """True when a plan lowered with precision="bf16" sends this conv to conv2d_bf16
+    (rpst_conv2d_bf16_supports: host only)."""
+    return bool(_lib.load().rpst_conv2d_bf16_supports(cout, cin, ksize, pad, in_op))
+
+
+def pack_conv_weight_bf16(weight: torch.Tensor) -> torch.Tensor:
+    """(Cout,Cin,3,3) fp32 weights rounded once to bf16 (nearest even) in conv2d_bf16's layout
+    [Cin/16][9][Cout_pad][16]: a flat bfloat16 tensor (rpst_conv2d_bf16_pack)."""
+    _check(weight)
+    weight = _c(weight.detach())
+    cout, cin, kh, kw = weight.shape
+    nbytes = _lib.load().rpst_conv2d_bf16_packed_size(cout, cin) if kh == kw == 3 else 0
+    if not nbytes:
+        raise ValueError(f"rpst: conv2d_bf16 has no kernel for {tuple(weight.shape)} weights "
+                         "(3x3, Cin a multiple of 16 in [16, 256], Cout >= 16)")
+    packed = torch.empty(nbytes // 2, device=weight.device, dtype=torch.bfloat16)
+    _lib.call("rpst_conv2d_bf16_pack", weight.data_ptr(), packed.data_ptr(), cout, cin,
+              _stream(weight))
+    return packed
+
+
+def conv2d_bf16(x: torch.Tensor, packed: torch.Tensor, bias: Optional[torch.Tensor], cout: int,
+                pad: int = PAD_ZERO, in_op: int = IN_NONE, relu=False,
+                aux: Optional[torch.Tensor] = None, x2: Optional[torch.Tensor] = None,
+                stats: bool = False, eps: float = 1e-5, store_n: Optional[int] = None):
+    """act(conv3x3(in_op(x)) + bias) with bf16 operands and fp32 accumulation
+    (rpst_conv2d_bf16): x and the result are fp32; x (after the AdaIN affine under IN_ADAIN,
+    aux = adain_params(...)) and the weights are each rounded once to bf16. packed:
+    pack_conv_weight_bf16(weight). x2: the conv runs over cat([x, x2]) read in place. stats:
+    also calc_mean_std of the output from the epilogue -> (out, mean, std); store_n as
+    conv2d_stats. A layer the kernel does not run raises (no fp32 fallback)."""
+    x, (n, cin, h, w) = _conv_in(x, x2, bias, aux)
+    _check(packed, dtype=torch.bfloat16)
+    n1 = n
+    if x2 is not None:
+        assert x2.dim() == 4 and tuple(x2.shape[1:]) == (cin, h, w)
+        x2 = _c(x2)
+        n += x2.shape[0]
+    if aux is not None:
+        aux = _c(aux)
+        assert aux.numel() == 4 * n * cin, "ADAIN aux = [mean_c|mean_s|std_c|std_s]"
+    if store_n is not None and not stats:
+        raise ValueError("rpst: conv2d_bf16's store_n goes with stats=True")
+    out = _conv_out(x, (n, cout, h, w))
+    mean = std = ws_t = None
+    nbytes = 0
+    if stats:
+        mean = torch.empty((n, cout, 1, 1), device=x.device, dtype=torch.float32)
+        std = torch.empty_like(mean)
+        ws_t, nbytes = _lib.workspace("conv2d_bf16", x, n, cin, h, w, cout)
+    moved = x.numel() + (0 if x2 is None else x2.numel()) + out.numel()
+    with _conv_traced((n, cin, h, w), cout, 3, in_op, moved,
+                      f"bf16conv3x3 {cin}->{cout} {h}x{w} N{n} op{in_op}"):
+        _lib.call("rpst_conv2d_bf16", x.data_ptr(), _ptr(x2), n1, _ptr(aux), packed.data_ptr(),
+                  _bias_ptr(bias), out.data_ptr(), n, cin, h, w, cout, pad, in_op, _act(relu),
+                  _ptr(mean), _ptr(std), eps, n if store_n is None else int(store_n),
+                  _ptr(ws_t), nbytes, _stream(x))
+    return (out, mean, std) if stats else out
+
+
 def se_gate(mean_h2: torch.Tensor, w3: torch.Tensor, b3: torch.Tensor, fc_a: torch.Tensor,
             fc_b: torch.Tensor) -> torch.Tensor:
     """SE gate (network/attention.py:17-22 on conv3's pooled output): mean_h2 (N, C[, 1, 1]),

@@ -155,18 +155,23 @@ def cached(module: nn.Module, attr: str, key, make):
     return value
 
 
-def packed_weight(conv: nn.Conv2d, flip: bool = False) -> torch.Tensor:
+def packed_weight(conv: nn.Conv2d, flip: bool = False, bf16: bool = False) -> torch.Tensor:
     """conv.weight in its kernel's K-major layout (rpst_conv7's for a 7x7 conv, else the conv /
     Winograd kernels'), cached on the module. flip: of the flip-transposed weights (Cin, Cout,
-    k, k) instead, which are the weights of the conv's dgrad."""
+    k, k) instead, which are the weights of the conv's dgrad. bf16: conv2d_bf16's bf16 image
+    instead, cached beside the fp32 one under the same key."""
     def make():
         w = conv.weight.detach()
+        if bf16:
+            return ops.pack_conv_weight_bf16(w)
         if flip:
             w = ops.conv_weight_flip(w)
         return (ops.pack_conv7_weight if w.shape[2] == 7 else ops.pack_conv_weight)(w)
 
-    return cached(conv, "_rpst_flip_packed" if flip else "_rpst_packed",
-                  _tensor_key(conv.weight), make)
+    if bf16 and flip:
+        raise NotImplementedError("rpst plan: no bf16 image of the flip-transposed weights")
+    attr = "_rpst_packed_bf16" if bf16 else ("_rpst_flip_packed" if flip else "_rpst_packed")
+    return cached(conv, attr, _tensor_key(conv.weight), make)
 
 
 def fold_batchnorm(conv: nn.Conv2d, bn: nn.BatchNorm2d):
@@ -223,13 +228,20 @@ def conv(step_or_conv, x: torch.Tensor, *, op: Optional[str] = None, pad=None, i
     pad / in_op / relu override the step's. op: the ops wrapper that runs (default conv2d, or
     conv2d_k7 for a 7x7 conv); operands are that wrapper's own (aux, residual, out,
     out_channel_offset, x2, store_n, fold; content for conv2d_skip_adain, mix = (T, c) for
-    conv2d_mix). flip: the conv's dgrad instead: flip-transposed weights, no bias."""
+    conv2d_mix). flip: the conv's dgrad instead: flip-transposed weights, no bias. op
+    "conv2d_bf16": the bf16 kernel on the bf16 weight image; operands aux / x2, and store_n
+    (its presence asks for the statistics epilogue, its value may be None)."""
     s = step_or_conv if isinstance(step_or_conv, ConvStep) else ConvStep(
         step_or_conv, ops.PAD_ZERO, ops.IN_NONE, ops.ACT_NONE)
     c = s.conv
     pad = s.pad if pad is None else pad
     in_op = s.in_op if in_op is None else in_op
     relu = s.relu if relu is None else relu
+    if op == "conv2d_bf16":
+        return ops.conv2d_bf16(x, packed_weight(c, bf16=True), c.bias, c.out_channels, pad=pad,
+                               in_op=in_op, relu=relu, aux=operands.get("aux"),
+                               x2=operands.get("x2"), stats="store_n" in operands,
+                               store_n=operands.get("store_n"))
     w = (packed_weight(c, flip),) + ((None, c.in_channels) if flip else (c.bias, c.out_channels))
     if c.kernel_size[0] == 7:
         if in_op != ops.IN_NONE or any(operands.get(k) is not None for k in ("aux", "residual")):
@@ -246,6 +258,9 @@ def conv(step_or_conv, x: torch.Tensor, *, op: Optional[str] = None, pad=None, i
     return getattr(ops, op or "conv2d")(x, *w, pad=pad, in_op=in_op, relu=relu, **operands)
 
 
+PRECISIONS = ("fp32", "bf16")
+
+
 @dataclass
 class Launch:
     """One record of lower()'s launch list."""
@@ -257,10 +272,16 @@ class Launch:
 
 
 def lower(steps: List[object], shape, x2_shape=None, *, first_in_op=None,
-          first_mix: bool = False, stats_last: bool = False) -> List[Launch]:
+          first_mix: bool = False, stats_last: bool = False,
+          precision: str = "fp32") -> List[Launch]:
     """The launches run() performs for a compiled plan on an input of `shape` (over the batch
     [x; x2] with x2_shape), in order. Host only: no tensor, no device, the library's algorithm
-    queries alone. Every refusal of run() is raised here, before any launch."""
+    queries alone. Every refusal of run() is raised here, before any launch.
+    precision "bf16": a plain, paired, AdaIN-loading or statistics conv step that
+    ops.conv2d_bf16_supports accepts becomes op "conv2d_bf16" with the same operands (takes);
+    every other step, and everything under "fp32", lowers as it always has."""
+    if precision not in PRECISIONS:
+        raise ValueError(f"rpst plan: precision must be one of {PRECISIONS}, got {precision!r}")
     n, cin, h, w = shape
     s0 = steps[0] if steps else None
     if is_k7(s0) and (first_in_op is not None or first_mix):
@@ -323,18 +344,21 @@ def lower(steps: List[object], shape, x2_shape=None, *, first_in_op=None,
                 rec.op, rec.takes = "conv2d_skip_adain", ("content", "aux")
             elif last:
                 rec.op, rec.takes = "conv2d_stats", rec.takes + ("store_n",)
+        if (precision == "bf16" and rec.op in ("conv2d", "conv2d_pair", "conv2d_stats")
+                and ops.conv2d_bf16_supports(cout, cin, k, s.pad, rec.in_op)):
+            rec.op = "conv2d_bf16"
         out.append(rec)
         cin, (h, w) = cout, ops.conv_out_hw(h, w, rec.in_op)
         if rec.pooled:
             h, w = ops.conv_out_hw(h, w, ops.IN_MAXPOOL2)
-    if stats_last and not (out and out[-1].op == "conv2d_stats"):
+    if stats_last and not (out and "store_n" in out[-1].takes):
         out.append(Launch("calc_mean_std"))
     return out
 
 
 def run(steps: List[object], x: torch.Tensor, first_aux=None, first_in_op=None,
         stats_last: bool = False, first_content=None, first_mix=None, store_n=None,
-        x2: Optional[torch.Tensor] = None):
+        x2: Optional[torch.Tensor] = None, precision: str = "fp32"):
     """Run a compiled plan: perform lower()'s launch list. first_in_op/first_aux override the
     first conv's input operator (e.g. RPST_IN_ADAIN to fuse AdaIN into the decoder's first
     conv; RPST_IN_ADD_ADAIN with first_content = the skip feature, for x + AdaIN(content));
@@ -344,11 +368,12 @@ def run(steps: List[object], x: torch.Tensor, first_aux=None, first_in_op=None,
     needed only through their statistics; their part of x is unspecified). x2: the plan runs
     over the batch cat([x, x2]); a plain first conv reads both in place (rpst_conv2d_pair, or
     rpst_conv7's second input for a 7x7 conv over two equal halves), any other first step
-    gets the concatenation."""
+    gets the concatenation. precision: lower()'s; "bf16" is for inference only."""
     given = dict(aux=first_aux, content=first_content, mix=first_mix, store_n=store_n, x2=x2)
     mean = std = None
     for rec in lower(steps, x.shape, None if x2 is None else x2.shape, first_in_op=first_in_op,
-                     first_mix=first_mix is not None, stats_last=stats_last):
+                     first_mix=first_mix is not None, stats_last=stats_last,
+                     precision=precision):
         if rec.op == "cat":
             x = torch.cat([x, x2], dim=0)
         elif rec.op == "calc_mean_std":
@@ -358,7 +383,7 @@ def run(steps: List[object], x: torch.Tensor, first_aux=None, first_in_op=None,
         else:
             x = conv(rec.step, x, op=rec.op, in_op=rec.in_op,
                      **{k: given[k] for k in rec.takes})
-            if rec.op == "conv2d_stats":
+            if "store_n" in rec.takes:
                 x, mean, std = x
     return (x, mean, std) if stats_last else x
 

@@ -10,6 +10,10 @@ stylises every pair of `test_dir` into `<output>/test/test_output/{cn}-{sn}.png`
 ToTensor and save_image's pixel path on the GPU). With `use_mask: True` and
 `test_dataset: photoreal` the pipeline also decodes each pair's two segmentation masks and
 `src` / `multi_adain` / `ld_adain` / `ld_adain4` stylise per label.
+One key the reference does not have: `precision: bf16` (default `fp32`) with `network: adain`
+runs the RP stacks' layers of 64 or more output channels on the bf16 MFMA (AdaINRPNet.test();
+fp32 activations in memory, bf16 operands, fp32 accumulation; DESIGN.md "bf16 inference").
+Every other network raises NotImplementedError for it, any other value is a ValueError.
 
 Differences from test.py, by design: no TensorBoard writer, no per-step cv2 import, the
 test.py:135 `iterations=i` NameError is not reproduced (iterations=0 is passed), and
